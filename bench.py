@@ -5,6 +5,10 @@ One process per GPU (`python -m torch.distributed.run --nproc-per-node N bench.p
 one camera stream per GPU (weak scaling, no data-path collective); the gallery shards are
 all-gathered once over RCCL at setup.  Frames are resident in HBM when the
 timed region starts.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`).
+--full adds the per-kernel figures, the side lines and the CPU baseline; --dump-outputs DIR writes
+the results of the last timed step.  Inputs are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -122,6 +126,26 @@ def gallery_rows(n_total, first, count, seed=42):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20         # under 64 MB with the .npy headers, whichever MB is meant
+
+
+def dump_outputs(out_dir, res):
+    """--dump-outputs: the arrays one step handed its caller (boxes, kps, scores, counts, emb, match_idx, match_cos; frame
+    axis first), one <name>.npy each under out_dir, float32 - integer arrays as float64, which holds them exactly.  Beyond
+    DUMP_LIMIT_BYTES in all, every array keeps the same seeded sample of frames, whose indices go to frame_index.npy."""
+    arrays = {k: v.astype(np.float64 if v.dtype.kind in "iu" else np.float32) for k, v in res.items()}
+    B = len(arrays["counts"])
+    per_frame = sum(a.nbytes for a in arrays.values()) / max(1, B) + 8
+    keep = int(DUMP_LIMIT_BYTES // per_frame)
+    if keep < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["frame_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def cpu_baseline(raw, frames, K, n_gallery, sample_frames):
     """Bounded CPU sample of the same workload on this box's host cores: the fp32 oracle
     network (torch-CPU, all cores) + the reference's own per-face compare loop
@@ -185,6 +209,7 @@ def run_config4(args, json_fd):
 
     import threading
     faces_of = [0] * L
+    final = [None]          # results of step n_steps - 1 of the latest run_steps (--dump-outputs)
 
     def lane_loop(i, counter, n_steps):
         with lanes[i].sequence():
@@ -192,8 +217,12 @@ def run_config4(args, json_fd):
                 with counter["lock"]:
                     if counter["next"] >= n_steps:
                         return
+                    mine = counter["next"]
                     counter["next"] += 1
-                faces_of[i] += int(step(lanes[i])["counts"].sum())
+                r_ = step(lanes[i])
+                faces_of[i] += int(r_["counts"].sum())
+                if mine == n_steps - 1:
+                    final[0] = r_
 
     lane_errors = []
 
@@ -213,9 +242,9 @@ def run_config4(args, json_fd):
         if lane_errors:
             raise lane_errors[0]
 
-    # the stage times come from one batch at a time on lane 0 (kernels of two lanes share the chip otherwise)
-    single = None
-    if L > 1:
+    # the stage times come from one batch at a time on lane 0 (kernels of two lanes share the chip otherwise); --full only
+    single = ctr = None
+    if L > 1 and args.full:
         eng.set_profile(True)
         with eng.sequence():
             step(eng)
@@ -240,12 +269,10 @@ def run_config4(args, json_fd):
         e_.synchronize()
     dt = time.perf_counter() - t0
     n_faces = sum(faces_of)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final[0])
     if L == 1:
         ctr = eng.counters()
-    conv_ms = ctr["ms_det_conv"] + ctr["ms_emb_conv"]
-    conv_flops = ctr["det_conv_flops"] + ctr["emb_conv_flops"]
-    achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    match_gbs = ctr["match_bytes"] / (ctr["ms_match"] * 1e-3) / 1e9 if ctr["ms_match"] > 0 else None
     line = {
         "metric": "faces/sec (detect+embed+match) on 4K pyramid @ 1M gallery (BASELINE config 4, per GPU)",
         "value": round(n_faces / dt, 2), "unit": "faces/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -256,16 +283,24 @@ def run_config4(args, json_fd):
                                f"{N}-identity fp16 gallery, host results out every step",
                    "lanes": L, "one_batch_at_a_time": single,
                    "frames_per_s": round(args.steps * B / dt, 2), "faces_per_frame_mean": round(n_faces / (args.steps * B), 2),
-                   "gflop_per_frame_detect_all_scales": round(ctr["det_conv_flops"] / max(1, args.steps * B) / 1e9, 1),
-                   "stage_ms_per_step": {k[3:]: round(ctr[k] / args.steps, 3) for k in
-                                         ("ms_preprocess", "ms_det_conv", "ms_decode", "ms_align", "ms_emb_conv", "ms_l2norm", "ms_match")}},
-        "roofline": {"bound": "mfma", "kernel": "conv family (detector at 3 scales + embedder)", "achieved": round(achieved, 2),
-                     "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": None,
-                     "kernel_source_sha256_16": native.kernel_source_hash(),
-                     "match_kernel": {"bound": "hbm", "achieved": round(match_gbs, 1) if match_gbs else None, "peak": HBM_PEAK_GBS,
-                                      "unit": "GB/s", "frac": round(match_gbs / HBM_PEAK_GBS, 4) if match_gbs else None,
-                                      "bytes_per_launch": N * 512 * 2}},
+                   "gflop_per_frame_detect_all_scales": None, "stage_ms_per_step": None},
+        "roofline": None,
     }
+    if ctr is not None:
+        conv_ms = ctr["ms_det_conv"] + ctr["ms_emb_conv"]
+        conv_flops = ctr["det_conv_flops"] + ctr["emb_conv_flops"]
+        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        match_gbs = ctr["match_bytes"] / (ctr["ms_match"] * 1e-3) / 1e9 if ctr["ms_match"] > 0 else None
+        line["config"].update({
+            "gflop_per_frame_detect_all_scales": round(ctr["det_conv_flops"] / max(1, args.steps * B) / 1e9, 1),
+            "stage_ms_per_step": {k[3:]: round(ctr[k] / args.steps, 3) for k in
+                                  ("ms_preprocess", "ms_det_conv", "ms_decode", "ms_align", "ms_emb_conv", "ms_l2norm", "ms_match")}})
+        line["roofline"] = {"bound": "mfma", "kernel": "conv family (detector at 3 scales + embedder)", "achieved": round(achieved, 2),
+                            "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": None,
+                            "kernel_source_sha256_16": native.kernel_source_hash(),
+                            "match_kernel": {"bound": "hbm", "achieved": round(match_gbs, 1) if match_gbs else None, "peak": HBM_PEAK_GBS,
+                                             "unit": "GB/s", "frac": round(match_gbs / HBM_PEAK_GBS, 4) if match_gbs else None,
+                                             "bytes_per_launch": N * 512 * 2}}
     os.write(json_fd, (json.dumps(line) + "\n").encode())
     for e_ in lanes:
         e_.close()
@@ -336,7 +371,16 @@ def main():
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU: run only the multi-rank plumbing of this command (launcher, rendezvous, stream -> rank split, gallery "
                          "shard all-gather, JSON line) on the gloo backend; `value` is null.  What tests/test_bench_launcher.py drives")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the one-batch-at-a-time per-kernel measurement (roofline and "
+                         "stage times with more than one lane), the host-to-host / JPEG / threshold-mode / service side lines and the CPU "
+                         "baseline.  Without it --cpu-frames, --pcie-steps, --jpeg-steps and --threshold-steps are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy (float32, integer "
+                         "arrays as float64; at most 64 MB, a fixed sample of the frames beyond that)")
     args = ap.parse_args()
+    if not args.full:
+        args.cpu_frames = args.pcie_steps = args.jpeg_steps = args.threshold_steps = 0
 
     # Everything except the final JSON line goes to stderr: RCCL prints a version banner on the
     # stdout file descriptor when its communicator is created.
@@ -440,9 +484,10 @@ def main():
             e_.synchronize()
 
     # Per-kernel measurement (before the timed region): K steps one batch at a time on lane 0 with the stage timers on
-    # (HIP events on the stream the kernels run on).  With one lane the timed region itself is that measurement.
-    single = None
-    if L > 1:
+    # (HIP events on the stream the kernels run on).  With one lane the timed region itself is that measurement; with more
+    # it runs under --full only, and a plain run's line has no per-kernel figures (roofline, stage times: null).
+    single = ctr = None
+    if L > 1 and args.full:
         eng.set_profile(True)
         eng.process_resident(K, flags=flags)      # (first use of the timers: untimed)
         eng.fetch_results()
@@ -468,6 +513,7 @@ def main():
     # the favoured lane sat idle until its turn came.)
     import threading
     last = [None] * L
+    final = [None]          # results of step n_steps - 1 of the latest run_steps, whichever lane took it (--dump-outputs)
 
     lane_errors = []
 
@@ -501,6 +547,8 @@ def main():
             lanes[i].process_resident(K, flags=flags)
             tb = time.perf_counter()
             last[i] = lanes[i].fetch_results()
+            if mine == n_steps - 1:
+                final[0] = last[i]
             if step_trace is not None:
                 step_trace.append((i, mine, ta, tb, time.perf_counter()))
 
@@ -543,6 +591,8 @@ def main():
         per_rank = [round(args.steps * B * K / float(x.item()), 1) for x in every]     # each rank's own clock
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final[0])
     # The same with HOST frames every step (never `value`): each lane's thread uploads its batch from page-locked memory
     # on its own stream (the copy runs under the other lane's kernels), processes it and fetches the results.
     h2h_lanes = None
@@ -780,10 +830,6 @@ def main():
 
     if rank == 0:
         faces_total = world * args.steps * B * K
-        conv_ms = ctr["ms_det_conv"] + ctr["ms_emb_conv"]
-        conv_flops = ctr["det_conv_flops"] + ctr["emb_conv_flops"]
-        launches = ctr["det_conv_launches"] + ctr["emb_conv_launches"]
-        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
         f8 = args.weights == "fp8-mfma"
         out = {
             "metric": ("faces/sec (detect+embed+match) on 720p mixed streams @ 100k gallery, fp8 embedder (BASELINE config 5, per GPU)"
@@ -807,38 +853,45 @@ def main():
                        "lanes": L, "lane_warmup_steps": (max(args.warmup, LANE_SETTLE_STEPS) if L > 1 else args.warmup), "one_batch_at_a_time": single,
                        "host_to_host": pcie, "host_to_host_lanes": h2h_lanes, "jpeg_to_host_lanes": jpeg_lanes,
                        "threshold_mode": thr, "threshold_mode_lanes": thr_lanes, "service_api": svc_line,
-                       "gflop_per_frame_detect": round(ctr["det_conv_flops"] / max(1, ctr["frames"]) / 1e9, 2),
-                       "gflop_per_face_embed": round(ctr["emb_conv_flops"] / max(1, ctr["faces"]) / 1e9, 3),
-                       "stage_ms_per_step": {k[3:]: round(ctr[k] / args.steps, 3) for k in
-                                             ("ms_preprocess", "ms_det_conv", "ms_decode", "ms_align", "ms_emb_conv",
-                                              "ms_l2norm", "ms_match")}},
-            "roofline": {"bound": "mfma", "kernel": "conv3x3_lean_kernel + conv3x3_wino2_kernel + conv3x3_c64_kernel + conv_mfma_kernel + stem12_u8_kernel + emb_stem_kernel (conv family, all detector+embedder launches; FLOPs = the direct convolution's algorithmic count, also for the Winograd launches)",
-                         "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
-                         "traffic": pmc_conv_traffic_per_launch(launches // max(1, args.steps)),
-                         "traffic_source": PMC_SUMMARY + " (same native sources: hash-checked)",
-                         "kernel_source_sha256_16": native.kernel_source_hash(),
-                         "launches_per_step": launches // max(1, args.steps),
-                         "avg_launch_us": round(conv_ms * 1e3 / max(1, launches), 2),
-                         "algorithmic_gflop_per_step": round(conv_flops / args.steps / 1e9, 1),
-                         "measured_on": ("the timed region" if L == 1 else
-                                         "lane 0 running the same steps one batch at a time just before the timed region (config.one_batch_at_a_time): with "
-                                         f"{L} batches in flight kernels of different streams share the chip and their durations overlap"),
-                         "chip_level_timed_region": None if L == 1 else {
-                             "achieved": round(conv_flops / args.steps / (dt / args.steps) / 1e12, 2),
-                             "frac": round(conv_flops / args.steps / (dt / args.steps) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                             "note": "conv FLOPs of a step / wall time of a step in the timed region (charges the conv family "
-                                     "for the decode / align / match time as well: a lower bound)"},
-                         "match_hbm_GBs": round(ctr["match_bytes"] / (ctr["ms_match"] * 1e-3) / 1e9, 1) if ctr["ms_match"] > 0 else None},
+                       "gflop_per_frame_detect": None, "gflop_per_face_embed": None, "stage_ms_per_step": None},
+            "roofline": None,
         }
-        if f8:      # the embedder family against the fp8 matrix peak (its fp16 launches included: a lower bound)
-            MFMA_PEAK_FP8 = 5000.0
-            emb_tf = ctr["emb_conv_flops"] / (ctr["ms_emb_conv"] * 1e-3) / 1e12 if ctr["ms_emb_conv"] > 0 else 0.0
-            out["roofline_fp8_embedder"] = {
-                "bound": "mfma", "kernel": "embedder conv family (conv3x3_lean_kernel<F8> on E4M3 operands + its fp16 launches)",
-                "achieved": round(emb_tf, 2), "peak": MFMA_PEAK_FP8, "unit": "TFLOP/s", "frac": round(emb_tf / MFMA_PEAK_FP8, 4),
-                "fp8_share_of_embedder_flops": round(ctr["f8_conv_flops"] / max(1.0, ctr["emb_conv_flops"]), 4),
-                "fp8_launches_per_step": ctr["f8_conv_launches"] // max(1, args.steps)}
+        if ctr is not None:         # per-kernel figures: the timed region's own with one lane, config.one_batch_at_a_time's (--full) with more
+            conv_ms = ctr["ms_det_conv"] + ctr["ms_emb_conv"]
+            conv_flops = ctr["det_conv_flops"] + ctr["emb_conv_flops"]
+            launches = ctr["det_conv_launches"] + ctr["emb_conv_launches"]
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            out["config"].update({
+                "gflop_per_frame_detect": round(ctr["det_conv_flops"] / max(1, ctr["frames"]) / 1e9, 2),
+                "gflop_per_face_embed": round(ctr["emb_conv_flops"] / max(1, ctr["faces"]) / 1e9, 3),
+                "stage_ms_per_step": {k[3:]: round(ctr[k] / args.steps, 3) for k in
+                                      ("ms_preprocess", "ms_det_conv", "ms_decode", "ms_align", "ms_emb_conv", "ms_l2norm", "ms_match")}})
+            out["roofline"] = {"bound": "mfma", "kernel": "conv3x3_lean_kernel + conv3x3_wino2_kernel + conv3x3_c64_kernel + conv_mfma_kernel + stem12_u8_kernel + emb_stem_kernel (conv family, all detector+embedder launches; FLOPs = the direct convolution's algorithmic count, also for the Winograd launches)",
+                               "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / MFMA_PEAK_TFLOPS, 4),
+                               "traffic": pmc_conv_traffic_per_launch(launches // max(1, args.steps)),
+                               "traffic_source": PMC_SUMMARY + " (same native sources: hash-checked)",
+                               "kernel_source_sha256_16": native.kernel_source_hash(),
+                               "launches_per_step": launches // max(1, args.steps),
+                               "avg_launch_us": round(conv_ms * 1e3 / max(1, launches), 2),
+                               "algorithmic_gflop_per_step": round(conv_flops / args.steps / 1e9, 1),
+                               "measured_on": ("the timed region" if L == 1 else
+                                               "lane 0 running the same steps one batch at a time just before the timed region (config.one_batch_at_a_time): with "
+                                               f"{L} batches in flight kernels of different streams share the chip and their durations overlap"),
+                               "chip_level_timed_region": None if L == 1 else {
+                                   "achieved": round(conv_flops / args.steps / (dt / args.steps) / 1e12, 2),
+                                   "frac": round(conv_flops / args.steps / (dt / args.steps) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                                   "note": "conv FLOPs of a step / wall time of a step in the timed region (charges the conv family "
+                                           "for the decode / align / match time as well: a lower bound)"},
+                               "match_hbm_GBs": round(ctr["match_bytes"] / (ctr["ms_match"] * 1e-3) / 1e9, 1) if ctr["ms_match"] > 0 else None}
+            if f8:      # the embedder family against the fp8 matrix peak (its fp16 launches included: a lower bound)
+                MFMA_PEAK_FP8 = 5000.0
+                emb_tf = ctr["emb_conv_flops"] / (ctr["ms_emb_conv"] * 1e-3) / 1e12 if ctr["ms_emb_conv"] > 0 else 0.0
+                out["roofline_fp8_embedder"] = {
+                    "bound": "mfma", "kernel": "embedder conv family (conv3x3_lean_kernel<F8> on E4M3 operands + its fp16 launches)",
+                    "achieved": round(emb_tf, 2), "peak": MFMA_PEAK_FP8, "unit": "TFLOP/s", "frac": round(emb_tf / MFMA_PEAK_FP8, 4),
+                    "fp8_share_of_embedder_flops": round(ctr["f8_conv_flops"] / max(1.0, ctr["emb_conv_flops"]), 4),
+                    "fp8_launches_per_step": ctr["f8_conv_launches"] // max(1, args.steps)}
         if dist is not None:       # (single-process runs keep the line byte-compatible: no extra keys)
             out["config"]["rccl_ranks"] = rccl_ranks
             out["config"]["gallery_allgather"] = gather_path

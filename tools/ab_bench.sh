@@ -8,7 +8,7 @@ cd "$root"
 for r in $(seq 1 $rounds); do
   for v in A B; do
     if [ $v = A ]; then export FRP_LIB=$root/face-recognition-platform_amd/libfrp_base.so; else unset FRP_LIB; fi
-    python bench.py --steps 20 --warmup 3 --cpu-frames 0 --pcie-steps 0 --threshold-steps 0 "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 20 --warmup 3 --cpu-frames 0 --pcie-steps 0 --threshold-steps 0 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); s=d['config']['stage_ms_per_step']
 print('$v', 'ms/step %.3f' % d['ms_per_step'], 'det %.3f emb %.3f' % (s['det_conv'], s['emb_conv']), 'conv TF %.1f' % d['roofline']['achieved'])"

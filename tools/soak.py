@@ -8,7 +8,7 @@ import sys
 
 steps = [int(a) for a in sys.argv[1:]] or [300, 3000]
 for n in steps:
-    code = ("import resource, runpy, sys; sys.argv = ['bench.py', '--steps', '%d', '--cpu-frames', '0', '--pcie-steps', '0', '--threshold-steps', '0'];"
+    code = ("import resource, runpy, sys; sys.argv = ['bench.py', '--full', '--steps', '%d', '--cpu-frames', '0', '--pcie-steps', '0', '--threshold-steps', '0'];"
             "\ntry:\n    runpy.run_path('bench.py', run_name='__main__')\nexcept SystemExit:\n    pass\n"
             "print('RSS_MIB', resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024, file=sys.stderr)") % n
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

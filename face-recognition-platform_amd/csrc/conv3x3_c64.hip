@@ -350,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(ConvParams p_in) {
     // Measured (tools/c64_pingpong_probe.py, same process): 272 x 480 with residual 404 -> 383 us, without 344 -> 338, in the pipeline the
     // detector -37 us per step.  The fused-stem variant does NOT take it (its late waves' accumulators next to the stem phase's registers:
     // 13 spilled registers, embedder +35 us): there the stem phase alone is dealt to the two halves of the iteration.
-    const bool late = !STEM && wave >= 4 && !(p.dbg & 4096);   // (dbg bit 4096 = flags bit 22 of frp_conv2d_nhwc / frp_conv_bench: all waves in the same order - A/B runs)
+    const bool late = !STEM && wave >= 4 && !(p.dbg & CONV_DBG_C64_SAME_ORDER);   // (A/B runs: flags bit 22 of frp_conv2d_nhwc / frp_conv_bench)
     const bool stem_first = STEM && wave < 4;
     int slot = 0, it = 0;
     for (int ct = t0; ct < t1; ct += tstep, ++it) {
@@ -456,10 +456,9 @@ bool conv3x3_c64_eligible(const ConvParams& p) {
     if (c64_tiles(p, tw) < 2L * (p.n_cu > 0 ? p.n_cu : 256)) return false;
     // where it pays (tools/c64_probe.py, profiles/r5/c64_probe.txt): x1.11 / x1.14 over the row-patch kernel on maps whose tiles are all
     // full (the detector's 272 x 480 in 32 x 8 tiles, the embedder's 112 x 112 in 16 x 16 tiles); x0.99-1.03 on its 56 x 56 maps, where
-    // either geometry leaves an eighth of the tile pixels empty - those stay on the row-patch kernel (FRP_C64_ALL=1 takes every
+    // either geometry leaves an eighth of the tile pixels empty - those stay on the row-patch kernel (CONV_DBG_C64_ALL takes every
     // eligible shape: the parity tests)
-    static const bool all = getenv("FRP_C64_ALL") != nullptr;
-    return all || fill >= 0.95;
+    return (p.dbg & CONV_DBG_C64_ALL) || fill >= 0.95;
 }
 
 template <int ACT, bool RES, bool BORDER, int TW, bool STEM = false>

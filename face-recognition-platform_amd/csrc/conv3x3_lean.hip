@@ -473,7 +473,7 @@ static hipError_t launch_lean_cfg(const ConvParams& p0, hipStream_t stream) {
     // a launch of at most 128 tiles (a call of up to ~20 faces: where the latency of ONE call is what counts) leaves three quarters
     // of the slots empty: 64 more workgroups warm the L2s for the next launch.  Larger quarter-tile launches (config 4's ~36 faces
     // on two lanes) keep their spare CUs for the other lane's kernels: there the prefetchers cost 4 % of the throughput.
-    if (TP == 128 && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots && conv_prefetch_enabled()) {
+    if (TP == 128 && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots) {
         p.n_workers = (int)grid;
         grid += CONV_PF_WGS;
     }
@@ -508,8 +508,8 @@ hipError_t launch_conv3x3_lean(const ConvParams& p, hipStream_t stream) {
         if (conv_small_m(p, def_tiles, ncu)) return launch_lean_cfg<64, 4, 2, false, 128>(p, stream);
     }
     if (p.Cout > 64) return launch_lean_cfg<128, 4, 2, false, 256>(p, stream);
-    if (p.dbg & 128) return launch_lean_cfg<64, 8, 1, false, 256>(p, stream);      // A/B: the 256-pixel tile (1.5 reads per MFMA)
-    if (p.Cout <= 32 && !(p.dbg & 64)) return launch_lean_cfg<64, 8, 1, false, 512, 32>(p, stream);   // head outputs (dbg 64: A/B, all 64 rows)
+    if (p.dbg & CONV_DBG_LEAN_TILE256) return launch_lean_cfg<64, 8, 1, false, 256>(p, stream);                      // (A/B)
+    if (p.Cout <= 32 && !(p.dbg & CONV_DBG_LEAN_ALL_ROWS)) return launch_lean_cfg<64, 8, 1, false, 512, 32>(p, stream);   // head outputs
     return launch_lean_cfg<64, 8, 1, false, 512>(p, stream);
 }
 

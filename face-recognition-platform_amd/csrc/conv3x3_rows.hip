@@ -555,8 +555,8 @@ static hipError_t launch_rows_cfg(const ConvParams& p0, hipStream_t stream) {
 hipError_t launch_conv3x3_rows(const ConvParams& p, hipStream_t stream) {
     if (!conv3x3_rows_eligible(p)) return hipErrorInvalidValue;
     if (p.out2) return launch_conv3x3_lean(p, stream);   // the fp8-copy epilogue lives in the static-loop generation only
-    // dbg bits 2..5: timing-only ablations of the 128-cout kernel (wrong results; conv_bench only)
-    if (p.Cout > 64) switch ((p.dbg >> 2) & 15) {
+    // timing-only ablations of the 128-cout kernel (wrong results; conv_bench only)
+    if (p.Cout > 64) switch (conv_dbg_field(p.dbg, CONV_DBG_ROWS_ABLATION)) {
         case 1: return launch_rows_cfg<128, 4, 2, false, 1>(p, stream);
         case 2: return launch_rows_cfg<128, 4, 2, false, 2>(p, stream);
         case 4: return launch_rows_cfg<128, 4, 2, false, 4>(p, stream);
@@ -569,12 +569,12 @@ hipError_t launch_conv3x3_rows(const ConvParams& p, hipStream_t stream) {
         case 10: return launch_rows_cfg<128, 4, 2, false, 10>(p, stream);
         default: break;
     }
-    // dbg bit 2 (value 2): the pre-prefetch k-step (A/B runs, bit-identical results)
-    if (p.dbg & 2) {
+    // the pre-prefetch k-step (A/B runs, bit-identical results)
+    if (p.dbg & CONV_DBG_ROWS_PRE_PREFETCH) {
         if (p.Cout > 64) return launch_rows_cfg<128, 4, 2, false>(p, stream);
         return launch_rows_cfg<64, 8, 1, false>(p, stream);
     }
-    if (p.dbg & 64) {                              // first-generation kernel with the cross-barrier prefetch
+    if (p.dbg & CONV_DBG_ROWS_GEN1) {                // first-generation kernel with the cross-barrier prefetch
         if (p.Cout > 64) return launch_rows_cfg<128, 4, 2, true>(p, stream);
         return launch_rows_cfg<64, 8, 1, true>(p, stream);
     }

@@ -1041,9 +1041,9 @@ static int wino_form(const ConvParams& p) {
     if (p.KS != 3 || p.stride != 1 || (p.Cin & 63) || p.ksplit != 1 || (p.W & 1) || p.W < 2) return 0;
     if (p.Ho != p.H || p.Wo != p.W) return 0;
     if (p.flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_F8 | FRP_FLAG_OUT_FP8 | FRP_FLAG_RES_UP2) || p.out2) return 0;
-#ifdef FRP_LAB    // dbg bit 256 (conv2d / conv_bench flags bit 19): the 2-D tiles whatever the shape; dbg bit 64: the first generation's
-    if ((p.dbg & 256) && !p.n_dev && conv3x3_wino_lab_shape_ok(p.W, p.Cin, p.KS, p.stride)) return 2;      // row-patch form for wide maps
-    if ((p.dbg & 64) && conv3x3_wino_lab_shape_ok(p.W, p.Cin, p.KS, p.stride)) return 1;                   // (slower than the direct kernel)
+#ifdef FRP_LAB    // the 2-D tiles whatever the shape (conv2d / conv_bench flags bit 19); the first generation's row-patch form for wide maps
+    if ((p.dbg & CONV_DBG_WINO_2D) && !p.n_dev && conv3x3_wino_lab_shape_ok(p.W, p.Cin, p.KS, p.stride)) return 2;
+    if ((p.dbg & CONV_DBG_WINO_ROW_PATCH) && conv3x3_wino_lab_shape_ok(p.W, p.Cin, p.KS, p.stride)) return 1;   // (slower than the direct kernel)
 #endif
     if (!p.wino_wide_only && conv3x3_wino_shape_ok(p.W, p.Cin, p.KS, p.stride)) return 1;
     return wino_2d_pays(p) ? 2 : 0;
@@ -1062,7 +1062,7 @@ bool conv3x3_wino_shape_ok(int W, int Cin, int ksize, int stride) {
     return ksize == 3 && stride == 1 && !(Cin & 63) && !(W & 1) && W >= 2 && wino_super_patch(W);
 }
 #ifdef FRP_LAB
-bool conv3x3_wino_lab_shape_ok(int W, int Cin, int ksize, int stride) {      // + wide maps (row-patch form, dbg bit 64)
+bool conv3x3_wino_lab_shape_ok(int W, int Cin, int ksize, int stride) {      // + wide maps (row-patch form, CONV_DBG_WINO_ROW_PATCH)
     return ksize == 3 && stride == 1 && !(Cin & 63) && !(W & 1) && W >= 2;
 }
 #endif
@@ -1131,21 +1131,25 @@ hipError_t launch_conv3x3_wino(const ConvParams& p, hipStream_t stream) {
     const int form = wino_form(p);
     if (!form || !conv3x3_wino_eligible(p)) return hipErrorInvalidValue;
     if (form == 2) return launch_wino2_cfg<32>(p, stream);            // 2-D tiles
-#ifdef FRP_LAB   // dbg bit 128: the first generation of the k-loop (compiler-scheduled; A/B partner of the hand-ordered one)
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 13) return launch_wino2_cfg<2>(p, stream);   // sub-step stamps
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 8) return launch_wino2_cfg<64>(p, stream);   // 100 MHz phase stamps
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 14) return launch_wino2_cfg<1>(p, stream);   // waves 4-7 at priority 1
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 12) return launch_wino2_cfg<4>(p, stream);   // priority falls with progress
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 11) return launch_wino2_cfg<8>(p, stream);   // DMA by waves 0-3 only
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 10) return launch_wino2_cfg<16>(p, stream);  // ring two ahead
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && ((p.dbg >> 1) & 15) == 9) return launch_wino2_cfg<9>(p, stream);    // DMA by waves 0-3, waves 4-7 at priority 1
-    if (!(p.dbg & 128) && wino_super_patch(p.W) && !(p.dbg & (32 | 64)) && !((p.dbg >> 1) & 15)) return launch_wino2_cfg<0>(p, stream);
+#ifdef FRP_LAB   // CONV_DBG_WINO_KLOOP_GEN1: the first generation of the k-loop (compiler-scheduled; A/B partner of the hand-ordered one)
+    if (!(p.dbg & (CONV_DBG_WINO_KLOOP_GEN1 | CONV_DBG_WINO_ONE_WAVE | CONV_DBG_WINO_ROW_PATCH)) && wino_super_patch(p.W))
+        switch (conv_dbg_field(p.dbg, CONV_DBG_WINO_ABLATION)) {
+            case 13: return launch_wino2_cfg<2>(p, stream);      // sub-step stamps
+            case 8: return launch_wino2_cfg<64>(p, stream);      // 100 MHz phase stamps
+            case 14: return launch_wino2_cfg<1>(p, stream);      // waves 4-7 at priority 1
+            case 12: return launch_wino2_cfg<4>(p, stream);      // priority falls with progress
+            case 11: return launch_wino2_cfg<8>(p, stream);      // DMA by waves 0-3 only
+            case 10: return launch_wino2_cfg<16>(p, stream);     // ring two ahead
+            case 9: return launch_wino2_cfg<9>(p, stream);       // DMA by waves 0-3, waves 4-7 at priority 1
+            case 0: return launch_wino2_cfg<0>(p, stream);
+            default: break;                                      // (the other numbers: ablations of the first generation)
+        }
 #else
     return wino_super_patch(p.W) ? launch_wino2_cfg<0>(p, stream) : hipErrorInvalidValue;
 #endif
-#ifdef FRP_LAB   // dbg bit 32: the one-wave-per-SIMD configuration (A/B runs in the lab build; 0.7 x the speed of the default)
-    if ((p.dbg & 32) && wino_super_patch(p.W)) return launch_wino_cfg<4>(p, stream);
-    if (wino_super_patch(p.W)) switch ((p.dbg >> 1) & 15) {               // dbg bits 1..4: timing ablations (tools/wino_ablate.py)
+#ifdef FRP_LAB   // the one-wave-per-SIMD configuration (A/B runs in the lab build; 0.7 x the speed of the default)
+    if ((p.dbg & CONV_DBG_WINO_ONE_WAVE) && wino_super_patch(p.W)) return launch_wino_cfg<4>(p, stream);
+    if (wino_super_patch(p.W)) switch (conv_dbg_field(p.dbg, CONV_DBG_WINO_ABLATION)) {      // timing ablations (tools/wino_ablate.py)
         case 1: return launch_wino_cfg<8, 1>(p, stream);
         case 2: return launch_wino_cfg<8, 2>(p, stream);
         case 4: return launch_wino_cfg<8, 4>(p, stream);
@@ -1161,7 +1165,7 @@ hipError_t launch_conv3x3_wino(const ConvParams& p, hipStream_t stream) {
     }
 #endif
 #ifdef FRP_LAB
-    if (p.dbg & 64) return launch_wino_cfg<8, 0, true>(p, stream);     // row-patch form (first generation; wide maps, or forced for an A/B)
+    if (p.dbg & CONV_DBG_WINO_ROW_PATCH) return launch_wino_cfg<8, 0, true>(p, stream);     // row-patch form (first generation; wide maps, or forced for an A/B)
 #endif
     if (!wino_super_patch(p.W)) return hipErrorInvalidValue;
     return launch_wino_cfg<8>(p, stream);

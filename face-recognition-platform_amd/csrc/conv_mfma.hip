@@ -459,7 +459,7 @@ static hipError_t launch_cfg(const ConvParams& p0, hipStream_t stream) {
     // a launch of at most 128 tiles (a call of up to ~20 faces: where the latency of ONE call is what counts) leaves three quarters
     // of the slots empty: 64 more workgroups warm the L2s for the next launch.  Larger quarter-tile launches (config 4's ~36 faces
     // on two lanes) keep their spare CUs for the other lane's kernels: there the prefetchers cost 4 % of the throughput.
-    if (TP == 128 && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots && conv_prefetch_enabled()) {
+    if (TP == 128 && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots) {
         p.n_workers = (int)grid;
         grid += CONV_PF_WGS;
     }
@@ -533,26 +533,23 @@ hipError_t launch_conv(const ConvParams& in, hipStream_t stream) {
     const bool few = conv_small_m(p, (long)((p.M + 255) / 256) * ((p.Cout + 127) / 128), ncu_);
     // (a caller that hands over the Winograd image has chosen the kernel FAMILY - frp_api.cpp: run_embed, by the slots of the
     // call -; the tile count of a single launch does not overrule it: the families differ in the last bits)
-    if (p.wino_w && !p.x2 && !(p.dbg & 1) && conv3x3_wino_eligible(p)) {      // Winograd F(2,3) along the rows: 1.5 x fewer MFMAs
+    if (p.wino_w && !p.x2 && !(p.dbg & CONV_DBG_GENERIC) && conv3x3_wino_eligible(p)) {      // Winograd F(2,3) along the rows: 1.5 x fewer MFMAs
         p.w = p.wino_w;
         return launch_conv3x3_wino(p, stream);
     }
-    // 3x3 stride-2 layers: row patches with shared neighbour entries (conv3x3_s2.hip).  OPT-IN (dbg bit 2048: FRP_S2=1 in the engine,
+    // 3x3 stride-2 layers: row patches with shared neighbour entries (conv3x3_s2.hip).  OPT-IN (CONV_DBG_S2: FRP_S2 in the engine,
     // flags bit 21 of frp_conv2d_nhwc): on the headline shapes it measures 9-13 % SLOWER than this kernel's per-tap images
     // (profiles/r5/s2_probe.txt)
-    if ((p.dbg & 2048) && !(p.dbg & 1) && !few && conv3x3_s2_eligible(p)) return launch_conv3x3_s2(p, stream);
+    if ((p.dbg & CONV_DBG_S2) && !(p.dbg & CONV_DBG_GENERIC) && !few && conv3x3_s2_eligible(p)) return launch_conv3x3_s2(p, stream);
     // the embedder's stem fused into the conv behind it: only conv3x3_c64.hip does that (the caller asked conv3x3_c64_fuses_stem first)
     if (p.stem_x) return (p.small_m <= 0 && conv3x3_c64_eligible(p)) ? launch_conv3x3_c64(p, stream) : hipErrorInvalidValue;
-    // 64 -> 64 layers on large maps: weights in registers, 2-D tiles (conv3x3_c64.hip; dbg bit 512 / FRP_NO_C64=1: the row-patch
-    // kernel instead - A/B runs; bit-identical results either way)
-    {
-        static const bool no_c64 = getenv("FRP_NO_C64") != nullptr;
-        if (!no_c64 && !(p.dbg & (1 | 512)) && p.small_m <= 0 && conv3x3_c64_eligible(p)) return launch_conv3x3_c64(p, stream);
-    }
+    // 64 -> 64 layers on large maps: weights in registers, 2-D tiles (conv3x3_c64.hip; CONV_DBG_NO_C64: the row-patch kernel instead -
+    // A/B runs; bit-identical results either way)
+    if (!(p.dbg & (CONV_DBG_GENERIC | CONV_DBG_NO_C64)) && p.small_m <= 0 && conv3x3_c64_eligible(p)) return launch_conv3x3_c64(p, stream);
 #ifdef FRP_LAB   // lab build: dbg bits select the first-generation kernel and its timing ablations (conv3x3_rows.hip)
-    if (!(p.dbg & 1) && !p.x2 && conv3x3_rows_eligible(p)) return launch_conv3x3_rows(p, stream);
+    if (!(p.dbg & CONV_DBG_GENERIC) && !p.x2 && conv3x3_rows_eligible(p)) return launch_conv3x3_rows(p, stream);
 #else
-    if (!(p.dbg & 1) && !p.x2 && conv3x3_rows_eligible(p)) return launch_conv3x3_lean(p, stream);
+    if (!(p.dbg & CONV_DBG_GENERIC) && !p.x2 && conv3x3_rows_eligible(p)) return launch_conv3x3_lean(p, stream);
 #endif
     // Tile selection (measured on MI355X, tools/conv_bench.py):
     //   Cout > 64 : 256 pixels x 128 couts, 8 waves (64x64 each), 3-slot ring (144 KiB, one

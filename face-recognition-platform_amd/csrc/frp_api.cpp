@@ -26,6 +26,29 @@
 
 using namespace frp;
 
+// The only readers of the environment (besides the JPEG size limit, jpeg_host.cpp: jpeg_max_pixels); the switches: frp_internal.h
+#define FRP_WINO_MIN_FACES 128   // default of Switches::wino_min_faces (run_embed)
+Switches frp::read_switches() {
+    auto set = [](const char* n) { return getenv(n) ? 1 : 0; };
+    const char *sm = getenv("FRP_SMALL_M"), *wm = getenv("FRP_WINO_MIN_FACES");
+    Switches s{};
+    s.small_m = !sm ? 0 : (sm[0] == '0' ? -1 : 1);
+    s.wino_min_faces = wm ? atoi(wm) : FRP_WINO_MIN_FACES;
+    s.s2 = set("FRP_S2"); s.host_count = set("FRP_HOST_COUNT"); s.match_v1 = set("FRP_MATCH_V1");
+    s.no_fused_stem12 = set("FRP_NO_FUSED_STEM12"); s.no_fused_stem = set("FRP_NO_FUSED_STEM");
+    s.no_emb_stem = set("FRP_NO_EMB_STEM"); s.no_stem_fuse = set("FRP_NO_STEM_FUSE");
+    s.no_wino = set("FRP_NO_WINO"); s.no_kconcat = set("FRP_NO_KCONCAT");
+    return s;
+}
+
+const ProcessSwitches& frp::process_switches() {
+    static const ProcessSwitches s = [] {
+        const char* jh = getenv("FRP_JPEG_DEVICE_HUFFMAN");
+        return ProcessSwitches{getenv("FRP_NO_GRAPH") != nullptr, getenv("FRP_C64_ALL") != nullptr, !jh ? 0 : (jh[0] == '0' ? -1 : 1)};
+    }();
+    return s;
+}
+
 namespace {
 
 struct DevBuf {
@@ -383,7 +406,7 @@ bool stem12_fusable(const Net& net) {
 // planned for): every kernel derives its tile count from it.  The flop counters are charged for `batch` images and
 // corrected by the caller once the count is known.
 // `allow_wino` false: the direct kernels also where a Winograd weight image exists (calls of few faces, run_embed).
-int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem,
+int run_net_body(frp_handle* h, const Switches& sw, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem,
                  const int32_t* n_dev, bool allow_wino) {
     // dims are re-derived while walking (physical buffers are reused by several tensors)
     std::vector<TensorDims> d(net.n_bufs);
@@ -392,14 +415,11 @@ int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops
     bool first = true;
     size_t skip = 0;
     if (&net == &h->det && h->det_hash_on) HIPCHK(h, hipMemsetAsync(h->det_hashes.p, 0, 64 * 8, h->stream));
-    // tile class of the conv launches (conv_common.h: conv_small_m): FRP_SMALL_M=0 never quarter tiles, =1 always, unset: by
-    // the tile count of each launch (A/B runs, tests that pin a kernel family)
-    const char* sm_env = getenv("FRP_SMALL_M");
-    const int small_m = !sm_env ? 0 : (sm_env[0] == '0' ? -1 : 1);
-    const bool s2_optin = getenv("FRP_S2") != nullptr;        // the opt-in stride-2 row-patch kernel (conv3x3_s2.hip; A/B runs, its pipeline test)
-    // both detector stems in one kernel (the stem1 map never reaches HBM); FRP_NO_FUSED_STEM12=1 keeps
+    // the kernel A/B bits of every conv launch of the pass (frp_internal.h: CONV_DBG_*)
+    const int dbg = (sw.s2 ? CONV_DBG_S2 : 0) | (process_switches().c64_all ? CONV_DBG_C64_ALL : 0);
+    // both detector stems in one kernel (the stem1 map never reaches HBM); FRP_NO_FUSED_STEM12 keeps
     // stem1 (fused with the u8 normalisation) and stem2 (generic conv) apart for A/B runs
-    if (stem && stem12_fusable(net) && (stem->Hc % 4) == 0 && (stem->Wc % 4) == 0 && !getenv("FRP_NO_FUSED_STEM12")) {
+    if (stem && stem12_fusable(net) && (stem->Hc % 4) == 0 && (stem->Wc % 4) == 0 && !sw.no_fused_stem12) {
         const frp_conv_op& a = net.ops[0];
         const frp_conv_op& b = net.ops[1];
         Stem12Params sp{};
@@ -423,14 +443,14 @@ int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops
         skip = 2;
         first = false;
     }
-    // embedder stem (chips NHWC8 -> 3x3 s1 3->64 + PReLU): dedicated kernel; FRP_NO_EMB_STEM=1 keeps the generic one
+    // embedder stem (chips NHWC8 -> 3x3 s1 3->64 + PReLU): dedicated kernel; FRP_NO_EMB_STEM keeps the generic one
     bool fuse_stem = false, fuse_even_only = false;
     size_t fuse_op = 0;
     EmbStemParams fused{};
     if (!stem && !net.ops.empty()) {
         const frp_conv_op& a = net.ops[0];
         if (a.in_buf == net.in_buf && a.cin == 8 && (a.real_ch & 0xffff) == 3 && a.cout == 64 && a.ksize == 3 && a.stride == 1 &&
-            a.act == FRP_ACT_PRELU && a.res_buf < 0 && a.flags == 0 && a.slope_off >= 0 && !getenv("FRP_NO_EMB_STEM")) {
+            a.act == FRP_ACT_PRELU && a.res_buf < 0 && a.flags == 0 && a.slope_off >= 0 && !sw.no_emb_stem) {
             EmbStemParams ep{};
             ep.x = (const _Float16*)net.bufs[a.in_buf].p;
             ep.M = batch; ep.H = H; ep.W = W;
@@ -441,11 +461,11 @@ int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops
             ep.n_dev = n_dev;
             // ... and where the conv behind it runs on the 64 -> 64 kernel (conv3x3_c64.hip), that launch computes the stem of its own
             // input patch from the chips: the 64-channel map is written once (the block's shortcut reads it) and never read back by
-            // the conv; one launch fewer.  FRP_NO_STEM_FUSE=1: the two launches (A/B runs; the results are the same bits)
+            // the conv; one launch fewer.  FRP_NO_STEM_FUSE: the two launches (A/B runs; the results are the same bits)
             // (the next op that launches: the block's shortcut conv in between rides in a later k-loop - kc_skip - and reads the map then)
             size_t nb = 1;
             while (nb < net.ops.size() && nb < net.kc_skip.size() && net.kc_skip[nb]) ++nb;
-            if (nb < net.ops.size() && !getenv("FRP_NO_STEM_FUSE") && small_m <= 0) {
+            if (nb < net.ops.size() && !sw.no_stem_fuse && sw.small_m <= 0) {
                 const frp_conv_op& b = net.ops[nb];
                 const bool plain = !(b.flags & ~FRP_FLAG_BORDER_BIAS) && (b.flags & FRP_FLAG_BORDER_BIAS) && b.out2_buf < 0 && b.res_buf < 0;
                 const bool chained = !(nb < net.kc_src.size() && net.kc_src[nb] >= 0);
@@ -464,7 +484,6 @@ int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops
                                           o.ksize == 1 && o.stride == 2;
                     if (!shortcut) fuse_even_only = false;
                 }
-                if (getenv("FRP_STEM_FULL_MAP")) fuse_even_only = false;          // (A/B runs)
             }
             if (fuse_stem) {
                 fused = ep;
@@ -519,8 +538,8 @@ int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops
         p.KS = op.ksize; p.stride = op.stride; p.act = op.act;
         p.n_dev = n_dev;
         p.n_cu = h->n_cu;
-        p.small_m = small_m;
-        if (s2_optin) p.dbg |= 2048;
+        p.small_m = sw.small_m;
+        p.dbg = dbg;
         if (fuse_stem && opi == fuse_op) {
             p.stem_x = fused.x; p.stem_w = fused.w; p.stem_bias = fused.bias; p.stem_slope = fused.slope; p.stem_out = fused.out;
             p.stem_even_only = fuse_even_only ? 1 : 0;
@@ -553,7 +572,7 @@ int run_net_body(frp_handle* h, Net& net, int batch, int H, int W, double* flops
         // skinny fp32-output GEMM (the FC): split K over the CUs; the slabs are reduced (+bias) by
         // the l2norm kernel that follows
         h->fc_ksplit = 0;
-        if ((op.flags & FRP_FLAG_OUT_F32) && &op == &net.ops.back() && !getenv("FRP_NO_SPLITK")) {
+        if ((op.flags & FRP_FLAG_OUT_F32) && &op == &net.ops.back()) {
             const int ncu = h->n_cu;
             const int hw_out = ((in.h + 2 * (op.ksize / 2) - op.ksize) / op.stride + 1) * ((in.w + 2 * (op.ksize / 2) - op.ksize) / op.stride + 1);
             // device-side count: the kernel picks the factor of the real batch itself (the same function), the slabs are
@@ -621,24 +640,22 @@ static void drop_graphs(frp_handle* h) {
     h->graph_bad.clear();
 }
 
-// The pass, replayed from its captured graph when it has been asked for before (FRP_NO_GRAPH=1: always launch by launch).  The key names
-// everything the launches depend on that is not fixed by the loaded weights: program, shapes, family, operand pointers, every switch
-// run_net_body reads; device buffers and weights are covered by the allocation epoch.  Not with stage timers (events between the
+// The pass, replayed from its captured graph when it has been asked for before (FRP_NO_GRAPH: always launch by launch).  The key names
+// everything the launches depend on that is not fixed by the loaded weights: program, shapes, family, operand pointers, the bytes of the
+// switch snapshot; device buffers and weights are covered by the allocation epoch.  Not with stage timers (events between the
 // passes are fine, but the diagnostics inside a pass are not captured), not with the detector diagnostics.
-int run_net(frp_handle* h, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem = nullptr,
+int run_net(frp_handle* h, const Switches& sw, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem = nullptr,
             const int32_t* n_dev = nullptr, bool allow_wino = true) {
-    static const bool off = getenv("FRP_NO_GRAPH") != nullptr;
-    if (off || h->det_hash_on || h->det_op_limit >= 0) return run_net_body(h, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
+    if (process_switches().no_graph || h->det_hash_on || h->det_op_limit >= 0)
+        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
     char kb[512];
-    auto env = [](const char* n) { const char* v = getenv(n); return v ? (v[0] ? v[0] : '1') : '-'; };
-    int len = snprintf(kb, sizeof kb, "%c|%d|%d|%d|%d|%p|%p|%c%c%c%c%c%c%c%c|", &net == &h->det ? 'd' : 'e', batch, H, W, (int)allow_wino, (const void*)n_dev,
-                       (const void*)h->wdata.p, env("FRP_SMALL_M"), env("FRP_S2"), env("FRP_NO_STEM_FUSE"), env("FRP_STEM_FULL_MAP"),
-                       env("FRP_NO_FUSED_STEM12"), env("FRP_NO_EMB_STEM"), env("FRP_NO_SPLITK"), env("FRP_NO_PREFETCH"));
+    int len = snprintf(kb, sizeof kb, "%c|%d|%d|%d|%d|%p|%p|", &net == &h->det ? 'd' : 'e', batch, H, W, (int)allow_wino, (const void*)n_dev,
+                       (const void*)h->wdata.p);
     if (stem && len > 0 && len < (int)sizeof kb)
         len += snprintf(kb + len, sizeof kb - len, "%p|%d|%d|%d|%ld|%ld|%d|%d|%d", (const void*)stem->frames, stem->B, stem->H, stem->W, stem->row_stride,
                         stem->frame_stride, stem->Hc, stem->Wc, stem->rgb_in);
-    if (len <= 0 || len >= (int)sizeof kb) return run_net_body(h, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    const std::string key(kb);
+    if (len <= 0 || len >= (int)sizeof kb) return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
+    const std::string key = std::string(kb, len) + std::string(reinterpret_cast<const char*>(&sw), sizeof sw);
     for (size_t i = 0; i < h->graphs.size(); ++i) {
         NetGraph& g = h->graphs[i];
         if (g.key != key) continue;
@@ -667,7 +684,7 @@ int run_net(frp_handle* h, Net& net, int batch, int H, int W, double* flops, int
     if (has(h->graph_bad, key) || !has(h->graph_seen, key)) {
         if (h->graph_seen.size() > 256) h->graph_seen.clear();
         if (!has(h->graph_seen, key)) h->graph_seen.push_back(key);
-        return run_net_body(h, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
+        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
     }
     // second request for this pass: capture it (thread-local mode: the other lanes' threads keep allocating and synchronising as they like)
     const uint64_t epoch0 = h->alloc_epoch;
@@ -676,9 +693,9 @@ int run_net(frp_handle* h, Net& net, int batch, int H, int W, double* flops, int
     if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
         h->graph_bad.push_back(key);
-        return run_net_body(h, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
+        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
     }
-    const int rc = run_net_body(h, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
+    const int rc = run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
     NetGraph g;
@@ -692,7 +709,7 @@ int run_net(frp_handle* h, Net& net, int batch, int H, int W, double* flops, int
         h->graph_bad.push_back(key);
         if (rc != FRP_OK) return rc;
         *flops = f0; *launches = l0; h->ctr.f8_conv_flops = f80; h->ctr.f8_conv_launches = l80;
-        return run_net_body(h, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
+        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
     }
     g.key = key;
     g.epoch = epoch0;
@@ -796,15 +813,15 @@ int ensure_results(frp_handle* h, int B, int K) {
     return FRP_OK;
 }
 
-int run_detect(frp_handle* h, int K, float det_thresh, float nms_iou, uint32_t flags) {
+int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float nms_iou, uint32_t flags) {
     if (!h->have_weights) return fail(h, FRP_ERR_NO_WEIGHTS, "no weights loaded");
     if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "no resident frames (call frp_upload_frames)");
     if (K <= 0 || K > FRP_MAX_FACES_CAP) return fail(h, FRP_ERR_INVALID, "max_faces out of range");
     const int B = h->rB, Hc = h->canvas_h, Wc = h->canvas_w;
     // The detector's first layer reads the u8 frames directly (fused normalise + conv) whenever
-    // the program starts with the standard 3x3 s2 3->32 stem; FRP_NO_FUSED_STEM=1 keeps the
+    // the program starts with the standard 3x3 s2 3->32 stem; FRP_NO_FUSED_STEM keeps the
     // two-kernel path (preprocess to an NHWC8 blob, then the generic conv) for A/B runs.
-    const bool fused = stem_fusable(h->det) && !getenv("FRP_NO_FUSED_STEM");
+    const bool fused = stem_fusable(h->det) && !sw.no_fused_stem;
     FRPCHK(plan_net(h, h->det, B, Hc, Wc, fused));
     FRPCHK(ensure_results(h, B, K));
     hipError_t e = hipSuccess;
@@ -825,7 +842,7 @@ int run_detect(frp_handle* h, int K, float det_thresh, float nms_iou, uint32_t f
     // Winograd family for the detector's wide 128 / 256-channel layers: from two rounds of 8 x 30 tiles on its stride-8 maps on
     // (1080p: four frames; below that the direct family with its quarter tiles and weight prefetch: single-image latency)
     const bool det_wino = (long)B * (Hc / 8) * (Wc / 8) >= 2L * 240 * (h->n_cu > 0 ? h->n_cu : 256);
-    FRPCHK(run_net(h, h->det, B, Hc, Wc, &h->ctr.det_conv_flops, &h->ctr.det_conv_launches, fused ? &sp : nullptr, nullptr, det_wino));
+    FRPCHK(run_net(h, sw, h->det, B, Hc, Wc, &h->ctr.det_conv_flops, &h->ctr.det_conv_launches, fused ? &sp : nullptr, nullptr, det_wino));
     rec(h, EV_DET);
     DecodeParams dp{};
     for (int l = 0; l < 3; ++l) {
@@ -866,14 +883,11 @@ int run_detect(frp_handle* h, int K, float det_thresh, float nms_iou, uint32_t f
 // found: `family_count` = the slots of the call (B x K of a process call, whether the face count stays on the device or
 // not; the faces handed to the embed / finish calls).  Within a family every tile size gives the same bits, so a face's
 // embedding depends on the call's slot count being above or below FRP_WINO_MIN_FACES and on nothing else in the batch.
-#define FRP_WINO_MIN_FACES 128
-int run_embed(frp_handle* h, int n, const int32_t* n_dev = nullptr, int family_count = -1) {
+int run_embed(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev = nullptr, int family_count = -1) {
     if (n <= 0) return FRP_OK;
     if (family_count < 0) family_count = n;
-    const char* wm = getenv("FRP_WINO_MIN_FACES");               // A/B runs and tests that pin the family
-    const int wino_min = wm ? atoi(wm) : FRP_WINO_MIN_FACES;
-    FRPCHK(run_net(h, h->emb, n, FRP_CHIP, FRP_CHIP, &h->ctr.emb_conv_flops, &h->ctr.emb_conv_launches, nullptr, n_dev,
-                   family_count >= wino_min));
+    FRPCHK(run_net(h, sw, h->emb, n, FRP_CHIP, FRP_CHIP, &h->ctr.emb_conv_flops, &h->ctr.emb_conv_launches, nullptr, n_dev,
+                   family_count >= sw.wino_min_faces));
     rec(h, EV_EMB);
     const int mpad = round_up(n, 32);
     FRPCHK(ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2));
@@ -887,7 +901,7 @@ int run_embed(frp_handle* h, int n, const int32_t* n_dev = nullptr, int family_c
 }
 
 // q16 [mpad,512] holds n unit queries -> best_idx/best_cos [n]
-int run_match(frp_handle* h, int n, float* all_scores_dev, const int32_t* n_dev = nullptr) {
+int run_match(frp_handle* h, const Switches& sw, int n, float* all_scores_dev, const int32_t* n_dev = nullptr) {
     if (n <= 0) return FRP_OK;
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     const int mpad = round_up(n, 32);
@@ -906,7 +920,7 @@ int run_match(frp_handle* h, int n, float* all_scores_dev, const int32_t* n_dev 
     mp.best_cos = (float*)h->best_cos.p; mp.best_idx = (int32_t*)h->best_idx.p;
     mp.all_scores = all_scores_dev;
     mp.n_dev = n_dev;
-    hipError_t e = launch_match(mp, h->stream);
+    hipError_t e = launch_match(mp, sw.match_v1 != 0, h->stream);
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("match: ") + hipGetErrorString(e));
     h->ctr.match_bytes += (double)h->g_rows * FRP_EMB_DIM * 2;
     h->ctr.match_launches += 1;
@@ -916,7 +930,7 @@ int run_match(frp_handle* h, int n, float* all_scores_dev, const int32_t* n_dev 
 // align + embed + match for the faces listed in h->kps / h->counts / h->face_slot (device), always from
 // the full-resolution resident frames.  n_known >= 0: face count known on the host.
 int resolve_count(frp_handle* h);
-int run_faces(frp_handle* h, int K, int n_known, uint32_t flags) {
+int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t flags) {
     const int B = h->rB;
     int n;
     // a device-count pass that nobody fetched or synchronised yet (two process calls queued back to back): its count and its
@@ -929,10 +943,10 @@ int run_faces(frp_handle* h, int K, int n_known, uint32_t flags) {
     // device only.  It STAYS there: align, the embedder's kernels, the l2norm and the matcher are launched for the capacity
     // B x K and read the count from device memory (grids sized for the capacity; workgroups beyond the real tiles leave at
     // once), so the pipeline has no host round trip.  The host learns the count with the results (frp_fetch_results).
-    // FRP_HOST_COUNT=1 keeps the former path (copy the count, wait, launch for exactly n) for A/B runs - both give the
+    // FRP_HOST_COUNT keeps the former path (copy the count, wait, launch for exactly n) for A/B runs - both give the
     // same bits.  More than FRP_MATCH_TOP1_MAX slots: the per-tile matcher has no device-count form, former path.
-    // (FRP_MATCH_V1=1 pins the per-tile matcher for A/B runs: it has no device-count form either)
-    const bool dev_count = n_known < 0 && round_up(B * K, 32) <= FRP_MATCH_TOP1_MAX && !getenv("FRP_HOST_COUNT") && !getenv("FRP_MATCH_V1");
+    // (FRP_MATCH_V1 pins the per-tile matcher for A/B runs: it has no device-count form either)
+    const bool dev_count = n_known < 0 && round_up(B * K, 32) <= FRP_MATCH_TOP1_MAX && !sw.host_count && !sw.match_v1;
     const int32_t* n_dev = nullptr;
     if (n_known >= 0) {
         n = n_known;
@@ -968,9 +982,9 @@ int run_faces(frp_handle* h, int K, int n_known, uint32_t flags) {
         hipError_t e = launch_align(ap, h->stream);
         if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("align: ") + hipGetErrorString(e));
         rec(h, EV_ALIGN);
-        FRPCHK(run_embed(h, n, n_dev, n_known >= 0 ? n_known : B * K));
+        FRPCHK(run_embed(h, sw, n, n_dev, n_known >= 0 ? n_known : B * K));
         if (!(flags & FRP_FLAG_NO_MATCH) && h->g_rows > 0) {
-            FRPCHK(run_match(h, n, nullptr, n_dev));
+            FRPCHK(run_match(h, sw, n, nullptr, n_dev));
             h->last_matched = true;
         }
         rec(h, EV_MATCH);
@@ -1006,10 +1020,11 @@ int resolve_count(frp_handle* h) {
 }
 
 int run_pipeline(frp_handle* h, int K, float det_thresh, float nms_iou, uint32_t flags) {
+    const Switches sw = read_switches();
     if (h->det_scaled) FRPCHK(select_det_source(h, h->rH, h->rW));     // the fused path always detects at full size
-    FRPCHK(run_detect(h, K, det_thresh, nms_iou, flags));
+    FRPCHK(run_detect(h, sw, K, det_thresh, nms_iou, flags));
     const long A = (long)h->det.dims[h->hdr.det_head_buf[0]].h * h->det.dims[h->hdr.det_head_buf[0]].w * 2;
-    return run_faces(h, K, ((flags & FRP_FLAG_FORCED_K) && A >= K) ? h->rB * K : -1, flags);   // forced-K: count known
+    return run_faces(h, sw, K, ((flags & FRP_FLAG_FORCED_K) && A >= K) ? h->rB * K : -1, flags);   // forced-K: count known
 }
 
 void accumulate_events(frp_handle* h, bool with_h2d) {
@@ -1332,10 +1347,11 @@ int frp_load_weights(frp_handle* h, const void* blob, size_t bytes) {
     }
     // Winograd weight images (conv3x3_wino.hip) for the embedder's eligible 3x3 stride-1 layers, appended behind the data
     // section.  The embedder's geometry is static (112 x 112 chips), so the map width of every op is known here; the
-    // detector's maps at camera resolutions are wider than the kernel's LDS holds.  FRP_NO_WINO=1: direct kernels only.
+    // detector's maps at camera resolutions are wider than the kernel's LDS holds.  FRP_NO_WINO: direct kernels only.
     h->det.wino_off.assign(h->det.ops.size(), -1);
     h->emb.wino_off.assign(h->emb.ops.size(), -1);
-    if (!getenv("FRP_NO_WINO")) {
+    const Switches sw = read_switches();
+    if (!sw.no_wino) {
         if (expanded.empty()) expanded.assign(data, data + hd.data_bytes);
         std::vector<int> bw(h->emb.n_bufs, 0);
         bw[h->emb.in_buf] = FRP_CHIP;
@@ -1374,14 +1390,14 @@ int frp_load_weights(frp_handle* h, const void* blob, size_t bytes) {
         data = expanded.data();
         data_bytes = expanded.size();
     }
-    // K-concat plans (both networks; FRP_NO_KCONCAT=1: every op as written in the blob)
+    // K-concat plans (both networks; FRP_NO_KCONCAT: every op as written in the blob)
     for (Net* net : {&h->det, &h->emb}) {
         const size_t n_ops = net->ops.size();
         net->kc_skip.assign(n_ops, 0);
         net->kc_src.assign(n_ops, -1);
         net->kc_w_off.assign(n_ops, -1);
         net->kc_bias_off.assign(n_ops, -1);
-        if (getenv("FRP_NO_KCONCAT")) continue;
+        if (sw.no_kconcat) continue;
         for (size_t j = 0; j < n_ops; ++j) {
             const frp_conv_op& c = net->ops[j];
             // consumer: 3x3 conv over whole channel blocks with a plain residual, fp16 operands, one bias class
@@ -1828,7 +1844,7 @@ int upload_jpeg_device(frp_handle* h, const uint8_t* const* jpegs, const size_t*
     // 9-12 ms: by default the device decodes streams whose intervals are at most 32 MCUs and the host the others.
     // FRP_JPEG_DEVICE_HUFFMAN=1 (read once): the device whatever the interval (takes the entropy decode off the host's cores; at
     // one interval per row it is slower than the pipeline consumes frames), =0: never.
-    static const int mode = [] { const char* e = getenv("FRP_JPEG_DEVICE_HUFFMAN"); return !e ? 0 : (e[0] == '0' ? -1 : 1); }();
+    const int mode = process_switches().jpeg_device_huffman;
     if (mode < 0 || I.restart_interval <= 0 || (mode == 0 && I.restart_interval > 32)) return 1;
     const long mcus = (long)I.mcus_x * I.mcus_y;
     const long n_int = (mcus + I.restart_interval - 1) / I.restart_interval;
@@ -2011,13 +2027,14 @@ int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size
     return FRP_OK;
 }
 
-// diagnostic: how many frp_upload_jpeg_async batches had their entropy decode on the device (restart-interval streams)
+// diagnostic: network passes replayed from a captured hipGraph (run_net)
 int64_t frp_debug_graph_replays(frp_handle* h) {
     if (!h) return -1;
     Guard g(h);
     return h->graph_replays;
 }
 
+// diagnostic: how many frp_upload_jpeg_async batches had their entropy decode on the device (restart-interval streams)
 int64_t frp_debug_jpeg_device_batches(frp_handle* h) {
     if (!h) return -1;
     Guard g(h, false);
@@ -2088,7 +2105,7 @@ int frp_detect(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, int32_t 
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
     FRPCHK(upload_frames(h, bgr, B, H, W, row_stride));
-    FRPCHK(run_detect(h, max_faces, det_thresh, nms_iou, flags));
+    FRPCHK(run_detect(h, read_switches(), max_faces, det_thresh, nms_iou, flags));
     const size_t s = (size_t)B * max_faces;
     if (boxes) HIPCHK(h, hipMemcpyAsync(boxes, h->boxes.p, s * 16, hipMemcpyDeviceToHost, h->stream));
     if (kps) HIPCHK(h, hipMemcpyAsync(kps, h->kps.p, s * 40, hipMemcpyDeviceToHost, h->stream));
@@ -2107,7 +2124,7 @@ int frp_detect_resident(frp_handle* h, int32_t B, int32_t det_h, int32_t det_w, 
     if (B != h->rB) return fail(h, FRP_ERR_INVALID, "detect_resident: buffers sized for another resident batch");
     rec(h, EV_H2D);
     FRPCHK(select_det_source(h, det_h, det_w));
-    FRPCHK(run_detect(h, max_faces, det_thresh, nms_iou, flags));
+    FRPCHK(run_detect(h, read_switches(), max_faces, det_thresh, nms_iou, flags));
     const size_t s = (size_t)B * max_faces;
     if (boxes) HIPCHK(h, hipMemcpyAsync(boxes, h->boxes.p, s * 16, hipMemcpyDeviceToHost, h->stream));
     if (kps) HIPCHK(h, hipMemcpyAsync(kps, h->kps.p, s * 40, hipMemcpyDeviceToHost, h->stream));
@@ -2159,7 +2176,7 @@ int frp_finish_faces(frp_handle* h, int32_t B_in, const float* boxes, const floa
     h->last_B = B;
     h->last_K = K;
     rec(h, EV_DEC);
-    FRPCHK(run_faces(h, K, n, flags));
+    FRPCHK(run_faces(h, read_switches(), K, n, flags));
     FRPCHK(fetch_results(h, nullptr, nullptr, nullptr, nullptr, emb, match_idx, match_cos));
     accumulate_face_events(h);
     h->ctr.calls += 1;
@@ -2209,7 +2226,8 @@ int frp_debug_det_prefix(frp_handle* h, int32_t n_ops, void* out_f16, int64_t ou
     if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "no resident frames (call frp_upload_frames)");
     if (n_ops <= 0 || n_ops > (int)h->det.ops.size()) return fail(h, FRP_ERR_INVALID, "op count out of range");
     const int B = h->rB, Hc = h->canvas_h, Wc = h->canvas_w;
-    const bool fused = stem_fusable(h->det) && !getenv("FRP_NO_FUSED_STEM");
+    const Switches sw = read_switches();
+    const bool fused = stem_fusable(h->det) && !sw.no_fused_stem;
     if (!fused) return fail(h, FRP_ERR_INVALID, "prefix runs need the fused stem");
     FRPCHK(plan_net(h, h->det, B, Hc, Wc, fused));
     StemParams sp{};
@@ -2222,7 +2240,7 @@ int frp_debug_det_prefix(frp_handle* h, int32_t n_ops, void* out_f16, int64_t ou
     double fl = 0.0;
     int64_t ln = 0;
     h->det_op_limit = n_ops;
-    const int rc = run_net(h, h->det, B, Hc, Wc, &fl, &ln, &sp, nullptr, det_wino);
+    const int rc = run_net(h, sw, h->det, B, Hc, Wc, &fl, &ln, &sp, nullptr, det_wino);
     h->det_op_limit = -1;
     if (rc != FRP_OK) return rc;
     const frp_conv_op& op = h->det.ops[n_ops - 1];
@@ -2332,7 +2350,7 @@ int frp_embed_faces(frp_handle* h, const uint8_t* bgr, int32_t H, int32_t W, int
     Guard g(h);
     if (!emb) return fail(h, FRP_ERR_INVALID, "null output");
     FRPCHK(align_common(h, bgr, H, W, row_stride, kps, M, flags, true));
-    FRPCHK(run_embed(h, M));
+    FRPCHK(run_embed(h, read_switches(), M));
     HIPCHK(h, hipMemcpyAsync(emb, h->emb.bufs[h->hdr.emb_out_buf].p, (size_t)M * FRP_EMB_DIM * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return FRP_OK;
@@ -2348,13 +2366,14 @@ int frp_embed_aligned(frp_handle* h, const uint8_t* chips, int32_t M, float* emb
     HIPCHK(h, hipMemcpyAsync(h->scratch.p, chips, (size_t)M * FRP_CHIP_PIX * 3, hipMemcpyHostToDevice, h->stream));
     hipError_t e = launch_chips_to_blob((const uint8_t*)h->scratch.p, M, (_Float16*)h->emb.bufs[h->emb.in_buf].p, h->stream);
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("chips_to_blob: ") + hipGetErrorString(e));
-    FRPCHK(run_embed(h, M));
+    FRPCHK(run_embed(h, read_switches(), M));
     HIPCHK(h, hipMemcpyAsync(emb, h->emb.bufs[h->hdr.emb_out_buf].p, (size_t)M * FRP_EMB_DIM * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return FRP_OK;
 }
 
 static int match_common(frp_handle* h, const float* q, int M, float* all_scores_host, int32_t* idx, float* cos) {
+    const Switches sw = read_switches();
     if (!q || M <= 0 || M > (1 << 20)) return fail(h, FRP_ERR_INVALID, "bad query arguments");
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     const int mpad = round_up(M, 32);
@@ -2363,7 +2382,7 @@ static int match_common(frp_handle* h, const float* q, int M, float* all_scores_
     FRPCHK(upload_rows_normalized(h, q, M, (_Float16*)h->q16.p));
     DevBuf all;
     if (all_scores_host) FRPCHK(ensure(h, all, (size_t)M * h->g_rows * 4));
-    int rc = run_match(h, M, (float*)all.p);
+    int rc = run_match(h, sw, M, (float*)all.p);
     hipError_t e = hipSuccess;
     if (rc == FRP_OK) {
         if (idx) e = hipMemcpyAsync(idx, h->best_idx.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream);
@@ -2387,6 +2406,7 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
     if (!q || !idx || !cos || M <= 0 || M > (1 << 20)) return fail(h, FRP_ERR_INVALID, "bad query arguments");
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     const long N = h->g_rows;
+    const Switches sw = read_switches();
     int chunk = (int)std::max<long>(1, std::min<long>(M, (1L << 28) / N));
     DevBuf all, didx, dcos;
     int rc = ensure(h, all, (size_t)chunk * N * 4);
@@ -2401,7 +2421,7 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
         e = hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream);
         if (e != hipSuccess) break;
         rc = upload_rows_normalized(h, q + (size_t)m0 * FRP_EMB_DIM, m, (_Float16*)h->q16.p);
-        if (rc == FRP_OK) rc = run_match(h, m, (float*)all.p);
+        if (rc == FRP_OK) rc = run_match(h, sw, m, (float*)all.p);
         if (rc != FRP_OK) break;
         e = launch_topk_rows((const float*)all.p, m, N, topk, (int32_t*)didx.p, (float*)dcos.p, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(idx + (size_t)m0 * topk, didx.p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
@@ -2423,6 +2443,16 @@ int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, i
     if (n_cols != h->g_rows) return fail(h, FRP_ERR_INVALID, "match_scores: output sized for another gallery size");
     return match_common(h, q, M, cos_all, nullptr, nullptr);
 }
+
+namespace {
+// frp_conv2d_nhwc / frp_conv_bench `flags` (include/frp.h) -> the kernel A/B bits and the tile class of one conv launch
+void conv_route_from_abi_flags(int32_t flags, ConvParams& p) {
+    p.dbg = ((flags >> 8) & 0xff) | ((flags & (1 << 19)) ? CONV_DBG_WINO_2D : 0) | ((flags & (1 << 20)) ? CONV_DBG_NO_C64 : 0) |
+            ((flags & (1 << 21)) ? CONV_DBG_S2 : 0) | ((flags & (1 << 22)) ? CONV_DBG_C64_SAME_ORDER : 0) |
+            (process_switches().c64_all ? CONV_DBG_C64_ALL : 0);
+    p.small_m = (flags & (1 << 17)) ? 1 : (flags & ((1 << 18) | (1 << 16))) ? -1 : 0;     // (the Winograd kernel: never quarter tiles)
+}
+}  // namespace
 
 int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t W, int32_t Cin, const void* w, int32_t Cout,
                     int32_t ksize, int32_t stride, const float* bias, const float* slope, const void* res, int32_t res_h,
@@ -2446,14 +2476,16 @@ int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t 
     if (rc == FRP_OK) rc = ensure(h, dout, ob);
     if (rc == FRP_OK && slope) rc = ensure(h, ds, (size_t)Cout * 4);
     if (rc == FRP_OK && res) rc = ensure(h, dr, rb);
+    ConvParams p{};
+    conv_route_from_abi_flags(flags, p);
     // flags bit 16: through the Winograd kernel (parity tests); an ineligible shape is an error, not a silent fallback
-    const bool want_wino = (flags & 0x10000) != 0;
+    const bool want_wino = (flags & (1 << 16)) != 0;
     std::vector<uint16_t> wimg;
     if (want_wino) {
         bool shape_ok = conv3x3_wino_shape_ok(W, Cin, ksize, stride) ||
                         (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, res != nullptr));      // (2-D tiles: wide maps)
 #ifdef FRP_LAB
-        shape_ok = shape_ok || (((((flags >> 8) & 0xff) & 64) || (flags & 0x80000)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
+        shape_ok = shape_ok || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
 #endif
         if (!shape_ok || (flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2)))
             return fail(h, FRP_ERR_INVALID, "shape not covered by the Winograd kernel");
@@ -2470,17 +2502,12 @@ int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t 
         if (e == hipSuccess && slope) e = hipMemcpyAsync(ds.p, slope, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess && res) e = hipMemcpyAsync(dr.p, res, rb, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) {
-            ConvParams p{};
             p.x = (const _Float16*)dx.p; p.w = (const _Float16*)dw.p; p.bias = (const float*)db.p;
             p.slope = slope ? (const float*)ds.p : nullptr;
             p.res = res ? (const _Float16*)dr.p : nullptr;
             p.out = dout.p;
             p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ksize; p.stride = stride; p.act = act;
             p.flags = flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2);
-            p.dbg = ((flags >> 8) & 0xff) | ((flags & 0x80000) ? 256 : 0) | ((flags & 0x100000) ? 512 : 0) | ((flags & 0x200000) ? 2048 : 0) | ((flags & 0x400000) ? 4096 : 0);      // (bit 20: not the 64 -> 64 kernel; bit 21: the opt-in stride-2 row-patch kernel)      // kernel A/B switches (tests: 1 = generic kernel instead of the
-                                                                                // row-patch one; flags bit 19 = dbg 256: the Winograd kernel's 2-D tiles, lab build)
-            // flags bit 17 / 18: quarter tiles always / never (default: by the tile count, conv_common.h: conv_small_m)
-            p.small_m = (flags & 0x20000) ? 1 : ((flags & 0x40000) || want_wino) ? -1 : 0;
             p.Hr = res_h; p.Wr = res_w;
             if (want_wino) p.wino_w = (const _Float16*)dwino.p;
             e = launch_conv(p, h->stream);
@@ -2586,14 +2613,11 @@ int frp_conv_bench(frp_handle* h, int32_t N, int32_t H, int32_t W, int32_t Cin, 
             if (!(flags & FRP_FLAG_OUT_FP8)) p.out2 = dr.p;   // conv2-style: fp16 out + fp8 copy (residual buffer doubles as the copy target when unused)
             if (with_res) p.out2 = nullptr;
         }
-        p.dbg = ((flags >> 8) & 0xff) | ((flags & 0x80000) ? 256 : 0) | ((flags & 0x100000) ? 512 : 0) | ((flags & 0x200000) ? 2048 : 0) | ((flags & 0x400000) ? 4096 : 0);      // (bit 20: not the 64 -> 64 kernel)
-        p.small_m = (flags & 0x20000) ? 1 : ((flags & 0x40000) || (flags & 0x10000)) ? -1 : 0;
+        conv_route_from_abi_flags(flags, p);
         DevBuf dwino;
         bool wino_shape = conv3x3_wino_shape_ok(W, Cin, ksize, stride) || (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, with_res != 0));
-#ifdef FRP_LAB
-        wino_shape = wino_shape || ((p.dbg & (64 | 256)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
-#endif
-        if ((flags & 0x10000) && wino_shape) {     // Winograd kernel: a random weight image (timing only)
+        wino_shape = wino_shape || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
+        if ((flags & (1 << 16)) && wino_shape) {     // Winograd kernel: a random weight image (timing only)
             const size_t ib = conv3x3_wino_image_bytes(Cin, Cout);
             if (ensure(h, dwino, ib) == FRP_OK) {
                 e = launch_fill_random_f16((_Float16*)dwino.p, (long)(ib / 2), 5u, 1.0f / sqrtf((float)(9 * Cin)), h->stream);

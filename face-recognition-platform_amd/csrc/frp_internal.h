@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define FRP_ACT_NONE 0
 #define FRP_ACT_RELU 1
@@ -20,6 +21,36 @@
 #include "jpeg_host.h"
 
 namespace frp {
+
+// The engine's environment switches (A/B runs, tests that pin a kernel family; unset: the default routing; "set": any value).  These
+// comments are their record (INTEGRATION.md's table mirrors them); read_switches() / process_switches() (frp_api.cpp) their only readers.
+// Per call: an entry point takes ONE snapshot and hands it down; run_net keys captured graphs by all of its bytes, so a field added here
+// can never replay a graph recorded under another value.
+struct Switches {
+    int small_m;          // FRP_SMALL_M: tile class of the conv launches (conv_common.h: conv_small_m); unset: by each launch's tile count,
+                          // "0...": never quarter tiles (-1), any other value: always (1)
+    int s2;               // FRP_S2 set: the opt-in stride-2 row-patch kernel (conv3x3_s2.hip, CONV_DBG_S2)
+    int no_fused_stem12;  // FRP_NO_FUSED_STEM12 set: the detector's two stems as two launches (stem1 with the u8 normalisation, stem2 generic)
+    int no_fused_stem;    // FRP_NO_FUSED_STEM set: the detector input as preprocess + generic conv, not the u8 stem kernel(s)
+    int no_emb_stem;      // FRP_NO_EMB_STEM set: the embedder's stem on the generic kernel, not its dedicated one
+    int no_stem_fuse;     // FRP_NO_STEM_FUSE set: the embedder's stem and the 64 -> 64 conv behind it as two launches
+    int wino_min_faces;   // FRP_WINO_MIN_FACES=n (default 128): the embedder's Winograd family for calls of at least n slots (run_embed)
+    int host_count;       // FRP_HOST_COUNT set: threshold mode copies the face count to the host before the embedder (run_faces)
+    int match_v1;         // FRP_MATCH_V1 set: the per-tile matcher only, never the persistent top-1 kernel (also a host-side count)
+    int no_wino;          // FRP_NO_WINO set, read at weight load: no Winograd weight images, direct kernels only
+    int no_kconcat;       // FRP_NO_KCONCAT set, read at weight load: no 1x1 shortcut conv folded into its consumer's k-loop
+};
+static_assert(std::has_unique_object_representations_v<Switches>, "run_net keys captured graphs by the bytes of a Switches");
+Switches read_switches();
+
+// Read once per process, at the first call that needs one of them.
+struct ProcessSwitches {
+    bool no_graph;             // FRP_NO_GRAPH set: every network pass launch by launch, never replayed from a captured hipGraph (run_net)
+    bool c64_all;              // FRP_C64_ALL set: the 64 -> 64 kernel on every eligible shape (CONV_DBG_C64_ALL), also where it does not pay
+    int jpeg_device_huffman;   // FRP_JPEG_DEVICE_HUFFMAN: entropy decode of restart-interval JPEGs on the device; unset (0): for intervals of
+                               // at most 32 MCUs, "0..." (-1): never, any other value (1): always (upload_jpeg_device)
+};
+const ProcessSwitches& process_switches();
 
 struct ConvParams {
     const _Float16* x;      // [N,H,W,Cin]
@@ -47,7 +78,7 @@ struct ConvParams {
                             // M and its tile count from it (threshold mode: the face count never visits the host mid-pipeline)
     int n_cu;               // compute units (input of the device-side split-K choice)
     unsigned long long* stamps;   // conv_bench diagnostics: [grid][8] 100 MHz phase stamps, or null
-    int dbg;                // A/B switch (tests, conv_bench): 1 = generic kernel also for row-patch shapes
+    int dbg;                // kernel A/B bits (CONV_DBG_* below); 0 = the launcher's own choice
     int wino_wide_only;     // the Winograd kernel only in its 2-D tile form (maps wider than its flattened tiles cover) and only where the
                             // tile arithmetic says it pays (conv3x3_wino.hip: wino_2d_pays) - the detector's layers
     const void* pf_ptr;     // quarter-tile launches with CUs to spare: the NEXT launch's weights (pf_bytes of them), read once by 64 extra
@@ -71,6 +102,33 @@ struct ConvParams {
     int x2_shift;           // log2(Cin / Cin2)
 };
 
+// ConvParams::dbg: kernel A/B bits for parity tests, conv_bench and A/B runs.  frp_conv2d_nhwc / frp_conv_bench take them from their
+// `flags` (include/frp.h; frp_api.cpp: conv_route_from_abi_flags), the engine's passes from its switches (Switches, ProcessSwitches).
+constexpr int CONV_DBG_GENERIC = 1;               // the generic kernel also for shapes a specialised one covers
+constexpr int CONV_DBG_WINO_2D = 256;             // lab: the Winograd kernel's 2-D tiles whatever the shape
+constexpr int CONV_DBG_NO_C64 = 512;              // not the 64 -> 64 kernel (conv3x3_c64.hip): the row-patch one, bit-identical
+constexpr int CONV_DBG_C64_ALL = 1024;            // the 64 -> 64 kernel on every eligible shape, also where it does not pay
+constexpr int CONV_DBG_S2 = 2048;                 // the opt-in stride-2 row-patch kernel (conv3x3_s2.hip)
+constexpr int CONV_DBG_C64_SAME_ORDER = 4096;     // the 64 -> 64 kernel with all waves in the same order (A/B of its ping-pong)
+// bits 1..7 mean something else to each kernel family
+constexpr int CONV_DBG_LEAN_ALL_ROWS = 64;        // conv3x3_lean.hip: head outputs (Cout <= 32) on all 64 rows of the tile
+constexpr int CONV_DBG_LEAN_TILE256 = 128;        // conv3x3_lean.hip: the 256-pixel tile for 64 couts (1.5 reads per MFMA)
+constexpr int CONV_DBG_WINO_ABLATION = 15 << 1;   // lab, conv3x3_wino.hip: number of a timing ablation (tools/wino_ablate.py)
+constexpr int CONV_DBG_WINO_ONE_WAVE = 32;        // lab, conv3x3_wino.hip: one wave per SIMD
+constexpr int CONV_DBG_WINO_ROW_PATCH = 64;       // lab, conv3x3_wino.hip: the first generation's row-patch form (also wide maps)
+constexpr int CONV_DBG_WINO_KLOOP_GEN1 = 128;     // lab, conv3x3_wino.hip: the first generation of the k-loop (compiler-scheduled)
+constexpr int CONV_DBG_ROWS_PRE_PREFETCH = 2;     // lab, conv3x3_rows.hip: the pre-prefetch k-step (bit-identical)
+constexpr int CONV_DBG_ROWS_ABLATION = 15 << 2;   // lab, conv3x3_rows.hip: number of a timing ablation of the 128-cout kernel (wrong results)
+constexpr int CONV_DBG_ROWS_GEN1 = 64;            // lab, conv3x3_rows.hip: the first-generation kernel with the cross-barrier prefetch
+constexpr int CONV_DBG_ROUTING = CONV_DBG_GENERIC | CONV_DBG_WINO_2D | CONV_DBG_NO_C64 | CONV_DBG_C64_ALL | CONV_DBG_S2 | CONV_DBG_C64_SAME_ORDER;
+template <class... B> constexpr bool conv_dbg_disjoint(B... b) { return (b + ...) == (b | ...); }   // no bit set in two of them
+static_assert(conv_dbg_disjoint(CONV_DBG_GENERIC, CONV_DBG_WINO_2D, CONV_DBG_NO_C64, CONV_DBG_C64_ALL, CONV_DBG_S2, CONV_DBG_C64_SAME_ORDER) &&
+              conv_dbg_disjoint(CONV_DBG_ROUTING, CONV_DBG_LEAN_ALL_ROWS, CONV_DBG_LEAN_TILE256) &&
+              conv_dbg_disjoint(CONV_DBG_ROUTING, CONV_DBG_WINO_ABLATION, CONV_DBG_WINO_ONE_WAVE, CONV_DBG_WINO_ROW_PATCH, CONV_DBG_WINO_KLOOP_GEN1) &&
+              conv_dbg_disjoint(CONV_DBG_ROUTING, CONV_DBG_ROWS_PRE_PREFETCH, CONV_DBG_ROWS_ABLATION, CONV_DBG_ROWS_GEN1),
+              "the dbg bits one kernel family reads must be disjoint");
+constexpr int conv_dbg_field(int dbg, int field) { return (dbg & field) / (field & -field); }   // the number a multi-bit field holds
+
 hipError_t launch_conv(const ConvParams& p, hipStream_t stream);
 // row-patch variant for 3x3 stride-1 layers with Cin % 64 == 0 (conv3x3_rows.hip); launch_conv()
 // routes eligible shapes to it.  `p` must carry launch_conv()'s derived fields.
@@ -92,7 +150,7 @@ bool conv3x3_wino_eligible(const ConvParams& p);
 bool conv3x3_wino_shape_ok(int W, int Cin, int ksize, int stride);
 bool conv3x3_wino_wide_pays(int N, int H, int W, int Cin, int Cout, int n_cu, bool has_res);   // maps wider than 30: the 2-D tile form, where its tile arithmetic pays
 #ifdef FRP_LAB
-bool conv3x3_wino_lab_shape_ok(int W, int Cin, int ksize, int stride);   // + the maps only the lab's row-patch form covers (dbg bit 64)
+bool conv3x3_wino_lab_shape_ok(int W, int Cin, int ksize, int stride);   // + the maps only the lab's row-patch form covers (CONV_DBG_WINO_ROW_PATCH)
 #endif
 size_t conv3x3_wino_image_bytes(int Cin, int Cout);
 hipError_t launch_conv3x3_wino(const ConvParams& p, hipStream_t stream);
@@ -270,7 +328,8 @@ struct MatchParams {
 };
 int match_num_workgroups(long N);
 #define FRP_MATCH_TOP1_MAX 512   // queries per launch the persistent top-1 kernel covers (the only one that takes n_dev)
-hipError_t launch_match(const MatchParams& p, hipStream_t stream);
+// per_tile_only: never the persistent top-1 kernel (A/B runs: Switches::match_v1); a launch with n_dev then fails
+hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t stream);
 // top-k of each row of a device score matrix [M x N] by (cosine desc, row asc); -1 / -2.0 beyond N entries
 hipError_t launch_topk_rows(const float* scores, int M, long N, int k, int32_t* idx_out, float* cos_out, hipStream_t stream);
 

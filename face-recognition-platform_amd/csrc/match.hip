@@ -306,15 +306,15 @@ static int match_cu_count(int dev) {
 
 int match_num_workgroups(long N) { return (int)((N + MT_G - 1) / MT_G); }
 
-hipError_t launch_match(const MatchParams& p, hipStream_t stream) {
+hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t stream) {
     if (p.N <= 0 || p.M <= 0 || !p.gallery || !p.q || !p.part_cos || !p.part_idx || !p.best_cos || !p.best_idx)
         return hipErrorInvalidValue;
     if (p.Mpad % MT_Q != 0 || p.Mpad < p.M || p.n_wg != match_num_workgroups(p.N) || p.N > 0x7fffff00L)
         return hipErrorInvalidValue;
     MatchParams r = p;
     int dev = 0;
-    if (p.n_dev && (p.all_scores || p.Mpad > MT_MAXQT * MT_Q || getenv("FRP_MATCH_V1"))) return hipErrorInvalidValue;   // top-1 kernel only
-    if (!p.all_scores && p.Mpad <= MT_MAXQT * MT_Q && !getenv("FRP_MATCH_V1") && hipGetDevice(&dev) == hipSuccess) {
+    if (p.n_dev && (p.all_scores || p.Mpad > MT_MAXQT * MT_Q || per_tile_only)) return hipErrorInvalidValue;   // top-1 kernel only
+    if (!p.all_scores && p.Mpad <= MT_MAXQT * MT_Q && !per_tile_only && hipGetDevice(&dev) == hipSuccess) {
         // top-1 for a streaming batch: persistent workgroups, running winners in registers; its partials are the first
         // `grid` rows of the buffers the caller sized for the per-tile kernel (grid <= n_wg)
         const int ncu = match_cu_count(dev);

@@ -205,11 +205,11 @@ int frp_jpeg_coefficients(const uint8_t* data, size_t size, int16_t* coef, size_
  * frp_upload_frames_async does for raw frames: follow with frp_swap_frames.  Returns when the coefficients are staged; the
  * device half runs asynchronously on the copy stream. */
 int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B);
+/* network passes replayed from a captured hipGraph so far (round 5: a detector / embedder pass asked for a second time with the same shapes,
+ * buffers and switches is captured and from then on replayed by one call; FRP_NO_GRAPH turns that off) - tests and diagnosis */
+int64_t frp_debug_graph_replays(frp_handle* h);
 /* diagnostic: batches of this handle whose ENTROPY decode ran on the device too (every frame carries restart intervals of at most 32
  * MCUs - one thread per interval; longer intervals: the host decoder, unless FRP_JPEG_DEVICE_HUFFMAN=1; =0: always the host) */
-/* network passes replayed from a captured hipGraph so far (round 5: a detector / embedder pass asked for a second time with the same shapes,
- * buffers and switches is captured and from then on replayed by one call; FRP_NO_GRAPH=1 turns that off) - tests and diagnosis */
-int64_t frp_debug_graph_replays(frp_handle* h);
 int64_t frp_debug_jpeg_device_batches(frp_handle* h);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ----------------------------------------------------
@@ -281,7 +281,25 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
 int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, int64_t n_cols);
 
 /* one convolution through the MFMA kernel on host tensors (kernel parity tests):
- * x [N,H,W,Cin] fp16, w [Cout][k][k][Cin] fp16, bias fp32 [Cout] or [9][Cout], out fp16 or fp32 */
+ * x [N,H,W,Cin] fp16, w [Cout][k][k][Cin] fp16, bias fp32 [Cout] or [9][Cout], out fp16 or fp32
+ * flags (0: what the engine would launch for this shape, as set by the environment switches of INTEGRATION.md):
+ *   bit 0      bias [9][Cout], one row per border class of the output pixel
+ *   bit 1      fp32 output
+ *   bit 2      res [N,res_h,res_w,Cout] at half resolution, upsampled x2 on the fly
+ *   bit 8      the generic kernel, also where a specialised one covers the shape
+ *   bit 9      lab build: the first-generation row-patch kernel's pre-prefetch k-step
+ *   bits 9-12  lab build: the number of a timing ablation of the Winograd kernel
+ *   bits 10-13 lab build: the number of a timing ablation of the first-generation row-patch kernel (wrong results)
+ *   bit 13     lab build: the Winograd kernel with one wave per SIMD
+ *   bit 14     head outputs (Cout <= 32) on all 64 rows of the tile; lab build: the first-generation row-patch / Winograd kernels
+ *   bit 15     64-cout layers in 256-pixel tiles; lab build: the Winograd kernel's first-generation k-loop
+ *   bit 16     through the Winograd kernel (an error where it does not cover the shape), never in quarter tiles
+ *   bit 17/18  quarter tiles (128 pixels x 64 couts) always / never; default: by the tile count
+ *   bit 19     lab build: the Winograd kernel's 2-D tiles whatever the shape
+ *   bit 20     not the 64 -> 64 register-resident kernel
+ *   bit 21     the opt-in stride-2 row-patch kernel
+ *   bit 22     the 64 -> 64 kernel with all waves in the same order (A/B of its ping-pong schedule)
+ * (bits 8-15 and 19-22: csrc/frp_internal.h, CONV_DBG_*) */
 int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t W, int32_t Cin,
                     const void* w, int32_t Cout, int32_t ksize, int32_t stride,
                     const float* bias, const float* slope, const void* res, int32_t res_h, int32_t res_w,

@@ -481,7 +481,7 @@ static hipError_t launch_c64_geo(const ConvParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-// maps on which the launch of the embedder's first 64 -> 64 conv also computes the stem in front of it (frp_api.cpp: run_net): where the
+// maps on which the launch of the embedder's first 64 -> 64 conv also computes the stem in front of it (net_program.cpp: run_net): where the
 // kernel is routed anyway
 bool conv3x3_c64_fuses_stem(int N, int H, int W, int n_cu) {
     ConvParams q{};

@@ -10,7 +10,7 @@
 // Arithmetic.  Output pixels are taken in horizontal PAIRS (x = 2j, 2j+1; W even).  Per kernel row kh and input channel:
 //     d0..d3 = x[y+kh-1][2j-1 .. 2j+2]                       (zero outside the image)
 //     V0 = d0 - d2   V1 = d1 + d2   V2 = d2 - d1   V3 = d1 - d3            (B^T d, packed fp16, in registers)
-//     U0 = g0        U1 = (g0+g1+g2)/2   U2 = (g0-g1+g2)/2   U3 = g2        (G g, once at load time: frp_api.cpp)
+//     U0 = g0        U1 = (g0+g1+g2)/2   U2 = (g0-g1+g2)/2   U3 = g2        (G g, once at load time: net_program.cpp)
 //     M_f += U_f * V_f  summed over (kh, cin) on the matrix cores, fp32      (4 frequencies instead of 6 products per pair)
 //     y[2j] = M0 + M1 + M2        y[2j+1] = M1 - M2 - M3                     (A^T M, fp32, in the epilogue)
 // fp16 products of exactly transformed fp16 operands, fp32 accumulation: on the seeded IResNet-100 the embedding moves by

@@ -22,6 +22,7 @@
 #endif
 #include "frp_blob.h"
 #include "frp_internal.h"
+#include "frp_handle.h"
 #include "jpeg_host.h"
 
 using namespace frp;
@@ -50,129 +51,6 @@ const ProcessSwitches& frp::process_switches() {
 }
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-struct TensorDims {
-    int h = 0, w = 0, c = 0;
-    bool f32 = false;
-    bool f8 = false;      // OCP E4M3 bytes (BASELINE config 5: fp8 matrix path of the embedder)
-};
-
-struct Net {
-    std::vector<frp_conv_op> ops;
-    int n_bufs = 0;
-    int in_buf = 0, in_ch = 0;
-    std::vector<DevBuf> bufs;
-    std::vector<TensorDims> dims;   // per physical buffer, for the last planned shape
-    std::vector<int64_t> wino_off;  // per op: byte offset of its Winograd weight image in the data section, or -1
-    // K-concat (conv_mfma.hip): a block's 1x1 stride-s shortcut conv folded into its 3x3 stride-s conv as a second K segment
-    std::vector<int> kc_skip;       // per op: 1 = a shortcut conv that its consumer computes (not launched)
-    std::vector<int> kc_src;        // per op: index of the shortcut op folded into this conv, or -1
-    std::vector<int64_t> kc_w_off, kc_bias_off;   // per consumer op: concatenated weights [Cout][9 Cin + Cin2] / summed bias [Cout]
-};
-
-enum { EV_START = 0, EV_H2D, EV_PRE, EV_DET, EV_DEC, EV_ALIGN, EV_EMB, EV_L2, EV_MATCH, EV_D2H, EV_COUNT };
-
-// A network pass as a captured hipGraph (round 5): the ~50 / ~85 launches of a detector / embedder pass replayed by ONE call when the
-// same pass - same program, shapes, buffers, operands, switches - is asked for again (run_net).  What the host side of the pass does
-// besides launching (counters, the FC's split-K bookkeeping, the planned dims) is recorded with it and re-applied on replay.
-struct NetGraph {
-    std::string key;
-    hipGraphExec_t exec = nullptr;
-    uint64_t epoch = 0;                 // frp_handle::alloc_epoch at capture: any (re)allocation or weight load since makes it stale
-    double dflops = 0, df8flops = 0;
-    int64_t dlaunches = 0, df8launches = 0;
-    int fc_ksplit = 0, fc_ktot = 0;
-    const float* fc_bias = nullptr;
-    std::vector<TensorDims> dims;
-};
-
-}  // namespace
-
-struct frp_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-    std::string err;
-    frp_config cfg{};
-    // weights
-    bool have_weights = false;
-    frp_blob_header hdr{};
-    DevBuf wdata;
-    Net det, emb;
-    // resident frames (tightly packed u8 [B,H,W,3])
-    DevBuf frames;
-    int rB = 0, rH = 0, rW = 0;
-    int n_cu = 256;                   // compute units of the device (queried once at create)
-    // overlapped ingest: the NEXT batch is copied on its own stream while the current one is processed
-    DevBuf frames_next;
-    int nB = 0, nH = 0, nW = 0;
-    bool next_valid = false;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_next_ready = nullptr, ev_next_free = nullptr;
-    std::vector<void*> pinned;       // frp_host_alloc blocks, freed with the handle
-    // detector source: the resident frames, or a resized copy of them (pyramid scales)
-    DevBuf scaled;
-    int dH = 0, dW = 0;              // dims of the detector source
-    bool det_scaled = false;
-    int canvas_h = 0, canvas_w = 0;
-    int det_op_limit = -1;           // >= 0: frp_debug_det_prefix - the detector program stops behind this many ops
-    // captured passes (run_net): graphs, the keys seen once (a pass is captured the SECOND time it is asked for: the first allocates and
-    // sets kernel attributes), the keys whose capture failed, the allocation epoch
-    std::vector<NetGraph> graphs;
-    std::vector<std::string> graph_seen, graph_bad;
-    uint64_t alloc_epoch = 1;
-    int64_t graph_replays = 0;
-    // multi-GPU (frp_dist_init): this handle's RCCL communicator, rank and world size
-    void* comm = nullptr;
-    int dist_rank = 0, dist_world = 0;
-    DevBuf det_hashes;               // frp_debug_det_hashes: one 64-bit hash per detector op, taken right behind the op
-    bool det_hash_on = false;
-    // per-call results (device)
-    DevBuf boxes, kps, scores, counts, anchor, face_slot, nfaces, q16, part_cos, part_idx, best_cos, best_idx, scratch, splitk_ws, dense_logits;
-    int fc_ksplit = 0;               // >0: the embedder's FC wrote split-K slabs; l2norm reduces them (-1: factor chosen on the device)
-    int fc_ktot = 0;
-    const float* fc_bias = nullptr;
-    int last_B = 0, last_K = 0, last_nfaces = 0;   // last_nfaces -1: count still on the device (resolve_count)
-    int last_cap = 0, pend_cap = 0;
-    double pend_flops = 0.0, pend_f8flops = 0.0;
-    bool ev_pending = false;   // frp_process_resident's stage events are recorded but not yet read (see settle_events)
-    bool last_matched = false;
-    int32_t* h_nfaces = nullptr;   // pinned
-    unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
-    size_t pin_cap = 0;
-    // gallery snapshot
-    DevBuf gallery;
-    int64_t g_rows = 0;
-    DevBuf g_reserved;               // frp_gallery_reserve: filled by the caller, swapped in by frp_gallery_commit
-    // JPEG ingest (frp_upload_jpeg_async): page-locked coefficient staging, device coefficients / tables / sample planes
-    // (two staging buffers in turn: the host decodes batch t+1 while the copy of batch t still reads the other one)
-    void* jpeg_pin[2] = {nullptr, nullptr};
-    size_t jpeg_pin_cap[2] = {0, 0};
-    int jpeg_turn = 0;
-    DevBuf jpeg_coef, jpeg_planes;
-    int64_t ctr_jpeg_device_batches = 0;   // batches whose entropy decode ran on the device (frp_debug_jpeg_device_batches)
-    DevBuf jpeg_scan, jpeg_err;      // device entropy decode (restart-interval streams): compressed scans + interval offsets + tables; per-image error flags
-    hipEvent_t ev_jpeg_h2d[2] = {nullptr, nullptr};     // the copy out of jpeg_pin[i] has finished
-    bool jpeg_h2d_pending[2] = {false, false};
-    // exact compat rows (frp_gallery_exact): float64 [g_rows x 512] as enrolled, next to the unit fp16 snapshot
-    bool g_exact = false;
-    DevBuf gx, gx_q, gx_out;
-    // profiling
-    hipEvent_t ev[EV_COUNT]{};
-    frp_counters ctr{};
-};
-
-namespace {
-
-int fail(frp_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
 
 // librccl, opened at first use (frp_dist_*: the gallery all-gather; a process that never goes multi-GPU does not load it)
 struct Rccl {
@@ -203,122 +81,6 @@ Rccl& rccl() {
     return r;
 }
 
-
-#define HIPCHK(h, expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return fail(h, FRP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));          \
-    } while (0)
-
-#define FRPCHK(expr)                 \
-    do {                             \
-        int _r = (expr);             \
-        if (_r != FRP_OK) return _r; \
-    } while (0)
-
-int ensure(frp_handle* h, DevBuf& b, size_t bytes) {
-    if (bytes <= b.cap && b.p) return FRP_OK;
-    if (b.p) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    const size_t want = std::max<size_t>(bytes, 256);
-    ++h->alloc_epoch;                   // (captured passes hold device pointers)
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return fail(h, FRP_ERR_OOM, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
-    }
-    b.cap = want;
-    return FRP_OK;
-}
-
-void release(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// OCP FP8 E4M3FN (bias 7, no infinities; S.1111.111 = NaN, decoded as 0 here: the packer never emits it)
-float fp8_e4m3_value(unsigned char c) {
-    const int e = (c >> 3) & 0xF, m = c & 7;
-    float v;
-    if (e == 15 && m == 7) v = 0.f;
-    else if (e == 0) v = std::ldexp((float)m / 8.0f, -6);
-    else v = std::ldexp(1.0f + (float)m / 8.0f, e - 7);
-    return (c & 0x80) ? -v : v;
-}
-
-// fp32 -> fp16 bit pattern, round to nearest even (the rounding of numpy's astype(float16))
-uint16_t f32_to_f16_bits(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u) return (uint16_t)(sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));     // NaN / inf
-    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                                    // rounds to inf (>= 65520)
-    if (x < 0x33000001u) return (uint16_t)sign;                                                 // rounds to zero (<= 2^-25)
-    const int exp = (int)(x >> 23) - 127;
-    uint32_t mant = (x & 0x7fffffu) | 0x800000u;
-    int shift;
-    uint32_t base;
-    if (exp < -14) { shift = 13 + (-14 - exp); base = 0; }                                      // subnormal half
-    else { shift = 13; base = (uint32_t)(exp + 15) << 10; mant &= 0x7fffffu; }
-    uint32_t q = mant >> shift;
-    const uint32_t rem = mant & ((1u << shift) - 1), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (q & 1u))) ++q;                                            // a carry walks into the exponent
-    return (uint16_t)(sign | (base + q));
-}
-
-float f16_bits_to_f32(uint16_t hbits) {
-    const uint32_t sign = (uint32_t)(hbits & 0x8000u) << 16;
-    const int e = (hbits >> 10) & 31;
-    const uint32_t m = hbits & 0x3ffu;
-    float v;
-    if (e == 0) v = std::ldexp((float)m, -24);
-    else if (e == 31) v = m ? NAN : INFINITY;
-    else v = std::ldexp((float)(m | 0x400u), e - 25);
-    uint32_t bits;
-    memcpy(&bits, &v, 4);
-    bits |= sign;
-    memcpy(&v, &bits, 4);
-    return v;
-}
-
-// Weight image of the Winograd kernel (conv3x3_wino.hip) from folded fp16 weights [Cout][3][3][Cin]: per (cout tile of
-// 128, 64-channel block, kernel row, 16-channel slice) one 16 KiB stage = the LDS image itself: [frequency f][32-cout block]
-// [32 x 16-byte slots] (couts beyond Cout zero), the 8-channel half h of cout r of a block at slot (2 r + h) ^ ((r >> 3) & 1):
-// every fragment of a stage is one per-lane base + an immediate (conv3x3_wino.hip: wino_u_slot).  U = G g: g0, (g0+g1+g2)/2,
-// (g0-g1+g2)/2, g2 - exact in fp32 on fp16 inputs, rounded once.
-void build_wino_image(const uint16_t* w16, int Cin, int Cout, uint16_t* img) {
-    const int cpt = Cin / 64, nct = (Cout + 127) / 128;
-    for (int ct = 0; ct < nct; ++ct)
-        for (int cb = 0; cb < cpt; ++cb)
-            for (int kh = 0; kh < 3; ++kh)
-                for (int kk = 0; kk < 4; ++kk) {
-                    uint16_t* st = img + ((((size_t)ct * cpt + cb) * 3 + kh) * 4 + kk) * 8192;
-                    for (int row = 0; row < 128; ++row) {
-                        const int co = ct * 128 + row;
-                        for (int hh = 0; hh < 2; ++hh)
-                            for (int e = 0; e < 8; ++e) {
-                                const int ci = cb * 64 + kk * 16 + hh * 8 + e;
-                                float g[3] = {0.f, 0.f, 0.f};
-                                if (co < Cout)
-                                    for (int kw = 0; kw < 3; ++kw) g[kw] = f16_bits_to_f32(w16[(((size_t)co * 3 + kh) * 3 + kw) * Cin + ci]);
-                                const float u[4] = {g[0], (g[0] + g[1] + g[2]) * 0.5f, (g[0] - g[1] + g[2]) * 0.5f, g[2]};
-                                // stage layout (conv3x3_wino.hip: wino_u_slot): [f][32-cout block][slot (2 r + h) ^ ((r >> 3) & 1)][8 channels]
-                                const int r = row & 31, slot = (2 * r + hh) ^ ((r >> 3) & 1);
-                                for (int f = 0; f < 4; ++f) st[f * 2048 + (row >> 5) * 512 + slot * 8 + e] = f32_to_f16_bits(u[f]);
-                            }
-                    }
-                }
-}
-
 float logit_threshold(float t) {
     if (!(t > 0.f)) return -INFINITY;
     if (t >= 1.f) return INFINITY;
@@ -327,445 +89,6 @@ float logit_threshold(float t) {
 
 void rec(frp_handle* h, int which) {
     if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream);
-}
-
-// Plan + run one conv program.  in dims: [batch, H, W, in_ch] already written to bufs[in_buf].
-int plan_net(frp_handle* h, Net& net, int batch, int H, int W, bool skip_input = false) {
-    net.dims.assign(net.n_bufs, TensorDims());
-    std::vector<size_t> need(net.n_bufs, 0);
-    net.dims[net.in_buf] = {H, W, net.in_ch, false};
-    need[net.in_buf] = skip_input ? 0 : (size_t)batch * H * W * net.in_ch * 2;
-    for (const frp_conv_op& op : net.ops) {
-        TensorDims in = net.dims[op.in_buf];
-        if (in.c == 0) return fail(h, FRP_ERR_BLOB, "program reads an unwritten buffer");
-        if (op.flags & FRP_FLAG_FLATTEN) in = {1, 1, in.h * in.w * in.c, false};
-        if (in.c != op.cin) return fail(h, FRP_ERR_BLOB, "program channel mismatch");
-        const int pad = op.ksize / 2;
-        TensorDims out;
-        out.h = (in.h + 2 * pad - op.ksize) / op.stride + 1;
-        out.w = (in.w + 2 * pad - op.ksize) / op.stride + 1;
-        out.c = op.cout;
-        out.f32 = (op.flags & FRP_FLAG_OUT_F32) != 0;
-        if (out.h <= 0 || out.w <= 0) return fail(h, FRP_ERR_INVALID, "input too small for the network");
-        if (in.f32) return fail(h, FRP_ERR_BLOB, "program reads an fp32 tensor as a conv input");
-        const bool op_f8 = (op.flags & FRP_OPFLAG_FP8_MFMA) != 0;
-        if (in.f8 != op_f8) return fail(h, FRP_ERR_BLOB, "program operand precision mismatch (fp8 op <-> fp8 tensor)");
-        if (op_f8 && !(op.ksize == 3 && op.stride == 1 && (op.cin & 127) == 0 && !(op.flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_FLATTEN | FRP_FLAG_RES_UP2))))
-            return fail(h, FRP_ERR_BLOB, "op shape not covered by the fp8 matrix path");
-        out.f8 = (op.flags & FRP_OPFLAG_OUT_FP8) != 0;
-        if (out.f8 && (out.f32 || !op_f8)) return fail(h, FRP_ERR_BLOB, "fp8 primary output needs an fp8 op");
-        if (op.res_buf >= 0) {                     // the epilogue reads the residual unchecked: validate it here
-            const TensorDims& r = net.dims[op.res_buf];
-            const bool up2 = (op.flags & FRP_FLAG_RES_UP2) != 0;
-            if (r.c != op.cout || r.f32 || r.f8 || (up2 ? (r.h * 2 != out.h || r.w * 2 != out.w) : (r.h != out.h || r.w != out.w)))
-                return fail(h, FRP_ERR_BLOB, "program residual shape mismatch");
-        }
-        net.dims[op.out_buf] = out;
-        need[op.out_buf] = std::max(need[op.out_buf], (size_t)batch * out.h * out.w * out.c * (out.f32 ? 4 : out.f8 ? 1 : 2));
-        if (op.out2_buf >= 0) {                    // fp8 copy of an fp16 primary output
-            if (out.f32 || out.f8) return fail(h, FRP_ERR_BLOB, "fp8 copy of a non-fp16 output");
-            TensorDims o2 = out;
-            o2.f8 = true;
-            net.dims[op.out2_buf] = o2;
-            need[op.out2_buf] = std::max(need[op.out2_buf], (size_t)batch * out.h * out.w * out.c);
-        }
-    }
-    for (int i = 0; i < net.n_bufs; ++i)
-        if (need[i]) FRPCHK(ensure(h, net.bufs[i], need[i]));
-    return FRP_OK;
-}
-
-// first detector op as the fused u8 stem (no NHWC8 blob)?
-bool stem_fusable(const Net& net) {
-    if (net.ops.empty()) return false;
-    const frp_conv_op& op = net.ops[0];
-    return op.in_buf == net.in_buf && op.cin == 8 && op.cout == 32 && op.ksize == 3 && op.stride == 2 &&
-           op.act == FRP_ACT_RELU && op.res_buf < 0 && (op.flags & ~0) == 0 && (op.real_ch & 0xffff) == 3;
-}
-
-// ... and the second one (3x3 s2 32->64 + ReLU) reading nothing but the first: both stems in one kernel
-bool stem12_fusable(const Net& net) {
-    if (!stem_fusable(net) || net.ops.size() < 2) return false;
-    const frp_conv_op& a = net.ops[0];
-    const frp_conv_op& b = net.ops[1];
-    if (!(b.in_buf == a.out_buf && b.cin == 32 && b.cout == 64 && b.ksize == 3 && b.stride == 2 && b.act == FRP_ACT_RELU &&
-          b.res_buf < 0 && b.flags == 0))
-        return false;
-    for (size_t i = 2; i < net.ops.size(); ++i)          // the stem1 map must have no other reader
-        if (net.ops[i].in_buf == a.out_buf || net.ops[i].res_buf == a.out_buf) {
-            // (physical buffers are recycled: a later tensor may live in the same buffer - only a read
-            // before the next write of that buffer would be the stem1 map)
-            bool rewritten = false;
-            for (size_t j = 2; j < i; ++j) rewritten |= net.ops[j].out_buf == a.out_buf;
-            if (!rewritten) return false;
-        }
-    return true;
-}
-
-// `n_dev`: the number of images that really exist lives in device memory (`batch` is then the capacity the buffers were
-// planned for): every kernel derives its tile count from it.  The flop counters are charged for `batch` images and
-// corrected by the caller once the count is known.
-// `allow_wino` false: the direct kernels also where a Winograd weight image exists (calls of few faces, run_embed).
-int run_net_body(frp_handle* h, const Switches& sw, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem,
-                 const int32_t* n_dev, bool allow_wino) {
-    // dims are re-derived while walking (physical buffers are reused by several tensors)
-    std::vector<TensorDims> d(net.n_bufs);
-    d[net.in_buf] = {H, W, net.in_ch, false};
-    const char* wbase = (const char*)h->wdata.p;
-    bool first = true;
-    size_t skip = 0;
-    if (&net == &h->det && h->det_hash_on) HIPCHK(h, hipMemsetAsync(h->det_hashes.p, 0, 64 * 8, h->stream));
-    // the kernel A/B bits of every conv launch of the pass (frp_internal.h: CONV_DBG_*)
-    const int dbg = (sw.s2 ? CONV_DBG_S2 : 0) | (process_switches().c64_all ? CONV_DBG_C64_ALL : 0);
-    // both detector stems in one kernel (the stem1 map never reaches HBM); FRP_NO_FUSED_STEM12 keeps
-    // stem1 (fused with the u8 normalisation) and stem2 (generic conv) apart for A/B runs
-    if (stem && stem12_fusable(net) && (stem->Hc % 4) == 0 && (stem->Wc % 4) == 0 && !sw.no_fused_stem12) {
-        const frp_conv_op& a = net.ops[0];
-        const frp_conv_op& b = net.ops[1];
-        Stem12Params sp{};
-        sp.frames = stem->frames; sp.B = stem->B; sp.H = stem->H; sp.W = stem->W;
-        sp.row_stride = stem->row_stride; sp.frame_stride = stem->frame_stride;
-        sp.Hc = stem->Hc; sp.Wc = stem->Wc; sp.Ho1 = stem->Hc / 2; sp.Wo1 = stem->Wc / 2; sp.Ho2 = stem->Hc / 4; sp.Wo2 = stem->Wc / 4;
-        sp.rgb_in = stem->rgb_in;
-        sp.w1 = (const _Float16*)(wbase + a.w_off); sp.bias1 = (const float*)(wbase + a.bias_off);
-        sp.w2 = (const _Float16*)(wbase + b.w_off); sp.bias2 = (const float*)(wbase + b.bias_off);
-        sp.out = (_Float16*)net.bufs[b.out_buf].p;
-        hipError_t e = launch_stem12_u8(sp, h->stream);
-        if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("launch_stem12_u8: ") + hipGetErrorString(e));
-        d[a.out_buf] = {sp.Ho1, sp.Wo1, 32, false};
-        d[b.out_buf] = {sp.Ho2, sp.Wo2, 64, false};
-        *flops += 2.0 * batch * sp.Ho1 * sp.Wo1 * 9.0 * 3 * 32 + 2.0 * batch * sp.Ho2 * sp.Wo2 * 9.0 * 32 * 64;
-        *launches += 1;
-        if (h->det_hash_on) {
-            e = launch_tensor_hash(sp.out, (size_t)batch * sp.Ho2 * sp.Wo2 * 64 * 2, (unsigned long long*)h->det_hashes.p + 1, h->stream);
-            if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("tensor_hash: ") + hipGetErrorString(e));
-        }
-        skip = 2;
-        first = false;
-    }
-    // embedder stem (chips NHWC8 -> 3x3 s1 3->64 + PReLU): dedicated kernel; FRP_NO_EMB_STEM keeps the generic one
-    bool fuse_stem = false, fuse_even_only = false;
-    size_t fuse_op = 0;
-    EmbStemParams fused{};
-    if (!stem && !net.ops.empty()) {
-        const frp_conv_op& a = net.ops[0];
-        if (a.in_buf == net.in_buf && a.cin == 8 && (a.real_ch & 0xffff) == 3 && a.cout == 64 && a.ksize == 3 && a.stride == 1 &&
-            a.act == FRP_ACT_PRELU && a.res_buf < 0 && a.flags == 0 && a.slope_off >= 0 && !sw.no_emb_stem) {
-            EmbStemParams ep{};
-            ep.x = (const _Float16*)net.bufs[a.in_buf].p;
-            ep.M = batch; ep.H = H; ep.W = W;
-            ep.w = (const _Float16*)(wbase + a.w_off);
-            ep.bias = (const float*)(wbase + a.bias_off);
-            ep.slope = (const float*)(wbase + a.slope_off);
-            ep.out = (_Float16*)net.bufs[a.out_buf].p;
-            ep.n_dev = n_dev;
-            // ... and where the conv behind it runs on the 64 -> 64 kernel (conv3x3_c64.hip), that launch computes the stem of its own
-            // input patch from the chips: the 64-channel map is written once (the block's shortcut reads it) and never read back by
-            // the conv; one launch fewer.  FRP_NO_STEM_FUSE: the two launches (A/B runs; the results are the same bits)
-            // (the next op that launches: the block's shortcut conv in between rides in a later k-loop - kc_skip - and reads the map then)
-            size_t nb = 1;
-            while (nb < net.ops.size() && nb < net.kc_skip.size() && net.kc_skip[nb]) ++nb;
-            if (nb < net.ops.size() && !sw.no_stem_fuse && sw.small_m <= 0) {
-                const frp_conv_op& b = net.ops[nb];
-                const bool plain = !(b.flags & ~FRP_FLAG_BORDER_BIAS) && (b.flags & FRP_FLAG_BORDER_BIAS) && b.out2_buf < 0 && b.res_buf < 0;
-                const bool chained = !(nb < net.kc_src.size() && net.kc_src[nb] >= 0);
-                // (the fused launch reads the chips while it writes both maps: none of the three buffers may be another's alias - this
-                // packer pins network inputs, a foreign blob's plan might not)
-                fuse_stem = plain && chained && b.in_buf == a.out_buf && b.out_buf != a.out_buf && b.out_buf != a.in_buf && a.out_buf != a.in_buf && b.cin == 64 && b.cout == 64 && b.ksize == 3 &&
-                            b.stride == 1 && b.act == FRP_ACT_PRELU && b.slope_off >= 0 && conv3x3_c64_fuses_stem(batch, H, W, h->n_cu);
-                fuse_op = nb;
-                // who else reads the stem's map?  Only shortcut convs (1x1, stride 2) that ride in a later k-loop: then a quarter of its
-                // pixels is all that has to reach HBM
-                fuse_even_only = true;
-                for (size_t j = 1; j < net.ops.size(); ++j) {
-                    const frp_conv_op& o = net.ops[j];
-                    if (j == nb || (o.in_buf != a.out_buf && o.res_buf != a.out_buf)) continue;
-                    const bool shortcut = j < net.kc_skip.size() && net.kc_skip[j] && o.in_buf == a.out_buf && o.res_buf != a.out_buf &&
-                                          o.ksize == 1 && o.stride == 2;
-                    if (!shortcut) fuse_even_only = false;
-                }
-            }
-            if (fuse_stem) {
-                fused = ep;
-            } else {
-                hipError_t e = launch_emb_stem(ep, h->stream);
-                if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("launch_emb_stem: ") + hipGetErrorString(e));
-                *launches += 1;
-            }
-            d[a.out_buf] = {H, W, 64, false};
-            *flops += 2.0 * batch * H * W * 9.0 * 3 * 64;
-            skip = 1;
-            first = false;
-        }
-    }
-    for (const frp_conv_op& op : net.ops) {
-        if (&net == &h->det && h->det_op_limit >= 0 && (int)(&op - net.ops.data()) >= h->det_op_limit) break;   // (diagnostic prefix run)
-        if (skip) { --skip; continue; }
-        if (first && stem) {
-            first = false;
-            StemParams sp = *stem;
-            sp.w = (const _Float16*)(wbase + op.w_off);
-            sp.bias = (const float*)(wbase + op.bias_off);
-            sp.out = (_Float16*)net.bufs[op.out_buf].p;
-            hipError_t e = launch_stem_u8(sp, h->stream);
-            if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("launch_stem_u8: ") + hipGetErrorString(e));
-            d[op.out_buf] = {sp.Ho, sp.Wo, 32, false};
-            *flops += 2.0 * batch * sp.Ho * sp.Wo * 9.0 * 3 * 32;
-            *launches += 1;
-            continue;
-        }
-        first = false;
-        TensorDims in = d[op.in_buf];
-        if (op.flags & FRP_FLAG_FLATTEN) in = {1, 1, in.h * in.w * in.c, false};
-        const size_t opi = (size_t)(&op - net.ops.data());
-        if (opi < net.kc_skip.size() && net.kc_skip[opi]) {        // a shortcut conv its consumer computes (K-concat): FLOPs charged here
-            TensorDims o;
-            o.h = (in.h - 1) / op.stride + 1;
-            o.w = (in.w - 1) / op.stride + 1;
-            o.c = op.cout;
-            d[op.out_buf] = o;
-            *flops += 2.0 * batch * o.h * o.w * (double)op.cin * op.cout;
-            continue;
-        }
-        ConvParams p{};
-        p.x = (const _Float16*)net.bufs[op.in_buf].p;
-        p.w = (const _Float16*)(wbase + op.w_off);
-        p.bias = (const float*)(wbase + op.bias_off);
-        p.slope = op.slope_off >= 0 ? (const float*)(wbase + op.slope_off) : nullptr;
-        p.res = op.res_buf >= 0 ? (const _Float16*)net.bufs[op.res_buf].p : nullptr;
-        p.out = net.bufs[op.out_buf].p;
-        p.N = batch; p.H = in.h; p.W = in.w; p.Cin = op.cin; p.Cout = op.cout;
-        p.KS = op.ksize; p.stride = op.stride; p.act = op.act;
-        p.n_dev = n_dev;
-        p.n_cu = h->n_cu;
-        p.small_m = sw.small_m;
-        p.dbg = dbg;
-        if (fuse_stem && opi == fuse_op) {
-            p.stem_x = fused.x; p.stem_w = fused.w; p.stem_bias = fused.bias; p.stem_slope = fused.slope; p.stem_out = fused.out;
-            p.stem_even_only = fuse_even_only ? 1 : 0;
-        }
-        p.wino_wide_only = &net == &h->det ? 1 : 0;
-        {
-            const size_t oi = (size_t)(&op - net.ops.data());
-            if (allow_wino && oi < net.wino_off.size() && net.wino_off[oi] >= 0) p.wino_w = (const _Float16*)(wbase + net.wino_off[oi]);
-        }
-        p.flags = op.flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2);
-        if (op.flags & FRP_FLAG_RES_UP2) { p.Hr = d[op.res_buf].h; p.Wr = d[op.res_buf].w; }
-        p.in_scale = p.out_scale = 1.0f;
-        if (op.flags & FRP_OPFLAG_FP8_MFMA) {      // fp8 operands: E4M3 weights as stored, per-cout scales behind them
-            const size_t welems = (size_t)op.cout * op.ksize * op.ksize * op.cin;
-            p.flags |= FRP_FLAG_F8;
-            p.wscale = (const float*)(wbase + op.w_off + (welems + 15) / 16 * 16);
-            p.in_scale = op.in_scale;
-        }
-        if (opi < net.kc_src.size() && net.kc_src[opi] >= 0) {      // K-concat: the block's shortcut conv rides in this conv's k-loop
-            const frp_conv_op& sc = net.ops[net.kc_src[opi]];
-            p.x2 = (const _Float16*)net.bufs[sc.in_buf].p;
-            p.Cin2 = sc.cin;
-            p.w = (const _Float16*)(wbase + net.kc_w_off[opi]);
-            p.bias = (const float*)(wbase + net.kc_bias_off[opi]);
-            p.res = nullptr;
-        }
-        if (op.flags & FRP_OPFLAG_OUT_FP8) p.flags |= FRP_FLAG_OUT_FP8;
-        if (op.out2_buf >= 0) p.out2 = net.bufs[op.out2_buf].p;
-        if ((op.flags & FRP_OPFLAG_OUT_FP8) || op.out2_buf >= 0) p.out_scale = op.out_scale;
-        // skinny fp32-output GEMM (the FC): split K over the CUs; the slabs are reduced (+bias) by
-        // the l2norm kernel that follows
-        h->fc_ksplit = 0;
-        if ((op.flags & FRP_FLAG_OUT_F32) && &op == &net.ops.back()) {
-            const int ncu = h->n_cu;
-            const int hw_out = ((in.h + 2 * (op.ksize / 2) - op.ksize) / op.stride + 1) * ((in.w + 2 * (op.ksize / 2) - op.ksize) / op.stride + 1);
-            // device-side count: the kernel picks the factor of the real batch itself (the same function), the slabs are
-            // sized for the largest one - that of a single image - times the capacity
-            const int ks = conv_pick_ksplit((n_dev ? 1 : batch) * hw_out, op.cout, op.ksize * op.ksize * op.cin, op.flags, op.res_buf >= 0, ncu);
-            if (ks > 1) {
-                const size_t slab = (size_t)ks * batch * op.cout * 4;   // 1x1 output per image for the FC shape
-                if (in.h == 1 && in.w == 1 && ensure(h, h->splitk_ws, slab) == FRP_OK) {
-                    p.ksplit = n_dev ? -1 : ks;
-                    p.out = h->splitk_ws.p;
-                    h->fc_ksplit = p.ksplit;
-                    h->fc_bias = p.bias;
-                    h->fc_ktot = op.ksize * op.ksize * op.cin;
-                }
-            }
-        }
-        // the weights the NEXT launch will stream (a quarter-tile launch with CUs to spare warms the L2s with them: conv_common.h)
-        for (size_t nx = opi + 1; nx < net.ops.size(); ++nx) {
-            if (nx < net.kc_skip.size() && net.kc_skip[nx]) continue;
-            const frp_conv_op& no = net.ops[nx];
-            const size_t es = (no.flags & FRP_OPFLAG_FP8_MFMA) ? 1 : 2;
-            if (nx < net.kc_src.size() && net.kc_src[nx] >= 0) {
-                p.pf_ptr = wbase + net.kc_w_off[nx];
-                p.pf_bytes = (unsigned)((size_t)no.cout * (9 * (size_t)no.cin + net.ops[net.kc_src[nx]].cin) * 2);
-            } else if (allow_wino && nx < net.wino_off.size() && net.wino_off[nx] >= 0) {
-                p.pf_ptr = wbase + net.wino_off[nx];
-                p.pf_bytes = (unsigned)std::min<size_t>(conv3x3_wino_image_bytes(no.cin, no.cout), 0x7fffffffu);
-            } else {
-                p.pf_ptr = wbase + no.w_off;
-                p.pf_bytes = (unsigned)std::min<size_t>((size_t)no.cout * no.ksize * no.ksize * no.cin * es, 0x7fffffffu);
-            }
-            break;
-        }
-        hipError_t e = launch_conv(p, h->stream);
-        if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("launch_conv: ") + hipGetErrorString(e));
-        const int pad = op.ksize / 2;
-        TensorDims out;
-        out.h = (in.h + 2 * pad - op.ksize) / op.stride + 1;
-        out.w = (in.w + 2 * pad - op.ksize) / op.stride + 1;
-        out.c = op.cout;
-        out.f32 = (op.flags & FRP_FLAG_OUT_F32) != 0;
-        out.f8 = (op.flags & FRP_OPFLAG_OUT_FP8) != 0;
-        d[op.out_buf] = out;
-        if (op.out2_buf >= 0) { TensorDims o2 = out; o2.f8 = true; d[op.out2_buf] = o2; }
-        if (&net == &h->det && h->det_hash_on && opi < 64 && !n_dev) {      // (diagnostic: hash of this op's output, in stream order)
-            e = launch_tensor_hash(net.bufs[op.out_buf].p, (size_t)batch * out.h * out.w * out.c * (out.f32 ? 4 : 2),
-                                   (unsigned long long*)h->det_hashes.p + opi, h->stream);
-            if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("tensor_hash: ") + hipGetErrorString(e));
-        }
-        const int cin_r = op.real_ch & 0xffff, cout_r = (op.real_ch >> 16) & 0xffff;
-        const double fl = 2.0 * batch * out.h * out.w * (double)op.ksize * op.ksize * (cin_r ? cin_r : op.cin) * (cout_r ? cout_r : op.cout);
-        *flops += fl;
-        if (op.flags & FRP_OPFLAG_FP8_MFMA) { h->ctr.f8_conv_flops += fl; h->ctr.f8_conv_launches += 1; }
-        *launches += 1;
-    }
-    net.dims = d;
-    return FRP_OK;
-}
-
-static void drop_graphs(frp_handle* h) {
-    for (NetGraph& g : h->graphs)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    h->graphs.clear();
-    h->graph_seen.clear();
-    h->graph_bad.clear();
-}
-
-// The pass, replayed from its captured graph when it has been asked for before (FRP_NO_GRAPH: always launch by launch).  The key names
-// everything the launches depend on that is not fixed by the loaded weights: program, shapes, family, operand pointers, the bytes of the
-// switch snapshot; device buffers and weights are covered by the allocation epoch.  Not with stage timers (events between the
-// passes are fine, but the diagnostics inside a pass are not captured), not with the detector diagnostics.
-int run_net(frp_handle* h, const Switches& sw, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem = nullptr,
-            const int32_t* n_dev = nullptr, bool allow_wino = true) {
-    if (process_switches().no_graph || h->det_hash_on || h->det_op_limit >= 0)
-        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    char kb[512];
-    int len = snprintf(kb, sizeof kb, "%c|%d|%d|%d|%d|%p|%p|", &net == &h->det ? 'd' : 'e', batch, H, W, (int)allow_wino, (const void*)n_dev,
-                       (const void*)h->wdata.p);
-    if (stem && len > 0 && len < (int)sizeof kb)
-        len += snprintf(kb + len, sizeof kb - len, "%p|%d|%d|%d|%ld|%ld|%d|%d|%d", (const void*)stem->frames, stem->B, stem->H, stem->W, stem->row_stride,
-                        stem->frame_stride, stem->Hc, stem->Wc, stem->rgb_in);
-    if (len <= 0 || len >= (int)sizeof kb) return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    const std::string key = std::string(kb, len) + std::string(reinterpret_cast<const char*>(&sw), sizeof sw);
-    for (size_t i = 0; i < h->graphs.size(); ++i) {
-        NetGraph& g = h->graphs[i];
-        if (g.key != key) continue;
-        if (g.epoch != h->alloc_epoch) {            // its buffers may have moved
-            (void)hipGraphExecDestroy(g.exec);
-            h->graphs.erase(h->graphs.begin() + i);
-            break;
-        }
-        if (hipGraphLaunch(g.exec, h->stream) != hipSuccess) {      // (never seen; if the runtime refuses a replay, the pass is launched instead)
-            (void)hipGetLastError();
-            (void)hipGraphExecDestroy(g.exec);
-            h->graphs.erase(h->graphs.begin() + i);
-            h->graph_bad.push_back(key);
-            break;
-        }
-        *flops += g.dflops;
-        *launches += g.dlaunches;
-        h->ctr.f8_conv_flops += g.df8flops;
-        h->ctr.f8_conv_launches += g.df8launches;
-        h->fc_ksplit = g.fc_ksplit; h->fc_bias = g.fc_bias; h->fc_ktot = g.fc_ktot;
-        net.dims = g.dims;
-        h->graph_replays += 1;
-        return FRP_OK;
-    }
-    auto has = [](const std::vector<std::string>& v, const std::string& k) { for (const std::string& x : v) if (x == k) return true; return false; };
-    if (has(h->graph_bad, key) || !has(h->graph_seen, key)) {
-        if (h->graph_seen.size() > 256) h->graph_seen.clear();
-        if (!has(h->graph_seen, key)) h->graph_seen.push_back(key);
-        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    }
-    // second request for this pass: capture it (thread-local mode: the other lanes' threads keep allocating and synchronising as they like)
-    const uint64_t epoch0 = h->alloc_epoch;
-    const double f0 = *flops, f80 = h->ctr.f8_conv_flops;
-    const int64_t l0 = *launches, l80 = h->ctr.f8_conv_launches;
-    if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        h->graph_bad.push_back(key);
-        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    }
-    const int rc = run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(h->stream, &graph);
-    NetGraph g;
-    bool ok = rc == FRP_OK && ce == hipSuccess && graph && h->alloc_epoch == epoch0;
-    if (ok) ok = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess;
-    if (graph) (void)hipGraphDestroy(graph);
-    if (!ok) {
-        // nothing of the captured pass has run: say so once, then do it launch by launch (the counters were charged by the capture pass)
-        (void)hipGetLastError();
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        h->graph_bad.push_back(key);
-        if (rc != FRP_OK) return rc;
-        *flops = f0; *launches = l0; h->ctr.f8_conv_flops = f80; h->ctr.f8_conv_launches = l80;
-        return run_net_body(h, sw, net, batch, H, W, flops, launches, stem, n_dev, allow_wino);
-    }
-    g.key = key;
-    g.epoch = epoch0;
-    g.dflops = *flops - f0; g.dlaunches = *launches - l0;
-    g.df8flops = h->ctr.f8_conv_flops - f80; g.df8launches = h->ctr.f8_conv_launches - l80;
-    g.fc_ksplit = h->fc_ksplit; g.fc_bias = h->fc_bias; g.fc_ktot = h->fc_ktot;
-    g.dims = net.dims;
-    if (h->graphs.size() >= 16) {                  // (two frame buffers x two networks x a few call shapes; the oldest goes)
-        (void)hipGraphExecDestroy(h->graphs.front().exec);
-        h->graphs.erase(h->graphs.begin());
-    }
-    const hipError_t le = hipGraphLaunch(g.exec, h->stream);
-    h->graphs.push_back(g);
-    if (le != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    return FRP_OK;
-}
-
-int parse_net(frp_handle* h, const unsigned char* blob, size_t bytes, uint64_t off, uint32_t n_ops, uint32_t n_bufs,
-              uint32_t in_buf, uint32_t in_ch, uint64_t data_bytes, Net& net) {
-    if (off > bytes || n_ops > (bytes - off) / sizeof(frp_conv_op)) return fail(h, FRP_ERR_BLOB, "op table out of range");
-    if (n_bufs == 0 || n_bufs > 4096 || in_buf >= n_bufs) return fail(h, FRP_ERR_BLOB, "bad buffer count");
-    for (DevBuf& b : net.bufs) release(b);
-    net.ops.resize(n_ops);
-    if (n_ops) memcpy(net.ops.data(), blob + off, (size_t)n_ops * sizeof(frp_conv_op));
-    net.n_bufs = (int)n_bufs;
-    net.in_buf = (int)in_buf;
-    net.in_ch = (int)in_ch;
-    net.bufs.assign(n_bufs, DevBuf());
-    for (const frp_conv_op& op : net.ops) {
-        if (op.in_buf < 0 || op.in_buf >= (int)n_bufs || op.out_buf < 0 || op.out_buf >= (int)n_bufs ||
-            op.res_buf >= (int)n_bufs || op.res_buf < -1 || op.in_buf == op.out_buf || op.res_buf == op.out_buf)
-            return fail(h, FRP_ERR_BLOB, "op buffer id out of range");
-        if ((op.flags & FRP_FLAG_RES_UP2) && op.res_buf < 0) return fail(h, FRP_ERR_BLOB, "upsampled residual without a residual buffer");
-        if (op.out2_buf < -1 || op.out2_buf >= (int)n_bufs || op.out2_buf == op.in_buf || op.out2_buf == op.out_buf ||
-            (op.out2_buf >= 0 && op.out2_buf == op.res_buf))
-            return fail(h, FRP_ERR_BLOB, "op second-output buffer id out of range");
-        if ((op.flags & FRP_OPFLAG_FP8_MFMA) && !(op.flags & FRP_OPFLAG_W_FP8)) return fail(h, FRP_ERR_BLOB, "fp8 op without fp8 weights");
-        if ((op.flags & (FRP_OPFLAG_FP8_MFMA | FRP_OPFLAG_OUT_FP8)) || op.out2_buf >= 0) {
-            if (!(op.in_scale > 0.f) || !(op.out_scale > 0.f) || !std::isfinite(op.in_scale) || !std::isfinite(op.out_scale))
-                return fail(h, FRP_ERR_BLOB, "fp8 tensor scale must be positive and finite");
-        }
-        if (!(op.ksize == 1 || op.ksize == 3) || !(op.stride == 1 || op.stride == 2) || op.cin < 8 || (op.cin & 7) ||
-            op.cout < 4 || (op.cout & 3) || op.act < 0 || op.act > 2)
-            return fail(h, FRP_ERR_BLOB, "op shape not supported");
-        const uint64_t welems = (uint64_t)op.cout * op.ksize * op.ksize * op.cin;
-        // fp8 storage: one byte per element, then (16-byte aligned) cout fp32 scales
-        const uint64_t wbytes = (op.flags & FRP_OPFLAG_W_FP8) ? ((welems + 15) / 16 * 16 + (uint64_t)op.cout * 4) : welems * 2;
-        const uint64_t bbytes = (uint64_t)op.cout * 4 * ((op.flags & FRP_FLAG_BORDER_BIAS) ? 9 : 1);
-        if (op.w_off < 0 || (uint64_t)op.w_off + wbytes > data_bytes || (op.w_off & 15) || op.bias_off < 0 ||
-            (uint64_t)op.bias_off + bbytes > data_bytes || (op.bias_off & 15))
-            return fail(h, FRP_ERR_BLOB, "op tensor offset out of range");
-        if (op.act == FRP_ACT_PRELU &&
-            (op.slope_off < 0 || (uint64_t)op.slope_off + (uint64_t)op.cout * 4 > data_bytes || (op.slope_off & 15)))
-            return fail(h, FRP_ERR_BLOB, "op slope offset out of range");
-    }
-    return FRP_OK;
 }
 
 int upload_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride) {
@@ -821,7 +144,7 @@ int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float
     // The detector's first layer reads the u8 frames directly (fused normalise + conv) whenever
     // the program starts with the standard 3x3 s2 3->32 stem; FRP_NO_FUSED_STEM keeps the
     // two-kernel path (preprocess to an NHWC8 blob, then the generic conv) for A/B runs.
-    const bool fused = stem_fusable(h->det) && !sw.no_fused_stem;
+    const bool fused = h->det.det_stem && !sw.no_fused_stem;
     FRPCHK(plan_net(h, h->det, B, Hc, Wc, fused));
     FRPCHK(ensure_results(h, B, K));
     hipError_t e = hipSuccess;
@@ -886,15 +209,16 @@ int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float
 int run_embed(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev = nullptr, int family_count = -1) {
     if (n <= 0) return FRP_OK;
     if (family_count < 0) family_count = n;
+    FcSplitK fc;                          // the FC wrote split-K slabs: l2norm reduces them
     FRPCHK(run_net(h, sw, h->emb, n, FRP_CHIP, FRP_CHIP, &h->ctr.emb_conv_flops, &h->ctr.emb_conv_launches, nullptr, n_dev,
-                   family_count >= sw.wino_min_faces));
+                   family_count >= sw.wino_min_faces, &fc));
     rec(h, EV_EMB);
     const int mpad = round_up(n, 32);
     FRPCHK(ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2));
     HIPCHK(h, hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream));
     hipError_t e = launch_l2norm((float*)h->emb.bufs[h->hdr.emb_out_buf].p, (_Float16*)h->q16.p, n, FRP_EMB_DIM, h->stream,
-                                 h->fc_ksplit != 0 && h->fc_ksplit != 1 ? (const float*)h->splitk_ws.p : nullptr, h->fc_ksplit, h->fc_bias,
-                                 n_dev, h->fc_ktot, h->n_cu);
+                                 fc.ksplit != 0 && fc.ksplit != 1 ? (const float*)h->splitk_ws.p : nullptr, fc.ksplit, fc.bias, n_dev, fc.ktot,
+                                 h->n_cu);
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("l2norm: ") + hipGetErrorString(e));
     rec(h, EV_L2);
     return FRP_OK;
@@ -1310,145 +634,10 @@ int frp_load_weights(frp_handle* h, const void* blob, size_t bytes) {
     if (hd.data_offset > bytes || hd.data_bytes > bytes - hd.data_offset) return fail(h, FRP_ERR_BLOB, "data section out of range");
     if (hd.emb_dim != FRP_EMB_DIM || hd.emb_size != FRP_CHIP || hd.det_in_ch != 8 || hd.emb_in_ch != 8 || hd.det_num_anchors != 2)
         return fail(h, FRP_ERR_BLOB, "unsupported network geometry");
-    const unsigned char* b = (const unsigned char*)blob;
-    FRPCHK(parse_net(h, b, bytes, hd.det_ops_offset, hd.n_det_ops, hd.n_det_bufs, hd.det_in_buf, hd.det_in_ch, hd.data_bytes, h->det));
-    FRPCHK(parse_net(h, b, bytes, hd.emb_ops_offset, hd.n_emb_ops, hd.n_emb_bufs, hd.emb_in_buf, hd.emb_in_ch, hd.data_bytes, h->emb));
-    for (int l = 0; l < 3; ++l)
-        if (hd.det_head_buf[l] >= hd.n_det_bufs) return fail(h, FRP_ERR_BLOB, "head buffer id out of range");
-    if (hd.emb_out_buf >= hd.n_emb_bufs) return fail(h, FRP_ERR_BLOB, "embedding buffer id out of range");
-    // fp8-stored weights are expanded to fp16 behind the blob's data section (the kernels are the fp16 ones)
-    std::vector<unsigned char> expanded;
-    const unsigned char* data = b + hd.data_offset;
-    size_t data_bytes = hd.data_bytes;
-    bool any_fp8 = false;
-    for (Net* net : {&h->det, &h->emb})
-        for (const frp_conv_op& op : net->ops) any_fp8 |= (op.flags & FRP_OPFLAG_W_FP8) && !(op.flags & FRP_OPFLAG_FP8_MFMA);
-    if (any_fp8) {
-        expanded.assign(data, data + hd.data_bytes);
-        for (Net* net : {&h->det, &h->emb})
-            for (frp_conv_op& op : net->ops) {
-                if (!(op.flags & FRP_OPFLAG_W_FP8) || (op.flags & FRP_OPFLAG_FP8_MFMA)) continue;   // fp8 ops use the bytes as stored
-                const size_t per_row = (size_t)op.ksize * op.ksize * op.cin, n = per_row * op.cout;
-                const size_t src = (size_t)op.w_off, sc = src + (n + 15) / 16 * 16;
-                size_t dst = (expanded.size() + 255) / 256 * 256;
-                expanded.resize(dst + n * 2);
-                uint16_t* out16 = reinterpret_cast<uint16_t*>(expanded.data() + dst);
-                for (int r = 0; r < op.cout; ++r) {
-                    float scale;
-                    memcpy(&scale, data + sc + (size_t)r * 4, 4);
-                    for (size_t i = 0; i < per_row; ++i)
-                        out16[(size_t)r * per_row + i] = f32_to_f16_bits(fp8_e4m3_value(data[src + (size_t)r * per_row + i]) * scale);
-                }
-                op.w_off = (int64_t)dst;
-                op.flags &= ~FRP_OPFLAG_W_FP8;
-            }
-        data = expanded.data();
-        data_bytes = expanded.size();
-    }
-    // Winograd weight images (conv3x3_wino.hip) for the embedder's eligible 3x3 stride-1 layers, appended behind the data
-    // section.  The embedder's geometry is static (112 x 112 chips), so the map width of every op is known here; the
-    // detector's maps at camera resolutions are wider than the kernel's LDS holds.  FRP_NO_WINO: direct kernels only.
-    h->det.wino_off.assign(h->det.ops.size(), -1);
-    h->emb.wino_off.assign(h->emb.ops.size(), -1);
-    const Switches sw = read_switches();
-    if (!sw.no_wino) {
-        if (expanded.empty()) expanded.assign(data, data + hd.data_bytes);
-        std::vector<int> bw(h->emb.n_bufs, 0);
-        bw[h->emb.in_buf] = FRP_CHIP;
-        for (size_t i = 0; i < h->emb.ops.size(); ++i) {
-            const frp_conv_op& op = h->emb.ops[i];
-            const int win = (op.flags & FRP_FLAG_FLATTEN) ? 1 : bw[op.in_buf];
-            const int wout = (win + 2 * (op.ksize / 2) - op.ksize) / op.stride + 1;
-            bw[op.out_buf] = wout;
-            if (op.out2_buf >= 0) bw[op.out2_buf] = wout;
-            if (!conv3x3_wino_shape_ok(win, op.cin, op.ksize, op.stride) || op.cout < 64 ||
-                (op.flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_FLATTEN | FRP_FLAG_RES_UP2 | FRP_OPFLAG_W_FP8 | FRP_OPFLAG_FP8_MFMA | FRP_OPFLAG_OUT_FP8)) ||
-                op.out2_buf >= 0)
-                continue;
-            const size_t bytes = conv3x3_wino_image_bytes(op.cin, op.cout);
-            const size_t dst = (expanded.size() + 255) / 256 * 256;
-            expanded.resize(dst + bytes);
-            build_wino_image(reinterpret_cast<const uint16_t*>(expanded.data() + op.w_off), op.cin, op.cout,
-                             reinterpret_cast<uint16_t*>(expanded.data() + dst));
-            h->emb.wino_off[i] = (int64_t)dst;
-        }
-        // The detector's maps depend on the frame size, so which of its layers take the kernel (in its 2-D tile form: maps wider than
-        // 30 pixels) is decided per launch (conv3x3_wino.hip: wino_2d_pays); every 3x3 stride-1 layer of 128 channels and more that
-        // could gets an image here (a third more weight bytes for those layers).
-        for (size_t i = 0; i < h->det.ops.size(); ++i) {
-            const frp_conv_op& op = h->det.ops[i];
-            if (op.ksize != 3 || op.stride != 1 || (op.cin & 63) || op.cin < 128 || op.cout < 64 || op.out2_buf >= 0 ||
-                (op.flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_FLATTEN | FRP_FLAG_RES_UP2 | FRP_OPFLAG_W_FP8 | FRP_OPFLAG_FP8_MFMA | FRP_OPFLAG_OUT_FP8)))
-                continue;
-            const size_t bytes = conv3x3_wino_image_bytes(op.cin, op.cout);
-            const size_t dst = (expanded.size() + 255) / 256 * 256;
-            expanded.resize(dst + bytes);
-            build_wino_image(reinterpret_cast<const uint16_t*>(expanded.data() + op.w_off), op.cin, op.cout,
-                             reinterpret_cast<uint16_t*>(expanded.data() + dst));
-            h->det.wino_off[i] = (int64_t)dst;
-        }
-        data = expanded.data();
-        data_bytes = expanded.size();
-    }
-    // K-concat plans (both networks; FRP_NO_KCONCAT: every op as written in the blob)
-    for (Net* net : {&h->det, &h->emb}) {
-        const size_t n_ops = net->ops.size();
-        net->kc_skip.assign(n_ops, 0);
-        net->kc_src.assign(n_ops, -1);
-        net->kc_w_off.assign(n_ops, -1);
-        net->kc_bias_off.assign(n_ops, -1);
-        if (sw.no_kconcat) continue;
-        for (size_t j = 0; j < n_ops; ++j) {
-            const frp_conv_op& c = net->ops[j];
-            // consumer: 3x3 conv over whole channel blocks with a plain residual, fp16 operands, one bias class
-            if (c.ksize != 3 || c.res_buf < 0 || (c.cin & 63) || c.flags != 0) continue;
-            // producer of the residual: the last writer of res_buf before j
-            int i = -1;
-            for (int q = (int)j - 1; q >= 0; --q)
-                if (net->ops[q].out_buf == c.res_buf || net->ops[q].out2_buf == c.res_buf) { i = q; break; }
-            if (i < 0) continue;
-            const frp_conv_op& d = net->ops[i];
-            if (d.out_buf != c.res_buf || d.ksize != 1 || d.stride != c.stride || d.act != FRP_ACT_NONE || d.res_buf >= 0 || d.flags != 0 ||
-                d.out2_buf >= 0 || d.cout != c.cout || (d.cin & 63) || !(c.cin == d.cin || c.cin == 2 * d.cin) || net->kc_skip[i])
-                continue;
-            // the shortcut map has no other reader while it holds this tensor; its input and the consumer's input stay
-            // untouched from the shortcut op to the consumer, and the consumer does not write over the shortcut's input
-            bool ok = c.out_buf != d.in_buf && c.in_buf != d.in_buf;
-            for (size_t q = (size_t)i + 1; q < n_ops && ok; ++q) {
-                const frp_conv_op& o = net->ops[q];
-                if (q != j && (o.in_buf == c.res_buf || o.res_buf == c.res_buf)) ok = false;     // another reader
-                if (q < j && (o.out_buf == d.in_buf || o.out2_buf == d.in_buf)) ok = false;       // shortcut input rewritten early
-                if (o.out_buf == c.res_buf || o.out2_buf == c.res_buf) break;                     // the buffer moves on to another tensor
-            }
-            if (!ok) continue;
-            if (net == &h->det) { for (int l = 0; l < 3; ++l) ok &= (int)hd.det_head_buf[l] != c.res_buf; }   // (read by the decode kernel)
-            else ok &= (int)hd.emb_out_buf != c.res_buf;
-            if (!ok) continue;
-            if (expanded.empty()) expanded.assign(data, data + hd.data_bytes);
-            const size_t k1 = (size_t)9 * c.cin, k2 = (size_t)d.cin, kt = k1 + k2;
-            const size_t wdst = (expanded.size() + 255) / 256 * 256;
-            expanded.resize(wdst + (size_t)c.cout * kt * 2);
-            const size_t bdst = (expanded.size() + 255) / 256 * 256;
-            expanded.resize(bdst + (size_t)c.cout * 4);
-            for (int r = 0; r < c.cout; ++r) {
-                memcpy(expanded.data() + wdst + ((size_t)r * kt) * 2, expanded.data() + c.w_off + (size_t)r * k1 * 2, k1 * 2);
-                memcpy(expanded.data() + wdst + ((size_t)r * kt + k1) * 2, expanded.data() + d.w_off + (size_t)r * k2 * 2, k2 * 2);
-                float b1, b2;
-                memcpy(&b1, expanded.data() + c.bias_off + (size_t)r * 4, 4);
-                memcpy(&b2, expanded.data() + d.bias_off + (size_t)r * 4, 4);
-                const float bs = b1 + b2;
-                memcpy(expanded.data() + bdst + (size_t)r * 4, &bs, 4);
-            }
-            net->kc_skip[i] = 1;
-            net->kc_src[j] = i;
-            net->kc_w_off[j] = (int64_t)wdst;
-            net->kc_bias_off[j] = (int64_t)bdst;
-            data = expanded.data();
-            data_bytes = expanded.size();
-        }
-    }
-    FRPCHK(ensure(h, h->wdata, data_bytes));
-    HIPCHK(h, hipMemcpyAsync(h->wdata.p, data, data_bytes, hipMemcpyHostToDevice, h->stream));
+    std::vector<unsigned char> image;     // the device weight image: the data section + the load-time rewrites (net_program.cpp)
+    FRPCHK(load_program(h, hd, (const unsigned char*)blob, bytes, read_switches(), image));
+    FRPCHK(ensure(h, h->wdata, image.size()));
+    HIPCHK(h, hipMemcpyAsync(h->wdata.p, image.data(), image.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->hdr = hd;
     h->have_weights = true;
@@ -2227,7 +1416,7 @@ int frp_debug_det_prefix(frp_handle* h, int32_t n_ops, void* out_f16, int64_t ou
     if (n_ops <= 0 || n_ops > (int)h->det.ops.size()) return fail(h, FRP_ERR_INVALID, "op count out of range");
     const int B = h->rB, Hc = h->canvas_h, Wc = h->canvas_w;
     const Switches sw = read_switches();
-    const bool fused = stem_fusable(h->det) && !sw.no_fused_stem;
+    const bool fused = h->det.det_stem && !sw.no_fused_stem;
     if (!fused) return fail(h, FRP_ERR_INVALID, "prefix runs need the fused stem");
     FRPCHK(plan_net(h, h->det, B, Hc, Wc, fused));
     StemParams sp{};

@@ -1,0 +1,133 @@
+// The engine handle and the helpers every host translation unit uses on it (host only: the kernels' shared header is frp_internal.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "frp.h"
+#include "frp_blob.h"
+#include "frp_internal.h"
+#include "net_program.h"
+
+enum { EV_START = 0, EV_H2D, EV_PRE, EV_DET, EV_DEC, EV_ALIGN, EV_EMB, EV_L2, EV_MATCH, EV_D2H, EV_COUNT };
+
+struct frp_handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    std::string err;
+    frp_config cfg{};
+    // weights
+    bool have_weights = false;
+    frp_blob_header hdr{};
+    frp::DevBuf wdata;
+    frp::Net det, emb;
+    // resident frames (tightly packed u8 [B,H,W,3])
+    frp::DevBuf frames;
+    int rB = 0, rH = 0, rW = 0;
+    int n_cu = 256;                   // compute units of the device (queried once at create)
+    // overlapped ingest: the NEXT batch is copied on its own stream while the current one is processed
+    frp::DevBuf frames_next;
+    int nB = 0, nH = 0, nW = 0;
+    bool next_valid = false;
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_next_ready = nullptr, ev_next_free = nullptr;
+    std::vector<void*> pinned;       // frp_host_alloc blocks, freed with the handle
+    // detector source: the resident frames, or a resized copy of them (pyramid scales)
+    frp::DevBuf scaled;
+    int dH = 0, dW = 0;              // dims of the detector source
+    bool det_scaled = false;
+    int canvas_h = 0, canvas_w = 0;
+    int det_op_limit = -1;           // >= 0: frp_debug_det_prefix - the detector program stops behind this many ops
+    // captured passes (run_net): graphs, the keys seen once (a pass is captured the SECOND time it is asked for: the first allocates and
+    // sets kernel attributes), the keys whose capture failed, the allocation epoch
+    std::vector<frp::NetGraph> graphs;
+    std::vector<std::string> graph_seen, graph_bad;
+    uint64_t alloc_epoch = 1;
+    int64_t graph_replays = 0;
+    // multi-GPU (frp_dist_init): this handle's RCCL communicator, rank and world size
+    void* comm = nullptr;
+    int dist_rank = 0, dist_world = 0;
+    frp::DevBuf det_hashes;               // frp_debug_det_hashes: one 64-bit hash per detector op, taken right behind the op
+    bool det_hash_on = false;
+    // per-call results (device)
+    frp::DevBuf boxes, kps, scores, counts, anchor, face_slot, nfaces, q16, part_cos, part_idx, best_cos, best_idx, scratch, splitk_ws, dense_logits;
+    int last_B = 0, last_K = 0, last_nfaces = 0;   // last_nfaces -1: count still on the device (resolve_count)
+    int last_cap = 0, pend_cap = 0;
+    double pend_flops = 0.0, pend_f8flops = 0.0;
+    bool ev_pending = false;   // frp_process_resident's stage events are recorded but not yet read (see settle_events)
+    bool last_matched = false;
+    int32_t* h_nfaces = nullptr;   // pinned
+    unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
+    size_t pin_cap = 0;
+    // gallery snapshot
+    frp::DevBuf gallery;
+    int64_t g_rows = 0;
+    frp::DevBuf g_reserved;               // frp_gallery_reserve: filled by the caller, swapped in by frp_gallery_commit
+    // JPEG ingest (frp_upload_jpeg_async): page-locked coefficient staging, device coefficients / tables / sample planes
+    // (two staging buffers in turn: the host decodes batch t+1 while the copy of batch t still reads the other one)
+    void* jpeg_pin[2] = {nullptr, nullptr};
+    size_t jpeg_pin_cap[2] = {0, 0};
+    int jpeg_turn = 0;
+    frp::DevBuf jpeg_coef, jpeg_planes;
+    int64_t ctr_jpeg_device_batches = 0;   // batches whose entropy decode ran on the device (frp_debug_jpeg_device_batches)
+    frp::DevBuf jpeg_scan, jpeg_err;      // device entropy decode (restart-interval streams): compressed scans + interval offsets + tables; per-image error flags
+    hipEvent_t ev_jpeg_h2d[2] = {nullptr, nullptr};     // the copy out of jpeg_pin[i] has finished
+    bool jpeg_h2d_pending[2] = {false, false};
+    // exact compat rows (frp_gallery_exact): float64 [g_rows x 512] as enrolled, next to the unit fp16 snapshot
+    bool g_exact = false;
+    frp::DevBuf gx, gx_q, gx_out;
+    // profiling
+    hipEvent_t ev[EV_COUNT]{};
+    frp_counters ctr{};
+};
+
+namespace frp {
+
+inline int fail(frp_handle* h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    return code;
+}
+
+#define HIPCHK(h, expr)                                                                              \
+    do {                                                                                             \
+        hipError_t _e = (expr);                                                                      \
+        if (_e != hipSuccess)                                                                        \
+            return fail(h, FRP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));          \
+    } while (0)
+
+#define FRPCHK(expr)                 \
+    do {                             \
+        int _r = (expr);             \
+        if (_r != FRP_OK) return _r; \
+    } while (0)
+
+inline int ensure(frp_handle* h, DevBuf& b, size_t bytes) {
+    if (bytes <= b.cap && b.p) return FRP_OK;
+    if (b.p) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
+    }
+    const size_t want = std::max<size_t>(bytes, 256);
+    ++h->alloc_epoch;                   // (captured passes hold device pointers)
+    hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        return fail(h, FRP_ERR_OOM, std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
+    }
+    b.cap = want;
+    return FRP_OK;
+}
+
+inline void release(DevBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+}  // namespace frp

@@ -72,7 +72,7 @@ struct ConvParams {
     int Hr, Wr;             // residual spatial dims (RES_UP2)
     int ksplit;             // >1: split-K, `out` = fp32 workspace [ksplit][M][Cout] of raw partial sums;
                             // -1 (only with n_dev): the kernel picks conv_pick_ksplit(M) itself
-    const _Float16* wino_w; // null, or the Winograd weight image of this layer (conv3x3_wino.hip; built by frp_api.cpp:build_wino_image):
+    const _Float16* wino_w; // null, or the Winograd weight image of this layer (conv3x3_wino.hip; built by net_program.cpp:build_wino_image):
                             // launch_conv() takes the Winograd kernel when the shape is eligible
     const int32_t* n_dev;   // null, or the number of images that really exist (<= N) in device memory: the kernel derives
                             // M and its tile count from it (threshold mode: the face count never visits the host mid-pipeline)

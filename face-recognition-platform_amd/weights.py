@@ -171,7 +171,7 @@ def assign_buffers(layers: List[ns.ConvLayer], pinned: List[str]) -> Tuple[Dict[
         last_use[l.src] = i
         if l.res:
             last_use[l.res] = i
-            # K-concat (csrc/frp_api.cpp: frp_load_weights): the runtime folds a block's 1x1 strided shortcut conv into the
+            # K-concat (csrc/net_program.cpp: plan_kconcat): the runtime folds a block's 1x1 strided shortcut conv into the
             # 3x3 conv that adds it, which then reads the shortcut's INPUT - that tensor stays alive (and out of this
             # conv's output buffer) until here
             sc = producer.get(l.res)

@@ -505,7 +505,7 @@ def test_headline_step_is_bit_reproducible(fresh_engine):
 
 def test_network_passes_replayed_from_captured_graphs_give_the_same_bits_and_counters(fresh_engine):
     """A detector / embedder pass asked for a second time with the same shapes, buffers and switches is captured as a hipGraph and from
-    then on replayed by one call (frp_api.cpp: run_net).  Forced-K and threshold mode (device-side face count): the first call (launch
+    then on replayed by one call (net_program.cpp: run_net).  Forced-K and threshold mode (device-side face count): the first call (launch
     by launch), the capturing call and four replays return the same bits and charge the same counters; replays are counted; a weight
     reload and a changed batch size retire the stale graphs (results then equal a fresh handle's first, uncaptured call)."""
     from frp_amd import native

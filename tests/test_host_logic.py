@@ -334,7 +334,7 @@ def test_blob_layout_and_buffer_liveness():
 
 
 def test_buffer_plan_keeps_the_block_input_for_the_k_concat_consumer():
-    """K-concat (csrc/frp_api.cpp: frp_load_weights folds a strided block's 1x1 shortcut conv into the 3x3 conv that adds
+    """K-concat (csrc/net_program.cpp: plan_kconcat folds a strided block's 1x1 shortcut conv into the 3x3 conv that adds
     it): the fused conv reads the shortcut's INPUT, so the packer must keep that tensor alive until then and must not hand
     its buffer to the conv's output - the runtime refuses the fusion otherwise (and the four launches stay separate)."""
     for blocks in ((1, 1, 1, 1), (3, 13, 30, 3)):

@@ -45,7 +45,7 @@ def main():
     det = walk(ns.detector_layers(), 1088, 1920, "det.in", frames)
     emb = walk(ns.iresnet_layers(), 112, 112, "emb.in", faces)
     if not os.environ.get("FRP_NO_KCONCAT"):
-        # K-concat (csrc/frp_api.cpp: frp_load_weights): a strided block's 1x1 shortcut conv is not a launch of its own - it
+        # K-concat (csrc/net_program.cpp: plan_kconcat): a strided block's 1x1 shortcut conv is not a launch of its own - it
         # rides in the k-loop of the block's 3x3 stride-2 conv, which then reads the block input at every second pixel
         # instead of the shortcut map: FLOPs and bytes of the pair are charged to that launch
         fused, pend = [], None

@@ -1,9 +1,8 @@
-// C-ABI host runtime of libfrp.so: handle, weight/program blob, gallery snapshots, the
-// detect -> align -> embed -> match pipeline on one HIP stream, per-stage HIP-event timing.
+// C-ABI host runtime of libfrp.so: handle, weight/program blob, the detect -> align -> embed -> match
+// pipeline on one HIP stream, per-stage HIP-event timing.  The gallery snapshots and the multi-GPU
+// all-gather: gallery_api.cpp; the stand-alone kernel entry points and the lab hooks: kernel_api.cpp.
 // Interface and the reference call sites each entry point replaces: include/frp.h.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>   // types only: the library opens librccl at first use (frp_dist_*)
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <cmath>
@@ -17,9 +16,6 @@
 #include <atomic>
 
 #include "frp.h"
-#ifdef FRP_LAB
-#include "frp_lab.h"
-#endif
 #include "frp_blob.h"
 #include "frp_internal.h"
 #include "frp_handle.h"
@@ -51,35 +47,6 @@ const ProcessSwitches& frp::process_switches() {
 }
 
 namespace {
-
-// librccl, opened at first use (frp_dist_*: the gallery all-gather; a process that never goes multi-GPU does not load it)
-struct Rccl {
-    void* lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    std::string err;
-};
-Rccl& rccl() {
-    static Rccl r;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            r.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (r.lib) break;
-        }
-        if (!r.lib) { r.err = std::string("librccl not found: ") + (dlerror() ? dlerror() : "?"); return; }
-        r.GetUniqueId = (decltype(r.GetUniqueId))dlsym(r.lib, "ncclGetUniqueId");
-        r.CommInitRank = (decltype(r.CommInitRank))dlsym(r.lib, "ncclCommInitRank");
-        r.CommDestroy = (decltype(r.CommDestroy))dlsym(r.lib, "ncclCommDestroy");
-        r.AllGather = (decltype(r.AllGather))dlsym(r.lib, "ncclAllGather");
-        r.GetErrorString = (decltype(r.GetErrorString))dlsym(r.lib, "ncclGetErrorString");
-        if (!r.GetUniqueId || !r.CommInitRank || !r.CommDestroy || !r.AllGather || !r.GetErrorString) r.err = "librccl lacks an expected symbol";
-    });
-    return r;
-}
 
 float logit_threshold(float t) {
     if (!(t > 0.f)) return -INFINITY;
@@ -385,17 +352,6 @@ void accumulate_face_events(frp_handle* h) {
     h->ctr.ms_total += el(EV_DEC, EV_MATCH);
 }
 
-// frp_process_resident returns without waiting for the device also when the stage timers are on: its events are read
-// by whichever entry point next waits for the stream anyway (frp_fetch_results, frp_synchronize), or - with a wait of
-// their own - by the first other call on the handle, before it could re-record them.  (Reading them inside
-// frp_process_resident cost a full stream drain per step: 0.8 ms of a 15 ms step in bench.py's fetch-every-step loop.)
-void settle_events(frp_handle* h, bool stream_is_idle) {
-    if (!h->ev_pending) return;
-    h->ev_pending = false;
-    if (!stream_is_idle && hipStreamSynchronize(h->stream) != hipSuccess) return;
-    accumulate_events(h, false);
-}
-
 // page-locked staging for the result fetch, grown on demand.  Device -> PAGEABLE host copies go through the runtime's own
 // bounce buffers with whole-device synchronisation semantics: next to torch / RCCL in the process they serialised the
 // copy stream's upload of the next batch behind the fetch (the overlapped loop lost its overlap: 20 vs 14.7 ms per
@@ -474,74 +430,18 @@ int fetch_results(frp_handle* h, float* boxes, float* kps, float* scores, int32_
     return FRP_OK;
 }
 
-int to_f32(frp_handle* h, const void* src, size_t count, int dtype, std::vector<float>& out) {
-    out.resize(count);
-    if (dtype == FRP_F32) {
-        memcpy(out.data(), src, count * 4);
-    } else if (dtype == FRP_F64) {
-        const double* d = (const double*)src;
-        for (size_t i = 0; i < count; ++i) out[i] = (float)d[i];
-    } else if (dtype == FRP_F16) {
-        const _Float16* d = (const _Float16*)src;
-        for (size_t i = 0; i < count; ++i) out[i] = (float)d[i];
-    } else {
-        return fail(h, FRP_ERR_INVALID, "unknown dtype");
-    }
-    return FRP_OK;
-}
-
-// host fp32 rows -> unit fp16 rows at dst (device), via the scratch buffer
-int upload_rows_normalized(frp_handle* h, const float* rows, int64_t n, _Float16* dst) {
-    if (n <= 0) return FRP_OK;
-    const int64_t chunk = 1 << 16;
-    FRPCHK(ensure(h, h->scratch, (size_t)std::min(n, chunk) * FRP_EMB_DIM * 4));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int64_t m = std::min(chunk, n - r0);
-        HIPCHK(h, hipMemcpyAsync(h->scratch.p, rows + r0 * FRP_EMB_DIM, (size_t)m * FRP_EMB_DIM * 4, hipMemcpyHostToDevice, h->stream));
-        hipError_t e = launch_gallery_normalize((const float*)h->scratch.p, dst + r0 * FRP_EMB_DIM, m, FRP_EMB_DIM, h->stream);
-        if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("gallery_normalize: ") + hipGetErrorString(e));
-        HIPCHK(h, hipStreamSynchronize(h->stream));   // scratch is reused by the next chunk
-    }
-    return FRP_OK;
-}
-
-// exact compat rows: `n` host rows of `d` = 512 values of `dtype` -> float64 at dst (device row pointer)
-int upload_rows_exact(frp_handle* h, const void* emb, int64_t n, int dtype, double* dst) {
-    if (n <= 0) return FRP_OK;
-    const size_t cnt = (size_t)n * FRP_EMB_DIM;
-    std::vector<double> tmp;
-    const double* src = (const double*)emb;
-    if (dtype != FRP_F64) {
-        tmp.resize(cnt);
-        if (dtype == FRP_F32) { const float* f = (const float*)emb; for (size_t i = 0; i < cnt; ++i) tmp[i] = (double)f[i]; }
-        else if (dtype == FRP_F16) { const uint16_t* u = (const uint16_t*)emb; for (size_t i = 0; i < cnt; ++i) tmp[i] = (double)f16_bits_to_f32(u[i]); }
-        else return fail(h, FRP_ERR_INVALID, "bad dtype");
-        src = tmp.data();
-    }
-    HIPCHK(h, hipMemcpyAsync(dst, src, cnt * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));      // (tmp / the caller's rows go away)
-    return FRP_OK;
-}
-
-// a fresh exact matrix of `n` rows widened from unit fp16 device rows (rows installed from device data, or that existed before)
-int exact_from_f16(frp_handle* h, const void* dev_f16, int64_t n, DevBuf& fresh) {
-    if (n <= 0) return FRP_OK;
-    FRPCHK(ensure(h, fresh, (size_t)n * FRP_EMB_DIM * 8));
-    hipError_t e = launch_gallery_widen((const _Float16*)dev_f16, (double*)fresh.p, n, FRP_EMB_DIM, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { release(fresh); return fail(h, FRP_ERR_HIP, std::string("gallery_widen: ") + hipGetErrorString(e)); }
-    return FRP_OK;
-}
-
-struct Guard {
-    std::lock_guard<std::mutex> lk;
-    explicit Guard(frp_handle* h, bool settle = true) : lk(h->mu) {
-        (void)hipSetDevice(h->device);
-        if (settle) settle_events(h, false);
-    }
-};
-
 }  // namespace
+
+// frp_process_resident returns without waiting for the device also when the stage timers are on: its events are read
+// by whichever entry point next waits for the stream anyway (frp_fetch_results, frp_synchronize), or - with a wait of
+// their own - by the first other call on the handle, before it could re-record them.  (Reading them inside
+// frp_process_resident cost a full stream drain per step: 0.8 ms of a 15 ms step in bench.py's fetch-every-step loop.)
+void frp::settle_events(frp_handle* h, bool stream_is_idle) {
+    if (!h->ev_pending) return;
+    h->ev_pending = false;
+    if (!stream_is_idle && hipStreamSynchronize(h->stream) != hipSuccess) return;
+    accumulate_events(h, false);
+}
 
 extern "C" {
 
@@ -596,7 +496,7 @@ void frp_destroy(frp_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-    if (h->comm) { (void)rccl().CommDestroy((ncclComm_t)h->comm); h->comm = nullptr; }
+    dist_shutdown(h);
     drop_graphs(h);
     for (DevBuf& b : h->det.bufs) release(b);
     for (DevBuf& b : h->emb.bufs) release(b);
@@ -641,316 +541,6 @@ int frp_load_weights(frp_handle* h, const void* blob, size_t bytes) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->hdr = hd;
     h->have_weights = true;
-    return FRP_OK;
-}
-
-// ---------------------------------------------------------------- gallery
-int frp_gallery_set(frp_handle* h, const void* emb, int64_t n, int32_t d, int32_t dtype) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (h->g_reserved.p) return fail(h, FRP_ERR_INVALID, "a gallery reservation is pending: commit or cancel it first (frp_gallery_commit / frp_gallery_cancel)");
-    if (n < 0 || (n > 0 && !emb) || d != FRP_EMB_DIM) return fail(h, FRP_ERR_INVALID, "gallery must be [n x 512]");
-    DevBuf fresh, fresh_x;   // new snapshot(s), swapped in when complete
-    if (n > 0) {
-        std::vector<float> f;
-        const float* rows = (const float*)emb;
-        if (dtype != FRP_F32) { FRPCHK(to_f32(h, emb, (size_t)n * d, dtype, f)); rows = f.data(); }
-        FRPCHK(ensure(h, fresh, (size_t)n * d * 2));
-        int r = upload_rows_normalized(h, rows, n, (_Float16*)fresh.p);
-        if (r == FRP_OK && h->g_exact) {
-            r = ensure(h, fresh_x, (size_t)n * d * 8);
-            if (r == FRP_OK) r = upload_rows_exact(h, emb, n, dtype, (double*)fresh_x.p);
-        }
-        if (r != FRP_OK) { release(fresh); release(fresh_x); return r; }
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    release(h->gallery);
-    h->gallery = fresh;
-    release(h->gx);
-    h->gx = fresh_x;
-    h->g_rows = n;
-    return FRP_OK;
-}
-
-int frp_gallery_set_device(frp_handle* h, const void* dev_f16, int64_t n, int32_t d) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (h->g_reserved.p) return fail(h, FRP_ERR_INVALID, "a gallery reservation is pending: commit or cancel it first (frp_gallery_commit / frp_gallery_cancel)");
-    if (n <= 0 || !dev_f16 || d != FRP_EMB_DIM) return fail(h, FRP_ERR_INVALID, "gallery must be [n x 512] fp16 on the device");
-    DevBuf fresh;
-    FRPCHK(ensure(h, fresh, (size_t)n * d * 2));
-    hipError_t e = hipMemcpyAsync(fresh.p, dev_f16, (size_t)n * d * 2, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { release(fresh); return fail(h, FRP_ERR_HIP, std::string("gallery copy: ") + hipGetErrorString(e)); }
-    DevBuf fresh_x;
-    if (h->g_exact) { int r = exact_from_f16(h, fresh.p, n, fresh_x); if (r != FRP_OK) { release(fresh); return r; } }
-    release(h->gallery);
-    h->gallery = fresh;
-    release(h->gx);
-    h->gx = fresh_x;
-    h->g_rows = n;
-    return FRP_OK;
-}
-
-int frp_gallery_reserve(frp_handle* h, int64_t capacity_rows, void** dev_f16) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!dev_f16 || capacity_rows <= 0 || capacity_rows > 0x7fffff00L) return fail(h, FRP_ERR_INVALID, "bad gallery reservation");
-    release(h->g_reserved);
-    FRPCHK(ensure(h, h->g_reserved, (size_t)capacity_rows * FRP_EMB_DIM * 2));
-    *dev_f16 = h->g_reserved.p;
-    return FRP_OK;
-}
-
-int frp_gallery_cancel(frp_handle* h) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (h->g_reserved.p) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        release(h->g_reserved);
-    }
-    return FRP_OK;
-}
-
-int frp_gallery_commit(frp_handle* h, int64_t n_rows) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!h->g_reserved.p || n_rows < 0 || (size_t)n_rows * FRP_EMB_DIM * 2 > h->g_reserved.cap)
-        return fail(h, FRP_ERR_INVALID, "gallery commit without a matching reservation");
-    HIPCHK(h, hipStreamSynchronize(h->stream));      // nothing of this handle still reads the old snapshot
-    DevBuf fresh_x;
-    if (h->g_exact) FRPCHK(exact_from_f16(h, h->g_reserved.p, n_rows, fresh_x));
-    release(h->gallery);
-    h->gallery = h->g_reserved;
-    h->g_reserved = DevBuf();
-    release(h->gx);
-    h->gx = fresh_x;
-    h->g_rows = n_rows;
-    return FRP_OK;
-}
-
-// ---------------------------------------------------------------- multi-GPU: the one collective of the path, on RCCL
-// frames are sharded one stream per GPU and need no exchange; the watch list is the exception - every rank decrypts /
-// builds N / R rows and the full unit fp16 matrix is all-gathered over xGMI at load and on updates (the reference holds ENCODINGS
-// once, in its one process: backend/app/state.py:78).  The library owns that collective: librccl is opened at first use (dlopen - a
-// process that never goes multi-GPU does not load it), the communicator lives in the handle, and the gather lands STRAIGHT in a
-// reserved snapshot (shard r at row offset r * ceil(N / R): no compaction copy) that is then committed like any other gallery.
-// The caller's launcher (torch.distributed.run, MPI, a shell loop) only has to carry the 128-byte unique id from rank 0 to the others.
-static_assert(sizeof(ncclUniqueId) == FRP_DIST_ID_BYTES, "include/frp.h: FRP_DIST_ID_BYTES");
-
-int frp_dist_unique_id(void* id128) {
-    if (!id128) return FRP_ERR_INVALID;
-    Rccl& r = rccl();
-    if (!r.err.empty()) return FRP_ERR_HIP;
-    ncclUniqueId id;
-    if (r.GetUniqueId(&id) != ncclSuccess) return FRP_ERR_HIP;
-    memcpy(id128, &id, sizeof(id));
-    return FRP_OK;
-}
-
-int frp_dist_init(frp_handle* h, const void* id128, int32_t rank, int32_t world) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!id128 || world <= 0 || rank < 0 || rank >= world) return fail(h, FRP_ERR_INVALID, "bad rank / world size");
-    if (h->comm) return fail(h, FRP_ERR_INVALID, "this handle already has a communicator (frp_dist_destroy first)");
-    Rccl& r = rccl();
-    if (!r.err.empty()) return fail(h, FRP_ERR_HIP, r.err);
-    ncclUniqueId id;
-    memcpy(&id, id128, sizeof(id));
-    ncclComm_t c = nullptr;
-    const ncclResult_t e = r.CommInitRank(&c, world, id, rank);          // collective over the ranks (the guard has set this handle's device)
-    if (e != ncclSuccess) return fail(h, FRP_ERR_HIP, std::string("ncclCommInitRank: ") + r.GetErrorString(e));
-    h->comm = c;
-    h->dist_rank = rank;
-    h->dist_world = world;
-    return FRP_OK;
-}
-
-int frp_dist_destroy(frp_handle* h) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (h->comm) {
-        (void)hipStreamSynchronize(h->stream);
-        (void)rccl().CommDestroy((ncclComm_t)h->comm);
-        h->comm = nullptr;
-        h->dist_world = 0;
-    }
-    return FRP_OK;
-}
-
-int frp_gallery_allgather(frp_handle* h, const void* shard, int64_t shard_rows, int32_t dtype, int64_t n_total) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!h->comm) return fail(h, FRP_ERR_INVALID, "no communicator (frp_dist_init)");
-    if (h->g_reserved.p) return fail(h, FRP_ERR_INVALID, "a gallery reservation is pending: commit or cancel it first");
-    const int world = h->dist_world, rank = h->dist_rank;
-    if (n_total <= 0 || n_total > 0x7fffff00L || shard_rows < 0 || (shard_rows > 0 && !shard)) return fail(h, FRP_ERR_INVALID, "bad shard");
-    const int64_t block = (n_total + world - 1) / world;
-    const int64_t first = std::min<int64_t>((int64_t)rank * block, n_total), mine = std::min<int64_t>(block, n_total - first);
-    if (shard_rows != mine) return fail(h, FRP_ERR_INVALID, "this rank owns rows [rank * ceil(N / R), ...): shard has another row count");
-    Rccl& r = rccl();
-    // this rank's rows, unit fp16, padded with zero rows to the block size (the last ranks' shards may be short or empty)
-    DevBuf send;
-    FRPCHK(ensure(h, send, (size_t)block * FRP_EMB_DIM * 2));
-    int rc = FRP_OK;
-    hipError_t he = hipMemsetAsync(send.p, 0, (size_t)block * FRP_EMB_DIM * 2, h->stream);
-    if (he != hipSuccess) rc = fail(h, FRP_ERR_HIP, std::string("memset: ") + hipGetErrorString(he));
-    if (rc == FRP_OK && mine > 0) {
-        std::vector<float> f;
-        const float* rows = (const float*)shard;
-        if (dtype != FRP_F32) { rc = to_f32(h, shard, (size_t)mine * FRP_EMB_DIM, dtype, f); rows = f.data(); }
-        if (rc == FRP_OK) rc = upload_rows_normalized(h, rows, mine, (_Float16*)send.p);
-    }
-    if (rc == FRP_OK) rc = ensure(h, h->g_reserved, (size_t)world * block * FRP_EMB_DIM * 2);
-    if (rc == FRP_OK) {
-        const ncclResult_t e = r.AllGather(send.p, h->g_reserved.p, (size_t)block * FRP_EMB_DIM, ncclFloat16, (ncclComm_t)h->comm, h->stream);
-        if (e != ncclSuccess) rc = fail(h, FRP_ERR_HIP, std::string("ncclAllGather: ") + r.GetErrorString(e));
-    }
-    if (rc == FRP_OK) {
-        he = hipStreamSynchronize(h->stream);
-        if (he != hipSuccess) rc = fail(h, FRP_ERR_HIP, std::string("all-gather: ") + hipGetErrorString(he));
-    }
-    release(send);
-    if (rc != FRP_OK) { release(h->g_reserved); return rc; }
-    // commit (as frp_gallery_commit): rows [0, n_total) of the gathered blocks ARE the gallery
-    DevBuf fresh_x;
-    if (h->g_exact) {
-        rc = exact_from_f16(h, h->g_reserved.p, n_total, fresh_x);
-        if (rc != FRP_OK) { release(h->g_reserved); return rc; }
-    }
-    release(h->gallery);
-    h->gallery = h->g_reserved;
-    h->g_reserved = DevBuf();
-    release(h->gx);
-    h->gx = fresh_x;
-    h->g_rows = n_total;
-    return FRP_OK;
-}
-
-const void* frp_gallery_device_ptr(frp_handle* h) {
-    if (!h) return nullptr;
-    Guard g(h);
-    return h->g_rows > 0 ? h->gallery.p : nullptr;
-}
-
-int frp_gallery_update_row(frp_handle* h, int64_t row, const void* emb, int32_t d, int32_t dtype) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (h->g_reserved.p) return fail(h, FRP_ERR_INVALID, "a gallery reservation is pending: commit or cancel it first (frp_gallery_commit / frp_gallery_cancel)");
-    if (!emb || d != FRP_EMB_DIM || row < 0 || row > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery row");
-    std::vector<float> f;
-    FRPCHK(to_f32(h, emb, (size_t)d, dtype, f));
-    if (row == h->g_rows && (size_t)(h->g_rows + 1) * d * 2 > h->gallery.cap) {
-        // grow: new snapshot with doubled capacity
-        DevBuf fresh;
-        const size_t cap_rows = std::max<int64_t>(1024, h->g_rows * 2);
-        FRPCHK(ensure(h, fresh, cap_rows * d * 2));
-        if (h->g_rows > 0) {
-            hipError_t e = hipMemcpyAsync(fresh.p, h->gallery.p, (size_t)h->g_rows * d * 2, hipMemcpyDeviceToDevice, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) { release(fresh); return fail(h, FRP_ERR_HIP, std::string("gallery grow: ") + hipGetErrorString(e)); }
-        }
-        release(h->gallery);
-        h->gallery = fresh;
-    }
-    if (h->g_exact && (size_t)(row + 1) * d * 8 > h->gx.cap) {        // the exact copy grows with the snapshot's row capacity
-        DevBuf fresh;
-        const size_t cap_rows = std::max<size_t>(h->gallery.cap / ((size_t)d * 2), (size_t)row + 1);
-        FRPCHK(ensure(h, fresh, cap_rows * d * 8));
-        if (h->g_rows > 0) {
-            hipError_t e = hipMemcpyAsync(fresh.p, h->gx.p, (size_t)h->g_rows * d * 8, hipMemcpyDeviceToDevice, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) { release(fresh); return fail(h, FRP_ERR_HIP, std::string("exact gallery grow: ") + hipGetErrorString(e)); }
-        }
-        release(h->gx);
-        h->gx = fresh;
-    }
-    FRPCHK(upload_rows_normalized(h, f.data(), 1, (_Float16*)h->gallery.p + row * d));
-    if (h->g_exact) FRPCHK(upload_rows_exact(h, emb, 1, dtype, (double*)h->gx.p + row * d));
-    if (row == h->g_rows) h->g_rows += 1;
-    return FRP_OK;
-}
-
-int frp_gallery_remove_row(frp_handle* h, int64_t row) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (h->g_reserved.p) return fail(h, FRP_ERR_INVALID, "a gallery reservation is pending: commit or cancel it first (frp_gallery_commit / frp_gallery_cancel)");
-    if (row < 0 || row >= h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery row");
-    const int64_t last = h->g_rows - 1;
-    if (row != last) {
-        HIPCHK(h, hipMemcpyAsync((_Float16*)h->gallery.p + row * FRP_EMB_DIM, (_Float16*)h->gallery.p + last * FRP_EMB_DIM,
-                                 FRP_EMB_DIM * 2, hipMemcpyDeviceToDevice, h->stream));
-        if (h->g_exact)
-            HIPCHK(h, hipMemcpyAsync((double*)h->gx.p + row * FRP_EMB_DIM, (double*)h->gx.p + last * FRP_EMB_DIM, FRP_EMB_DIM * 8,
-                                     hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->g_rows = last;
-    return FRP_OK;
-}
-
-int64_t frp_gallery_size(const frp_handle* h) { return h ? h->g_rows : -1; }
-
-int frp_gallery_get(frp_handle* h, void* out_f16, int64_t first_row, int64_t n_rows) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!out_f16 || first_row < 0 || n_rows < 0 || first_row + n_rows > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery range");
-    if (n_rows == 0) return FRP_OK;
-    HIPCHK(h, hipMemcpyAsync(out_f16, (_Float16*)h->gallery.p + first_row * FRP_EMB_DIM, (size_t)n_rows * FRP_EMB_DIM * 2,
-                             hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return FRP_OK;
-}
-
-int frp_gallery_exact(frp_handle* h, int32_t on) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!on) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        release(h->gx); release(h->gx_q); release(h->gx_out);
-        h->g_exact = false;
-        return FRP_OK;
-    }
-    if (h->g_exact) return FRP_OK;
-    DevBuf fresh;
-    if (h->g_rows > 0) {          // rows that exist already: the unit fp16 rows widened (their exact values are gone)
-        const size_t cap_rows = std::max<size_t>(h->gallery.cap / ((size_t)FRP_EMB_DIM * 2), (size_t)h->g_rows);
-        FRPCHK(ensure(h, fresh, cap_rows * FRP_EMB_DIM * 8));
-        hipError_t e = launch_gallery_widen((const _Float16*)h->gallery.p, (double*)fresh.p, h->g_rows, FRP_EMB_DIM, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { release(fresh); return fail(h, FRP_ERR_HIP, std::string("gallery_widen: ") + hipGetErrorString(e)); }
-    }
-    release(h->gx);
-    h->gx = fresh;
-    h->g_exact = true;
-    return FRP_OK;
-}
-
-int frp_gallery_distances(frp_handle* h, const double* q, int32_t M, double* dist, int64_t n_cols) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!h->g_exact) return fail(h, FRP_ERR_INVALID, "exact rows are not enabled (frp_gallery_exact)");
-    if (!q || !dist || M <= 0 || M > 65536) return fail(h, FRP_ERR_INVALID, "bad distance arguments");
-    if (n_cols != h->g_rows) return fail(h, FRP_ERR_INVALID, "gallery_distances: output sized for another gallery size");
-    if (h->g_rows == 0) return FRP_OK;
-    FRPCHK(ensure(h, h->gx_q, (size_t)M * FRP_EMB_DIM * 8));
-    FRPCHK(ensure(h, h->gx_out, (size_t)M * h->g_rows * 8));
-    HIPCHK(h, hipMemcpyAsync(h->gx_q.p, q, (size_t)M * FRP_EMB_DIM * 8, hipMemcpyHostToDevice, h->stream));
-    hipError_t e = launch_gallery_distances((const double*)h->gx.p, h->g_rows, (const double*)h->gx_q.p, M, (double*)h->gx_out.p, h->stream);
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("gallery_distances: ") + hipGetErrorString(e));
-    HIPCHK(h, hipMemcpyAsync(dist, h->gx_out.p, (size_t)M * h->g_rows * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return FRP_OK;
-}
-
-int frp_gallery_get_exact(frp_handle* h, double* out, int64_t first_row, int64_t n_rows) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!h->g_exact) return fail(h, FRP_ERR_INVALID, "exact rows are not enabled (frp_gallery_exact)");
-    if (!out || first_row < 0 || n_rows < 0 || first_row + n_rows > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery range");
-    if (n_rows == 0) return FRP_OK;
-    HIPCHK(h, hipMemcpyAsync(out, (double*)h->gx.p + first_row * FRP_EMB_DIM, (size_t)n_rows * FRP_EMB_DIM * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
     return FRP_OK;
 }
 
@@ -1454,7 +1044,7 @@ int frp_decode_heads(frp_handle* h, const void* head8, const void* head16, const
         max_faces <= 0 || max_faces > FRP_MAX_FACES_CAP)
         return fail(h, FRP_ERR_INVALID, "bad decode arguments");
     const void* src[3] = {head8, head16, head32};
-    DevBuf tmp[3];
+    ScopedBuf tmp[3];
     DecodeParams dp{};
     int rc = FRP_OK;
     for (int l = 0; l < 3 && rc == FRP_OK; ++l) {
@@ -1462,9 +1052,9 @@ int frp_decode_heads(frp_handle* h, const void* head8, const void* head16, const
         dp.wl[l] = canvas_w / (8 << l);
         const size_t bytes = (size_t)B * dp.hl[l] * dp.wl[l] * 32 * 2;
         rc = ensure(h, tmp[l], bytes);
-        if (rc == FRP_OK && hipMemcpyAsync(tmp[l].p, src[l], bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+        if (rc == FRP_OK && hipMemcpyAsync(tmp[l]->p, src[l], bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
             rc = fail(h, FRP_ERR_HIP, "head upload failed");
-        dp.head[l] = (const _Float16*)tmp[l].p;
+        dp.head[l] = (const _Float16*)tmp[l]->p;
     }
     if (rc == FRP_OK) rc = ensure_results(h, B, max_faces);
     if (rc == FRP_OK) {
@@ -1491,7 +1081,6 @@ int frp_decode_heads(frp_handle* h, const void* head8, const void* head16, const
         if (e == hipSuccess && anchor_idx) e = hipMemcpyAsync(anchor_idx, h->anchor.p, s * 4, hipMemcpyDeviceToHost, h->stream);
     }
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    for (int l = 0; l < 3; ++l) release(tmp[l]);
     if (rc != FRP_OK) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return fail(h, FRP_ERR_HIP, "decode result copy failed");
     return FRP_OK;
@@ -1569,18 +1158,17 @@ static int match_common(frp_handle* h, const float* q, int M, float* all_scores_
     FRPCHK(ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2));
     HIPCHK(h, hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream));
     FRPCHK(upload_rows_normalized(h, q, M, (_Float16*)h->q16.p));
-    DevBuf all;
+    ScopedBuf all;
     if (all_scores_host) FRPCHK(ensure(h, all, (size_t)M * h->g_rows * 4));
-    int rc = run_match(h, sw, M, (float*)all.p);
+    int rc = run_match(h, sw, M, (float*)all->p);
     hipError_t e = hipSuccess;
     if (rc == FRP_OK) {
         if (idx) e = hipMemcpyAsync(idx, h->best_idx.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess && cos) e = hipMemcpyAsync(cos, h->best_cos.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess && all_scores_host)
-            e = hipMemcpyAsync(all_scores_host, all.p, (size_t)M * h->g_rows * 4, hipMemcpyDeviceToHost, h->stream);
+            e = hipMemcpyAsync(all_scores_host, all->p, (size_t)M * h->g_rows * 4, hipMemcpyDeviceToHost, h->stream);
     }
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    release(all);
     if (rc != FRP_OK) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return fail(h, FRP_ERR_HIP, "match result copy failed");
     return FRP_OK;
@@ -1597,7 +1185,7 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
     const long N = h->g_rows;
     const Switches sw = read_switches();
     int chunk = (int)std::max<long>(1, std::min<long>(M, (1L << 28) / N));
-    DevBuf all, didx, dcos;
+    ScopedBuf all, didx, dcos;
     int rc = ensure(h, all, (size_t)chunk * N * 4);
     if (rc == FRP_OK) rc = ensure(h, didx, (size_t)chunk * topk * 4);
     if (rc == FRP_OK) rc = ensure(h, dcos, (size_t)chunk * topk * 4);
@@ -1610,15 +1198,14 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
         e = hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream);
         if (e != hipSuccess) break;
         rc = upload_rows_normalized(h, q + (size_t)m0 * FRP_EMB_DIM, m, (_Float16*)h->q16.p);
-        if (rc == FRP_OK) rc = run_match(h, sw, m, (float*)all.p);
+        if (rc == FRP_OK) rc = run_match(h, sw, m, (float*)all->p);
         if (rc != FRP_OK) break;
-        e = launch_topk_rows((const float*)all.p, m, N, topk, (int32_t*)didx.p, (float*)dcos.p, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(idx + (size_t)m0 * topk, didx.p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * topk, dcos.p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
+        e = launch_topk_rows((const float*)all->p, m, N, topk, (int32_t*)didx->p, (float*)dcos->p, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(idx + (size_t)m0 * topk, didx->p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * topk, dcos->p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
     (void)hipStreamSynchronize(h->stream);
-    release(all); release(didx); release(dcos);
     if (rc != FRP_OK) return rc;
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("match top-k: ") + hipGetErrorString(e));
     return FRP_OK;
@@ -1632,280 +1219,6 @@ int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, i
     if (n_cols != h->g_rows) return fail(h, FRP_ERR_INVALID, "match_scores: output sized for another gallery size");
     return match_common(h, q, M, cos_all, nullptr, nullptr);
 }
-
-namespace {
-// frp_conv2d_nhwc / frp_conv_bench `flags` (include/frp.h) -> the kernel A/B bits and the tile class of one conv launch
-void conv_route_from_abi_flags(int32_t flags, ConvParams& p) {
-    p.dbg = ((flags >> 8) & 0xff) | ((flags & (1 << 19)) ? CONV_DBG_WINO_2D : 0) | ((flags & (1 << 20)) ? CONV_DBG_NO_C64 : 0) |
-            ((flags & (1 << 21)) ? CONV_DBG_S2 : 0) | ((flags & (1 << 22)) ? CONV_DBG_C64_SAME_ORDER : 0) |
-            (process_switches().c64_all ? CONV_DBG_C64_ALL : 0);
-    p.small_m = (flags & (1 << 17)) ? 1 : (flags & ((1 << 18) | (1 << 16))) ? -1 : 0;     // (the Winograd kernel: never quarter tiles)
-}
-}  // namespace
-
-int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t W, int32_t Cin, const void* w, int32_t Cout,
-                    int32_t ksize, int32_t stride, const float* bias, const float* slope, const void* res, int32_t res_h,
-                    int32_t res_w, int32_t act, int32_t flags, void* out) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!x || !w || !bias || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !(ksize == 1 || ksize == 3) ||
-        !(stride == 1 || stride == 2))
-        return fail(h, FRP_ERR_INVALID, "bad conv arguments");
-    const int pad = ksize / 2;
-    const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-    const bool up2 = flags & FRP_FLAG_RES_UP2;
-    const size_t xb = (size_t)N * H * W * Cin * 2, wb = (size_t)Cout * ksize * ksize * Cin * 2;
-    const size_t bb = (size_t)Cout * 4 * ((flags & FRP_FLAG_BORDER_BIAS) ? 9 : 1);
-    const size_t ob = (size_t)N * Ho * Wo * Cout * ((flags & FRP_FLAG_OUT_F32) ? 4 : 2);
-    const size_t rb = res ? (size_t)N * (up2 ? res_h : Ho) * (up2 ? res_w : Wo) * Cout * 2 : 0;
-    DevBuf dx, dw, db, ds, dr, dout, dwino;
-    int rc = ensure(h, dx, xb);
-    if (rc == FRP_OK) rc = ensure(h, dw, wb);
-    if (rc == FRP_OK) rc = ensure(h, db, bb);
-    if (rc == FRP_OK) rc = ensure(h, dout, ob);
-    if (rc == FRP_OK && slope) rc = ensure(h, ds, (size_t)Cout * 4);
-    if (rc == FRP_OK && res) rc = ensure(h, dr, rb);
-    ConvParams p{};
-    conv_route_from_abi_flags(flags, p);
-    // flags bit 16: through the Winograd kernel (parity tests); an ineligible shape is an error, not a silent fallback
-    const bool want_wino = (flags & (1 << 16)) != 0;
-    std::vector<uint16_t> wimg;
-    if (want_wino) {
-        bool shape_ok = conv3x3_wino_shape_ok(W, Cin, ksize, stride) ||
-                        (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, res != nullptr));      // (2-D tiles: wide maps)
-#ifdef FRP_LAB
-        shape_ok = shape_ok || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
-#endif
-        if (!shape_ok || (flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2)))
-            return fail(h, FRP_ERR_INVALID, "shape not covered by the Winograd kernel");
-        wimg.resize(conv3x3_wino_image_bytes(Cin, Cout) / 2);
-        build_wino_image((const uint16_t*)w, Cin, Cout, wimg.data());
-        if (rc == FRP_OK) rc = ensure(h, dwino, wimg.size() * 2);
-    }
-    hipError_t e = hipSuccess;
-    if (rc == FRP_OK) {
-        e = hipMemcpyAsync(dx.p, x, xb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && want_wino) e = hipMemcpyAsync(dwino.p, wimg.data(), wimg.size() * 2, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dw.p, w, wb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(db.p, bias, bb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && slope) e = hipMemcpyAsync(ds.p, slope, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && res) e = hipMemcpyAsync(dr.p, res, rb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            p.x = (const _Float16*)dx.p; p.w = (const _Float16*)dw.p; p.bias = (const float*)db.p;
-            p.slope = slope ? (const float*)ds.p : nullptr;
-            p.res = res ? (const _Float16*)dr.p : nullptr;
-            p.out = dout.p;
-            p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ksize; p.stride = stride; p.act = act;
-            p.flags = flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2);
-            p.Hr = res_h; p.Wr = res_w;
-            if (want_wino) p.wino_w = (const _Float16*)dwino.p;
-            e = launch_conv(p, h->stream);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, h->stream);
-    }
-    hipError_t e2 = hipStreamSynchronize(h->stream);
-    DevBuf* all[] = {&dx, &dw, &db, &ds, &dr, &dout, &dwino};
-    for (DevBuf* b : all) release(*b);
-    if (rc != FRP_OK) return rc;
-    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("conv2d: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv2d sync: ") + hipGetErrorString(e2));
-    return FRP_OK;
-}
-
-int frp_conv2d_f8(frp_handle* h, const void* x8, int32_t N, int32_t H, int32_t W, int32_t Cin, const void* w8, int32_t Cout,
-                  const float* wscale, const float* bias, const float* slope, const void* res16, int32_t act, int32_t flags,
-                  float in_scale, float out_scale, void* out, void* out2_f8) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!x8 || !w8 || !wscale || !bias || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
-        return fail(h, FRP_ERR_INVALID, "bad conv arguments");
-    const bool out8 = (flags & FRP_FLAG_OUT_FP8) != 0;
-    const size_t xb = (size_t)N * H * W * Cin, wb = (size_t)Cout * 9 * Cin, on = (size_t)N * H * W * Cout;
-    const size_t bb = (size_t)Cout * 4 * ((flags & FRP_FLAG_BORDER_BIAS) ? 9 : 1);
-    DevBuf dx, dw, dws, db, ds, dr, dout, dout2;
-    int rc = ensure(h, dx, xb);
-    if (rc == FRP_OK) rc = ensure(h, dw, wb);
-    if (rc == FRP_OK) rc = ensure(h, dws, (size_t)Cout * 4);
-    if (rc == FRP_OK) rc = ensure(h, db, bb);
-    if (rc == FRP_OK) rc = ensure(h, dout, on * (out8 ? 1 : 2));
-    if (rc == FRP_OK && out2_f8) rc = ensure(h, dout2, on);
-    if (rc == FRP_OK && slope) rc = ensure(h, ds, (size_t)Cout * 4);
-    if (rc == FRP_OK && res16) rc = ensure(h, dr, on * 2);
-    hipError_t e = hipSuccess;
-    if (rc == FRP_OK) {
-        e = hipMemcpyAsync(dx.p, x8, xb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dw.p, w8, wb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dws.p, wscale, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(db.p, bias, bb, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && slope) e = hipMemcpyAsync(ds.p, slope, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess && res16) e = hipMemcpyAsync(dr.p, res16, on * 2, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            ConvParams p{};
-            p.x = (const _Float16*)dx.p; p.w = (const _Float16*)dw.p; p.bias = (const float*)db.p;
-            p.slope = slope ? (const float*)ds.p : nullptr;
-            p.res = res16 ? (const _Float16*)dr.p : nullptr;
-            p.out = dout.p;
-            p.out2 = out2_f8 ? dout2.p : nullptr;
-            p.wscale = (const float*)dws.p;
-            p.in_scale = in_scale; p.out_scale = out_scale;
-            p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = 3; p.stride = 1; p.act = act;
-            p.flags = (flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_FP8)) | FRP_FLAG_F8;
-            e = launch_conv(p, h->stream);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.p, on * (out8 ? 1 : 2), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && out2_f8) e = hipMemcpyAsync(out2_f8, dout2.p, on, hipMemcpyDeviceToHost, h->stream);
-    }
-    hipError_t e2 = hipStreamSynchronize(h->stream);
-    DevBuf* all[] = {&dx, &dw, &dws, &db, &ds, &dr, &dout, &dout2};
-    for (DevBuf* b : all) release(*b);
-    if (rc != FRP_OK) return rc;
-    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("conv2d_f8: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv2d_f8 sync: ") + hipGetErrorString(e2));
-    return FRP_OK;
-}
-
-#ifdef FRP_LAB   // tuning hooks (include/frp_lab.h): only in libfrp_lab.so
-int frp_conv_bench(frp_handle* h, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride,
-                   int32_t act, int32_t flags, int32_t with_res, int32_t iters, float* ms_avg, uint64_t* stamps_out) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!ms_avg || iters <= 0 || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !(ksize == 1 || ksize == 3) ||
-        !(stride == 1 || stride == 2))
-        return fail(h, FRP_ERR_INVALID, "bad bench arguments");
-    const int pad = ksize / 2;
-    const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-    const size_t xn = (size_t)N * H * W * Cin, wn = (size_t)Cout * ksize * ksize * Cin, on = (size_t)N * Ho * Wo * Cout;
-    const bool f8 = (flags & FRP_FLAG_F8) != 0;          // fp8 operands: random fp16 bit patterns read as E4M3 bytes (timing only)
-    DevBuf dx, dw, db, ds, dr, dout;
-    int rc = ensure(h, dx, xn * 2);
-    if (rc == FRP_OK) rc = ensure(h, dw, wn * 2);
-    if (rc == FRP_OK) rc = ensure(h, db, (size_t)Cout * 4 * 9);
-    if (rc == FRP_OK) rc = ensure(h, ds, (size_t)Cout * 4);
-    if (rc == FRP_OK) rc = ensure(h, dr, on * 2);
-    if (rc == FRP_OK) rc = ensure(h, dout, on * 4);
-    hipError_t e = hipSuccess;
-    float ms = 0.f;
-    if (rc == FRP_OK) {
-        e = launch_fill_random_f16((_Float16*)dx.p, (long)xn, 1u, 1.0f, h->stream);
-        if (e == hipSuccess) e = launch_fill_random_f16((_Float16*)dw.p, (long)wn, 2u, 1.0f / sqrtf((float)(ksize * ksize * Cin)), h->stream);
-        if (e == hipSuccess) e = launch_fill_random_f16((_Float16*)dr.p, (long)on, 3u, 1.0f, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(db.p, 0, (size_t)Cout * 36, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(ds.p, 0, (size_t)Cout * 4, h->stream);
-        ConvParams p{};
-        p.x = (const _Float16*)dx.p; p.w = (const _Float16*)dw.p; p.bias = (const float*)db.p; p.slope = (const float*)ds.p;
-        p.res = with_res ? (const _Float16*)dr.p : nullptr; p.out = dout.p;
-        p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ksize; p.stride = stride; p.act = act;
-        p.flags = flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_F8 | FRP_FLAG_OUT_FP8);
-        if (f8) {                                         // unit scales in the slope buffer's neighbour: reuse the bias buffer (zeros) + 1
-            p.wscale = (const float*)ds.p;                // zeros: products vanish, timing is unaffected
-            p.in_scale = p.out_scale = 1.0f;
-            if (!(flags & FRP_FLAG_OUT_FP8)) p.out2 = dr.p;   // conv2-style: fp16 out + fp8 copy (residual buffer doubles as the copy target when unused)
-            if (with_res) p.out2 = nullptr;
-        }
-        conv_route_from_abi_flags(flags, p);
-        DevBuf dwino;
-        bool wino_shape = conv3x3_wino_shape_ok(W, Cin, ksize, stride) || (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, with_res != 0));
-        wino_shape = wino_shape || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
-        if ((flags & (1 << 16)) && wino_shape) {     // Winograd kernel: a random weight image (timing only)
-            const size_t ib = conv3x3_wino_image_bytes(Cin, Cout);
-            if (ensure(h, dwino, ib) == FRP_OK) {
-                e = launch_fill_random_f16((_Float16*)dwino.p, (long)(ib / 2), 5u, 1.0f / sqrtf((float)(9 * Cin)), h->stream);
-                p.wino_w = (const _Float16*)dwino.p;
-            }
-        }
-        DevBuf dst;
-        if (stamps_out && ensure(h, dst, 256 * 8 * 8) == FRP_OK) {
-            (void)hipMemsetAsync(dst.p, 0, 256 * 8 * 8, h->stream);
-            p.stamps = (unsigned long long*)dst.p;
-        }
-        for (int i = 0; i < 2 && e == hipSuccess; ++i) e = launch_conv(p, h->stream);   // warm-up
-        if (e == hipSuccess) e = hipEventRecord(h->ev[0], h->stream);
-        for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv(p, h->stream);
-        if (e == hipSuccess) e = hipEventRecord(h->ev[1], h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-        if (e == hipSuccess && stamps_out && p.stamps) e = hipMemcpy(stamps_out, p.stamps, 256 * 8 * 8, hipMemcpyDeviceToHost);
-        release(dst);
-        (void)hipStreamSynchronize(h->stream);
-        release(dwino);
-    }
-    (void)hipStreamSynchronize(h->stream);
-    DevBuf* all[] = {&dx, &dw, &db, &ds, &dr, &dout};
-    for (DevBuf* b : all) release(*b);
-    if (rc != FRP_OK) return rc;
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv_bench: ") + hipGetErrorString(e));
-    *ms_avg = ms / iters;
-    return FRP_OK;
-}
-
-int frp_mfma_peak(frp_handle* h, int32_t waves_per_simd, int32_t iters, float* tflops) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    // waves_per_simd 1..8: register-operand loop.  16*r + 2 (r = 4, 3, 2): the conv k-step mix - 8 waves per CU,
-    // r ds_read_b128 per 4 MFMAs - one 512-thread block per CU
-    const int lds_reads = waves_per_simd >> 4;
-    if (lds_reads) waves_per_simd &= 15;
-    if (!tflops || iters <= 0 || waves_per_simd < 1 || waves_per_simd > 8 || (lds_reads && (waves_per_simd != 2 || lds_reads < 2 || lds_reads > 4)))
-        return fail(h, FRP_ERR_INVALID, "bad arguments");
-    const int blocks = lds_reads ? h->n_cu : 256 * waves_per_simd;   // 256 CUs x (4 waves per block = one per SIMD)
-    DevBuf src, dst;
-    int rc = ensure(h, src, 3 * 384 * 128);
-    if (rc == FRP_OK) rc = ensure(h, dst, (size_t)blocks * 512 * 4);
-    hipError_t e = hipSuccess;
-    float ms = 0.f;
-    if (rc == FRP_OK) {
-        e = launch_fill_random_f16((_Float16*)src.p, 3 * 384 * 64, 7u, 1.0f, h->stream);
-        auto run = [&]() {
-            return lds_reads ? launch_mfma_lds((const _Float16*)src.p, (float*)dst.p, blocks, lds_reads, iters, h->stream)
-                             : launch_mfma_peak((const _Float16*)src.p, (float*)dst.p, blocks, iters, h->stream);
-        };
-        if (e == hipSuccess) e = run();
-        if (e == hipSuccess) e = hipEventRecord(h->ev[0], h->stream);
-        if (e == hipSuccess) e = run();
-        if (e == hipSuccess) e = hipEventRecord(h->ev[1], h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-    }
-    (void)hipStreamSynchronize(h->stream);
-    release(src);
-    release(dst);
-    if (rc != FRP_OK) return rc;
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("mfma_peak: ") + hipGetErrorString(e));
-    *tflops = (float)((double)blocks * (lds_reads ? 8.0 * 16 : 4.0 * 4) * iters * 32768.0 / (ms * 1e-3) / 1e12);
-    return FRP_OK;
-}
-
-int frp_kstep_lab(frp_handle* h, int32_t variant, int32_t iters, float* tflops) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    if (!tflops || iters <= 0) return fail(h, FRP_ERR_INVALID, "bad arguments");
-    const int blocks = h->n_cu;
-    DevBuf src, dst;
-    int rc = ensure(h, src, 4u << 20);        // LDS image + the 4 MiB window the lab's LDS-DMA variants read
-    if (rc == FRP_OK) rc = ensure(h, dst, (size_t)blocks * 512 * 4);
-    hipError_t e = hipSuccess;
-    float ms = 0.f;
-    if (rc == FRP_OK) {
-        e = launch_fill_random_f16((_Float16*)src.p, 2L << 20, 7u, 1.0f, h->stream);
-        if (e == hipSuccess) e = launch_kstep_lab((const _Float16*)src.p, (float*)dst.p, blocks, variant, iters, h->stream);
-        if (e == hipSuccess) e = hipEventRecord(h->ev[0], h->stream);
-        if (e == hipSuccess) e = launch_kstep_lab((const _Float16*)src.p, (float*)dst.p, blocks, variant, iters, h->stream);
-        if (e == hipSuccess) e = hipEventRecord(h->ev[1], h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-    }
-    (void)hipStreamSynchronize(h->stream);
-    release(src);
-    release(dst);
-    if (rc != FRP_OK) return rc;
-    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("kstep_lab: ") + hipGetErrorString(e));
-    // fp8 variants (bit 10): 8 MFMAs of 32x32x64 per wave and step = twice the FLOPs of the fp16 step
-    *tflops = (float)((double)blocks * kstep_lab_waves(variant) * 16 * kstep_lab_steps_per_iter(variant) * iters * 32768.0 * ((variant & 1024) ? 2.0 : 1.0) /
-                      (ms * 1e-3) / 1e12);
-    return FRP_OK;
-}
-
-#endif  // FRP_LAB
 
 int frp_get_counters(frp_handle* h, frp_counters* out) {
     if (!h || !out) return FRP_ERR_INVALID;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "frp.h"
@@ -129,5 +130,39 @@ inline void release(DevBuf& b) {
     b.p = nullptr;
     b.cap = 0;
 }
+
+#define FRP_LOCAL __attribute__((visibility("hidden")))   // shared between the host files, not one of the library's exports
+
+// A function-local device buffer: freed when it goes out of scope, on error returns too.  The only ways at the allocation are
+// ensure() below, reads through ->, and take(), which hands it on to a handle member: no copy can leave a second owner.
+// (A free behind unfinished work relies on hipFree waiting for the device, as release() always did.)
+class FRP_LOCAL ScopedBuf {
+    DevBuf b;
+    friend int ensure(frp_handle* h, ScopedBuf& s, size_t bytes) { return ensure(h, s.b, bytes); }
+
+public:
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf&) = delete;
+    ScopedBuf& operator=(const ScopedBuf&) = delete;
+    ~ScopedBuf() { release(b); }
+    const DevBuf* operator->() const { return &b; }
+    DevBuf take() { return std::exchange(b, DevBuf()); }
+};
+
+// What the files of entry points share (frp_api.cpp, gallery_api.cpp, kernel_api.cpp)
+FRP_LOCAL void settle_events(frp_handle* h, bool stream_is_idle);   // frp_api.cpp
+// host fp32 rows -> unit fp16 rows at dst (device), via the scratch buffer (gallery_api.cpp)
+FRP_LOCAL int upload_rows_normalized(frp_handle* h, const float* rows, int64_t n, _Float16* dst);
+FRP_LOCAL void dist_shutdown(frp_handle* h);                        // gallery_api.cpp: drops the handle's RCCL communicator, if any
+
+// every entry point's first statement: the handle's mutex, its device, and - unless the call only touches the copy stream - the stage
+// events of a pass nobody has read yet
+struct Guard {
+    std::lock_guard<std::mutex> lk;
+    explicit Guard(frp_handle* h, bool settle = true) : lk(h->mu) {
+        (void)hipSetDevice(h->device);
+        if (settle) settle_events(h, false);
+    }
+};
 
 }  // namespace frp

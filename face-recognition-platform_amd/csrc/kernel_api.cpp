@@ -1,0 +1,258 @@
+// The stand-alone kernel entry points of libfrp.so: one conv launch on host tensors (frp_conv2d_nhwc, frp_conv2d_f8: the parity
+// tests' way to a single kernel) and, in libfrp_lab.so only, the tuning hooks of include/frp_lab.h.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "frp.h"
+#ifdef FRP_LAB
+#include "frp_lab.h"
+#endif
+#include "frp_handle.h"
+
+using namespace frp;
+
+#ifdef FRP_LAB
+namespace {
+// the lab hooks' clock: `warm` launches, then `iters` of them between the handle's first two events; *ms = the time between the events
+template <typename Launch>
+hipError_t time_launches(frp_handle* h, int warm, int iters, Launch launch, float* ms) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < warm && e == hipSuccess; ++i) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(h->ev[0], h->stream);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch();
+    if (e == hipSuccess) e = hipEventRecord(h->ev[1], h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, h->ev[0], h->ev[1]);
+    return e;
+}
+}  // namespace
+#endif
+
+extern "C" {
+
+namespace {   // (inside extern "C", where it always stood: its C name stays in the library's dynamic symbol table)
+// frp_conv2d_nhwc / frp_conv_bench `flags` (include/frp.h) -> the kernel A/B bits and the tile class of one conv launch
+void conv_route_from_abi_flags(int32_t flags, ConvParams& p) {
+    p.dbg = ((flags >> 8) & 0xff) | ((flags & (1 << 19)) ? CONV_DBG_WINO_2D : 0) | ((flags & (1 << 20)) ? CONV_DBG_NO_C64 : 0) |
+            ((flags & (1 << 21)) ? CONV_DBG_S2 : 0) | ((flags & (1 << 22)) ? CONV_DBG_C64_SAME_ORDER : 0) |
+            (process_switches().c64_all ? CONV_DBG_C64_ALL : 0);
+    p.small_m = (flags & (1 << 17)) ? 1 : (flags & ((1 << 18) | (1 << 16))) ? -1 : 0;     // (the Winograd kernel: never quarter tiles)
+}
+}  // namespace
+
+int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t W, int32_t Cin, const void* w, int32_t Cout,
+                    int32_t ksize, int32_t stride, const float* bias, const float* slope, const void* res, int32_t res_h,
+                    int32_t res_w, int32_t act, int32_t flags, void* out) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!x || !w || !bias || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !(ksize == 1 || ksize == 3) ||
+        !(stride == 1 || stride == 2))
+        return fail(h, FRP_ERR_INVALID, "bad conv arguments");
+    const int pad = ksize / 2;
+    const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+    const bool up2 = flags & FRP_FLAG_RES_UP2;
+    const size_t xb = (size_t)N * H * W * Cin * 2, wb = (size_t)Cout * ksize * ksize * Cin * 2;
+    const size_t bb = (size_t)Cout * 4 * ((flags & FRP_FLAG_BORDER_BIAS) ? 9 : 1);
+    const size_t ob = (size_t)N * Ho * Wo * Cout * ((flags & FRP_FLAG_OUT_F32) ? 4 : 2);
+    const size_t rb = res ? (size_t)N * (up2 ? res_h : Ho) * (up2 ? res_w : Wo) * Cout * 2 : 0;
+    ScopedBuf dx, dw, db, ds, dr, dout, dwino;
+    FRPCHK(ensure(h, dx, xb));
+    FRPCHK(ensure(h, dw, wb));
+    FRPCHK(ensure(h, db, bb));
+    FRPCHK(ensure(h, dout, ob));
+    if (slope) FRPCHK(ensure(h, ds, (size_t)Cout * 4));
+    if (res) FRPCHK(ensure(h, dr, rb));
+    ConvParams p{};
+    conv_route_from_abi_flags(flags, p);
+    // flags bit 16: through the Winograd kernel (parity tests); an ineligible shape is an error, not a silent fallback
+    const bool want_wino = (flags & (1 << 16)) != 0;
+    std::vector<uint16_t> wimg;
+    if (want_wino) {
+        bool shape_ok = conv3x3_wino_shape_ok(W, Cin, ksize, stride) ||
+                        (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, res != nullptr));      // (2-D tiles: wide maps)
+#ifdef FRP_LAB
+        shape_ok = shape_ok || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
+#endif
+        if (!shape_ok || (flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2)))
+            return fail(h, FRP_ERR_INVALID, "shape not covered by the Winograd kernel");
+        wimg.resize(conv3x3_wino_image_bytes(Cin, Cout) / 2);
+        build_wino_image((const uint16_t*)w, Cin, Cout, wimg.data());
+        FRPCHK(ensure(h, dwino, wimg.size() * 2));
+    }
+    hipError_t e = hipMemcpyAsync(dx->p, x, xb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && want_wino) e = hipMemcpyAsync(dwino->p, wimg.data(), wimg.size() * 2, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw->p, w, wb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db->p, bias, bb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && slope) e = hipMemcpyAsync(ds->p, slope, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && res) e = hipMemcpyAsync(dr->p, res, rb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        p.x = (const _Float16*)dx->p; p.w = (const _Float16*)dw->p; p.bias = (const float*)db->p;
+        p.slope = slope ? (const float*)ds->p : nullptr;
+        p.res = res ? (const _Float16*)dr->p : nullptr;
+        p.out = dout->p;
+        p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ksize; p.stride = stride; p.act = act;
+        p.flags = flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2);
+        p.Hr = res_h; p.Wr = res_w;
+        if (want_wino) p.wino_w = (const _Float16*)dwino->p;
+        e = launch_conv(p, h->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout->p, ob, hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("conv2d: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv2d sync: ") + hipGetErrorString(e2));
+    return FRP_OK;
+}
+
+int frp_conv2d_f8(frp_handle* h, const void* x8, int32_t N, int32_t H, int32_t W, int32_t Cin, const void* w8, int32_t Cout,
+                  const float* wscale, const float* bias, const float* slope, const void* res16, int32_t act, int32_t flags,
+                  float in_scale, float out_scale, void* out, void* out2_f8) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!x8 || !w8 || !wscale || !bias || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0)
+        return fail(h, FRP_ERR_INVALID, "bad conv arguments");
+    const bool out8 = (flags & FRP_FLAG_OUT_FP8) != 0;
+    const size_t xb = (size_t)N * H * W * Cin, wb = (size_t)Cout * 9 * Cin, on = (size_t)N * H * W * Cout;
+    const size_t bb = (size_t)Cout * 4 * ((flags & FRP_FLAG_BORDER_BIAS) ? 9 : 1);
+    ScopedBuf dx, dw, dws, db, ds, dr, dout, dout2;
+    FRPCHK(ensure(h, dx, xb));
+    FRPCHK(ensure(h, dw, wb));
+    FRPCHK(ensure(h, dws, (size_t)Cout * 4));
+    FRPCHK(ensure(h, db, bb));
+    FRPCHK(ensure(h, dout, on * (out8 ? 1 : 2)));
+    if (out2_f8) FRPCHK(ensure(h, dout2, on));
+    if (slope) FRPCHK(ensure(h, ds, (size_t)Cout * 4));
+    if (res16) FRPCHK(ensure(h, dr, on * 2));
+    hipError_t e = hipMemcpyAsync(dx->p, x8, xb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw->p, w8, wb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dws->p, wscale, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db->p, bias, bb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && slope) e = hipMemcpyAsync(ds->p, slope, (size_t)Cout * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && res16) e = hipMemcpyAsync(dr->p, res16, on * 2, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        ConvParams p{};
+        p.x = (const _Float16*)dx->p; p.w = (const _Float16*)dw->p; p.bias = (const float*)db->p;
+        p.slope = slope ? (const float*)ds->p : nullptr;
+        p.res = res16 ? (const _Float16*)dr->p : nullptr;
+        p.out = dout->p;
+        p.out2 = out2_f8 ? dout2->p : nullptr;
+        p.wscale = (const float*)dws->p;
+        p.in_scale = in_scale; p.out_scale = out_scale;
+        p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = 3; p.stride = 1; p.act = act;
+        p.flags = (flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_FP8)) | FRP_FLAG_F8;
+        e = launch_conv(p, h->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout->p, on * (out8 ? 1 : 2), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && out2_f8) e = hipMemcpyAsync(out2_f8, dout2->p, on, hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("conv2d_f8: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv2d_f8 sync: ") + hipGetErrorString(e2));
+    return FRP_OK;
+}
+
+#ifdef FRP_LAB   // tuning hooks (include/frp_lab.h): only in libfrp_lab.so
+int frp_conv_bench(frp_handle* h, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride,
+                   int32_t act, int32_t flags, int32_t with_res, int32_t iters, float* ms_avg, uint64_t* stamps_out) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!ms_avg || iters <= 0 || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !(ksize == 1 || ksize == 3) ||
+        !(stride == 1 || stride == 2))
+        return fail(h, FRP_ERR_INVALID, "bad bench arguments");
+    const int pad = ksize / 2;
+    const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+    const size_t xn = (size_t)N * H * W * Cin, wn = (size_t)Cout * ksize * ksize * Cin, on = (size_t)N * Ho * Wo * Cout;
+    const bool f8 = (flags & FRP_FLAG_F8) != 0;          // fp8 operands: random fp16 bit patterns read as E4M3 bytes (timing only)
+    ScopedBuf dx, dw, db, ds, dr, dout, dwino, dst;
+    FRPCHK(ensure(h, dx, xn * 2));
+    FRPCHK(ensure(h, dw, wn * 2));
+    FRPCHK(ensure(h, db, (size_t)Cout * 4 * 9));
+    FRPCHK(ensure(h, ds, (size_t)Cout * 4));
+    FRPCHK(ensure(h, dr, on * 2));
+    FRPCHK(ensure(h, dout, on * 4));
+    float ms = 0.f;
+    hipError_t e = launch_fill_random_f16((_Float16*)dx->p, (long)xn, 1u, 1.0f, h->stream);
+    if (e == hipSuccess) e = launch_fill_random_f16((_Float16*)dw->p, (long)wn, 2u, 1.0f / sqrtf((float)(ksize * ksize * Cin)), h->stream);
+    if (e == hipSuccess) e = launch_fill_random_f16((_Float16*)dr->p, (long)on, 3u, 1.0f, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(db->p, 0, (size_t)Cout * 36, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ds->p, 0, (size_t)Cout * 4, h->stream);
+    ConvParams p{};
+    p.x = (const _Float16*)dx->p; p.w = (const _Float16*)dw->p; p.bias = (const float*)db->p; p.slope = (const float*)ds->p;
+    p.res = with_res ? (const _Float16*)dr->p : nullptr; p.out = dout->p;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ksize; p.stride = stride; p.act = act;
+    p.flags = flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_F8 | FRP_FLAG_OUT_FP8);
+    if (f8) {                                         // unit scales in the slope buffer's neighbour: reuse the bias buffer (zeros) + 1
+        p.wscale = (const float*)ds->p;                // zeros: products vanish, timing is unaffected
+        p.in_scale = p.out_scale = 1.0f;
+        if (!(flags & FRP_FLAG_OUT_FP8)) p.out2 = dr->p;   // conv2-style: fp16 out + fp8 copy (residual buffer doubles as the copy target when unused)
+        if (with_res) p.out2 = nullptr;
+    }
+    conv_route_from_abi_flags(flags, p);
+    bool wino_shape = conv3x3_wino_shape_ok(W, Cin, ksize, stride) || (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, with_res != 0));
+    wino_shape = wino_shape || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
+    if ((flags & (1 << 16)) && wino_shape) {     // Winograd kernel: a random weight image (timing only)
+        const size_t ib = conv3x3_wino_image_bytes(Cin, Cout);
+        if (ensure(h, dwino, ib) == FRP_OK) {
+            e = launch_fill_random_f16((_Float16*)dwino->p, (long)(ib / 2), 5u, 1.0f / sqrtf((float)(9 * Cin)), h->stream);
+            p.wino_w = (const _Float16*)dwino->p;
+        }
+    }
+    if (stamps_out && ensure(h, dst, 256 * 8 * 8) == FRP_OK) {
+        (void)hipMemsetAsync(dst->p, 0, 256 * 8 * 8, h->stream);
+        p.stamps = (unsigned long long*)dst->p;
+    }
+    if (e == hipSuccess) e = time_launches(h, 2, iters, [&] { return launch_conv(p, h->stream); }, &ms);
+    if (e == hipSuccess && stamps_out && p.stamps) e = hipMemcpy(stamps_out, p.stamps, 256 * 8 * 8, hipMemcpyDeviceToHost);
+    (void)hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv_bench: ") + hipGetErrorString(e));
+    *ms_avg = ms / iters;
+    return FRP_OK;
+}
+
+int frp_mfma_peak(frp_handle* h, int32_t waves_per_simd, int32_t iters, float* tflops) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    // waves_per_simd 1..8: register-operand loop.  16*r + 2 (r = 4, 3, 2): the conv k-step mix - 8 waves per CU,
+    // r ds_read_b128 per 4 MFMAs - one 512-thread block per CU
+    const int lds_reads = waves_per_simd >> 4;
+    if (lds_reads) waves_per_simd &= 15;
+    if (!tflops || iters <= 0 || waves_per_simd < 1 || waves_per_simd > 8 || (lds_reads && (waves_per_simd != 2 || lds_reads < 2 || lds_reads > 4)))
+        return fail(h, FRP_ERR_INVALID, "bad arguments");
+    const int blocks = lds_reads ? h->n_cu : 256 * waves_per_simd;   // 256 CUs x (4 waves per block = one per SIMD)
+    ScopedBuf src, dst;
+    FRPCHK(ensure(h, src, 3 * 384 * 128));
+    FRPCHK(ensure(h, dst, (size_t)blocks * 512 * 4));
+    float ms = 0.f;
+    hipError_t e = launch_fill_random_f16((_Float16*)src->p, 3 * 384 * 64, 7u, 1.0f, h->stream);
+    if (e == hipSuccess)
+        e = time_launches(h, 1, 1, [&] {
+            return lds_reads ? launch_mfma_lds((const _Float16*)src->p, (float*)dst->p, blocks, lds_reads, iters, h->stream)
+                             : launch_mfma_peak((const _Float16*)src->p, (float*)dst->p, blocks, iters, h->stream);
+        }, &ms);
+    (void)hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("mfma_peak: ") + hipGetErrorString(e));
+    *tflops = (float)((double)blocks * (lds_reads ? 8.0 * 16 : 4.0 * 4) * iters * 32768.0 / (ms * 1e-3) / 1e12);
+    return FRP_OK;
+}
+
+int frp_kstep_lab(frp_handle* h, int32_t variant, int32_t iters, float* tflops) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!tflops || iters <= 0) return fail(h, FRP_ERR_INVALID, "bad arguments");
+    const int blocks = h->n_cu;
+    ScopedBuf src, dst;
+    FRPCHK(ensure(h, src, 4u << 20));        // LDS image + the 4 MiB window the lab's LDS-DMA variants read
+    FRPCHK(ensure(h, dst, (size_t)blocks * 512 * 4));
+    float ms = 0.f;
+    hipError_t e = launch_fill_random_f16((_Float16*)src->p, 2L << 20, 7u, 1.0f, h->stream);
+    if (e == hipSuccess)
+        e = time_launches(h, 1, 1, [&] { return launch_kstep_lab((const _Float16*)src->p, (float*)dst->p, blocks, variant, iters, h->stream); }, &ms);
+    (void)hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("kstep_lab: ") + hipGetErrorString(e));
+    // fp8 variants (bit 10): 8 MFMAs of 32x32x64 per wave and step = twice the FLOPs of the fp16 step
+    *tflops = (float)((double)blocks * kstep_lab_waves(variant) * 16 * kstep_lab_steps_per_iter(variant) * iters * 32768.0 * ((variant & 1024) ? 2.0 : 1.0) /
+                      (ms * 1e-3) / 1e12);
+    return FRP_OK;
+}
+#endif  // FRP_LAB
+
+}  // extern "C"

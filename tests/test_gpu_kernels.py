@@ -1025,3 +1025,61 @@ def test_gallery_reserve_commit_zero_copy_import(engine):
         engine.gallery_commit(5)                             # nothing to commit
     engine.gallery_update_row(0, q[0])                       # updates work again
     engine.gallery_set(np.zeros((0, 512), np.float32))
+
+
+def test_every_way_to_install_a_gallery_snapshot_agrees(engine):
+    """The same 40 non-unit rows through every entry point that swaps a snapshot in (frp_gallery_set as fp32 / fp64 / fp16,
+    _set_device from another handle's pointer, _reserve + a producer on the device + _commit), without and with the exact
+    float64 copy: fp32 and fp64 installs give the same bytes (the fp64 rows are the fp32 rows widened), rows handed over on
+    the device arrive byte for byte, the fp16 install stays within the 1e-3 of test_exact_rows_follow_every_gallery_update
+    (fp16 rounding of unit rows: 2^-12 per value), and the exact copy holds the host rows widened bit for bit, or - rows that
+    came from the device - the unit fp16 rows widened.  40 rows: every path is row-independent."""
+    from frp_amd import dist as fdist, native
+    rng = np.random.default_rng(23)
+    r32 = (rng.standard_normal((40, 512)) * rng.uniform(0.2, 3.0, (40, 1))).astype(np.float32)
+    hosts = {"f32": r32, "f64": r32.astype(np.float64), "f16": r32.astype(np.float16)}
+    unit = fdist.normalize_rows_f16(r32)
+    first = native.Engine(0)
+
+    def from_first_engine():
+        engine.gallery_set_device(first.gallery_device_ptr(), 40)
+        return handed
+
+    def reserve_fill_commit():
+        ptr = engine.gallery_reserve(40)
+        t = torch.as_tensor(fdist._DevicePtr(ptr, 40, 512), device=torch.device("cuda", 0))
+        t.copy_(torch.from_numpy(unit))
+        torch.cuda.synchronize()
+        engine.gallery_commit(40)
+        return unit
+
+    try:
+        first.gallery_set(r32)
+        handed = first.gallery_get()
+        for exact in (False, True):
+            engine.gallery_exact(exact)
+            if exact:                      # switched on over the 40 rows the last install left: the unit fp16 rows widened
+                assert np.array_equal(engine.gallery_get_exact(), engine.gallery_get().astype(np.float64))
+            got = {}
+            for name, rows in hosts.items():
+                engine.gallery_set(rows)
+                assert engine.gallery_size() == 40
+                got[name] = engine.gallery_get()
+                wide = rows.astype(np.float64)
+                err = np.abs(got[name].astype(np.float64) - wide / np.linalg.norm(wide, axis=1, keepdims=True)).max()
+                print(f"exact={exact} {name}: max |snapshot - normalised rows| = {err:.3e}")
+                assert err < 1e-3
+                if exact:
+                    assert np.array_equal(engine.gallery_get_exact(), wide)
+            assert got["f32"].tobytes() == got["f64"].tobytes()
+            for install in (from_first_engine, reserve_fill_commit):
+                given = install()
+                assert engine.gallery_size() == 40 and engine.gallery_get().tobytes() == given.tobytes()
+                if exact:
+                    assert np.array_equal(engine.gallery_get_exact(), engine.gallery_get().astype(np.float64))
+        engine.gallery_set(np.zeros((0, 512), np.float32))
+        assert engine.gallery_size() == 0
+    finally:
+        first.close()
+        engine.gallery_cancel()
+        engine.gallery_exact(False)

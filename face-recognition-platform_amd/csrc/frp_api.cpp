@@ -181,6 +181,7 @@ int run_embed(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev = n
                    family_count >= sw.wino_min_faces, &fc));
     rec(h, EV_EMB);
     const int mpad = round_up(n, 32);
+    h->q16_of_pass = false;
     FRPCHK(ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2));
     HIPCHK(h, hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream));
     hipError_t e = launch_l2norm((float*)h->emb.bufs[h->hdr.emb_out_buf].p, (_Float16*)h->q16.p, n, FRP_EMB_DIM, h->stream,
@@ -191,8 +192,20 @@ int run_embed(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev = n
     return FRP_OK;
 }
 
-// q16 [mpad,512] holds n unit queries -> best_idx/best_cos [n]
-int run_match(frp_handle* h, const Switches& sw, int n, float* all_scores_dev, const int32_t* n_dev = nullptr) {
+// the "within" epilogue of a match pass (frp_match_within, FRP_FLAG_WITHIN): bound, list size and the device lists [n], [n x cap]
+struct WithinArgs {
+    float min_cos;
+    int cap;
+    int32_t* cnt;
+    int32_t* idx;
+    float* cos;
+};
+static_assert(FRP_WITHIN_MAX_CAP == FRP_MAX_TOPK, "frp_internal.h: FRP_WITHIN_MAX_CAP");
+bool within_args_ok(float min_cos, int cap) { return min_cos >= -2.0f && cap >= 1 && cap <= FRP_MAX_TOPK; }   // (NaN fails the first)
+
+// q16 [mpad,512] holds n unit queries -> best_idx/best_cos [n] (+ the hit lists of `within`, in the same launch)
+int run_match(frp_handle* h, const Switches& sw, int n, float* all_scores_dev, const int32_t* n_dev = nullptr,
+              const WithinArgs* within = nullptr) {
     if (n <= 0) return FRP_OK;
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     const int mpad = round_up(n, 32);
@@ -211,11 +224,64 @@ int run_match(frp_handle* h, const Switches& sw, int n, float* all_scores_dev, c
     mp.best_cos = (float*)h->best_cos.p; mp.best_idx = (int32_t*)h->best_idx.p;
     mp.all_scores = all_scores_dev;
     mp.n_dev = n_dev;
+    if (within) {
+        HIPCHK(h, hipMemsetAsync(within->cnt, 0, (size_t)n * 4, h->stream));      // counters start at zero before EVERY pass
+        mp.min_cos = within->min_cos; mp.cap = within->cap;
+        mp.hit_count = within->cnt; mp.hit_idx = within->idx; mp.hit_cos = within->cos;
+    }
     hipError_t e = launch_match(mp, sw.match_v1 != 0, h->stream);
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("match: ") + hipGetErrorString(e));
     h->ctr.match_bytes += (double)h->g_rows * FRP_EMB_DIM * 2;
     h->ctr.match_launches += 1;
     return FRP_OK;
+}
+
+// Queries `over` (indices into q16 and into the lists) have more than `cap` rows at or above the bound: which of them took the
+// slots was a race, so their lists are rebuilt as the first `cap` entries of the matcher's total order - the score rows of those
+// queries alone (the per-tile kernel's all_scores epilogue: the same bits), then launch_topk_rows.  All of those entries are hits.
+int rebuild_within_lists(frp_handle* h, const _Float16* q16, const std::vector<int>& over, int cap, int32_t* hit_idx, float* hit_cos) {
+    const long N = h->g_rows;
+    const int total = (int)over.size();
+    const int chunk = (int)std::max<long>(1, std::min<long>(total, (1L << 28) / N));      // <= 1 GiB of scores at a time
+    const int cpad = round_up(chunk, 32);
+    const int n_wg = match_num_workgroups(N);
+    ScopedBuf qt, all, pc, pi, bc, bi, tidx, tcos;
+    FRPCHK(ensure(h, qt, (size_t)cpad * FRP_EMB_DIM * 2));
+    FRPCHK(ensure(h, all, (size_t)chunk * N * 4));
+    FRPCHK(ensure(h, pc, (size_t)n_wg * cpad * 4));
+    FRPCHK(ensure(h, pi, (size_t)n_wg * cpad * 4));
+    FRPCHK(ensure(h, bc, (size_t)cpad * 4));
+    FRPCHK(ensure(h, bi, (size_t)cpad * 4));
+    FRPCHK(ensure(h, tidx, (size_t)chunk * cap * 4));
+    FRPCHK(ensure(h, tcos, (size_t)chunk * cap * 4));
+    for (int m0 = 0; m0 < total; m0 += chunk) {
+        const int m = std::min(chunk, total - m0);
+        HIPCHK(h, hipMemsetAsync(qt->p, 0, (size_t)cpad * FRP_EMB_DIM * 2, h->stream));
+        for (int i = 0; i < m; ++i)
+            HIPCHK(h, hipMemcpyAsync((_Float16*)qt->p + (size_t)i * FRP_EMB_DIM, q16 + (size_t)over[m0 + i] * FRP_EMB_DIM, FRP_EMB_DIM * 2,
+                                     hipMemcpyDeviceToDevice, h->stream));
+        MatchParams mp{};
+        mp.gallery = (const _Float16*)h->gallery.p;
+        mp.N = N;
+        mp.q = (const _Float16*)qt->p;
+        mp.M = m;
+        mp.Mpad = round_up(m, 32);
+        mp.n_wg = n_wg;
+        mp.part_cos = (float*)pc->p; mp.part_idx = (int32_t*)pi->p;
+        mp.best_cos = (float*)bc->p; mp.best_idx = (int32_t*)bi->p;
+        mp.all_scores = (float*)all->p;
+        hipError_t e = launch_match(mp, true, h->stream);
+        if (e == hipSuccess) e = launch_topk_rows((const float*)all->p, m, N, cap, (int32_t*)tidx->p, (float*)tcos->p, h->stream);
+        if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("match within (overflow): ") + hipGetErrorString(e));
+        h->ctr.match_bytes += (double)N * FRP_EMB_DIM * 2;
+        h->ctr.match_launches += 1;
+        for (int i = 0; i < m; ++i) {
+            const size_t dst = (size_t)over[m0 + i] * cap, src = (size_t)i * cap;
+            HIPCHK(h, hipMemcpyAsync(hit_idx + dst, (int32_t*)tidx->p + src, (size_t)cap * 4, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(hit_cos + dst, (float*)tcos->p + src, (size_t)cap * 4, hipMemcpyDeviceToDevice, h->stream));
+        }
+    }
+    return FRP_OK;          // stream-ordered: the caller waits for the stream before the scoped buffers go
 }
 
 // align + embed + match for the faces listed in h->kps / h->counts / h->face_slot (device), always from
@@ -224,6 +290,8 @@ int resolve_count(frp_handle* h);
 int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t flags) {
     const int B = h->rB;
     int n;
+    const bool want_within = (flags & FRP_FLAG_WITHIN) && !(flags & FRP_FLAG_NO_MATCH);
+    if (want_within && h->within_cap <= 0) return fail(h, FRP_ERR_INVALID, "FRP_FLAG_WITHIN: call frp_set_within first");
     // a device-count pass that nobody fetched or synchronised yet (two process calls queued back to back): its count and its
     // counter corrections live in single slots (h_nfaces, pend_*) this pass is about to reuse - settle it first
     if (h->last_nfaces < 0) {
@@ -254,6 +322,8 @@ int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t fl
     h->last_nfaces = n_dev ? -1 : n;          // -1: pending, resolved by the next call that waits for the stream
     h->last_cap = n;
     h->last_matched = false;
+    h->last_within_cap = want_within ? h->within_cap : 0;
+    h->last_within_lists = false;
     const double flops0 = h->ctr.emb_conv_flops, f8flops0 = h->ctr.f8_conv_flops;
     if (n > 0) {
         FRPCHK(plan_net(h, h->emb, n, FRP_CHIP, FRP_CHIP));
@@ -275,7 +345,18 @@ int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t fl
         rec(h, EV_ALIGN);
         FRPCHK(run_embed(h, sw, n, n_dev, n_known >= 0 ? n_known : B * K));
         if (!(flags & FRP_FLAG_NO_MATCH) && h->g_rows > 0) {
-            FRPCHK(run_match(h, sw, n, nullptr, n_dev));
+            if (want_within) {          // the same kernel with the hit-list epilogue: one gallery pass for top-1 and the lists
+                const int cap = h->within_cap;
+                FRPCHK(ensure(h, h->hit_cnt, (size_t)n * 4));
+                FRPCHK(ensure(h, h->hit_idx, (size_t)n * cap * 4));
+                FRPCHK(ensure(h, h->hit_cos, (size_t)n * cap * 4));
+                const WithinArgs w{h->within_min_cos, cap, (int32_t*)h->hit_cnt.p, (int32_t*)h->hit_idx.p, (float*)h->hit_cos.p};
+                FRPCHK(run_match(h, sw, n, nullptr, n_dev, &w));
+                h->last_within_lists = true;
+                h->q16_of_pass = true;
+            } else {
+                FRPCHK(run_match(h, sw, n, nullptr, n_dev));
+            }
             h->last_matched = true;
         }
         rec(h, EV_MATCH);
@@ -430,6 +511,66 @@ int fetch_results(frp_handle* h, float* boxes, float* kps, float* scores, int32_
     return FRP_OK;
 }
 
+// the hit lists of the last flagged pass, compact face list -> [B][K] slots (frp.h: frp_fetch_within)
+int fetch_within(frp_handle* h, int cap, int32_t* idx, float* cos, int32_t* n_hits) {
+    const int B = h->last_B, K = h->last_K;
+    if (B <= 0) return fail(h, FRP_ERR_INVALID, "nothing to fetch");
+    if (h->last_within_cap <= 0) return fail(h, FRP_ERR_INVALID, "fetch_within: the last pass ran without FRP_FLAG_WITHIN");
+    if (cap != h->last_within_cap) return fail(h, FRP_ERR_INVALID, "fetch_within: buffers sized for another list size than the pass used");
+    if (!idx || !cos || !n_hits) return fail(h, FRP_ERR_INVALID, "fetch_within: null output");
+    if (h->last_nfaces < 0) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        FRPCHK(resolve_count(h));
+    }
+    const int n = h->last_nfaces;
+    const size_t s = (size_t)B * K;
+    std::fill(n_hits, n_hits + s, 0);
+    std::fill(idx, idx + s * cap, -1);
+    std::fill(cos, cos + s * cap, -2.0f);
+    if (n <= 0 || !h->last_within_lists) return FRP_OK;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_cnt = take((size_t)B * 4), o_hc = take((size_t)n * 4), o_hi = take((size_t)n * cap * 4), o_hs = take((size_t)n * cap * 4);
+    FRPCHK(ensure_pinned(h, off));
+    unsigned char* st = h->pin_stage;
+    auto copy_lists = [&]() -> int {
+        HIPCHK(h, hipMemcpyAsync(st + o_hi, h->hit_idx.p, (size_t)n * cap * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + o_hs, h->hit_cos.p, (size_t)n * cap * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return FRP_OK;
+    };
+    HIPCHK(h, hipMemcpyAsync(st + o_cnt, h->counts.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(st + o_hc, h->hit_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    FRPCHK(copy_lists());
+    settle_events(h, true);
+    const int32_t* cnt = (const int32_t*)(st + o_cnt);
+    const int32_t* hc = (const int32_t*)(st + o_hc);
+    std::vector<int> over;
+    for (int f = 0; f < n; ++f)
+        if (hc[f] > cap) over.push_back(f);
+    if (!over.empty()) {
+        if (!h->q16_of_pass)
+            return fail(h, FRP_ERR_INVALID, "fetch_within: a face has more hits than the list holds and a later call replaced the pass's embeddings");
+        int rc = rebuild_within_lists(h, (const _Float16*)h->q16.p, over, cap, (int32_t*)h->hit_idx.p, (float*)h->hit_cos.p);
+        if (rc == FRP_OK) rc = copy_lists();
+        else (void)hipStreamSynchronize(h->stream);
+        FRPCHK(rc);
+    }
+    const int32_t* hi = (const int32_t*)(st + o_hi);
+    const float* hs = (const float*)(st + o_hs);
+    int f = 0;
+    for (int b = 0; b < B; ++b) {
+        const int nb = std::max(0, std::min(cnt[b], K));
+        for (int k = 0; k < nb && f < n; ++k, ++f) {
+            const size_t slot = (size_t)b * K + k;
+            n_hits[slot] = hc[f];
+            memcpy(idx + slot * cap, hi + (size_t)f * cap, (size_t)cap * 4);
+            memcpy(cos + slot * cap, hs + (size_t)f * cap, (size_t)cap * 4);
+        }
+    }
+    return FRP_OK;
+}
+
 }  // namespace
 
 // frp_process_resident returns without waiting for the device also when the stage timers are on: its events are read
@@ -501,7 +642,7 @@ void frp_destroy(frp_handle* h) {
     for (DevBuf& b : h->det.bufs) release(b);
     for (DevBuf& b : h->emb.bufs) release(b);
     DevBuf* all[] = {&h->wdata, &h->frames, &h->frames_next, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
-                     &h->q16, &h->part_cos, &h->part_idx, &h->best_cos, &h->best_idx, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
+                     &h->q16, &h->part_cos, &h->part_idx, &h->best_cos, &h->best_idx, &h->hit_cnt, &h->hit_idx, &h->hit_cos, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
                      &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->jpeg_coef, &h->jpeg_planes, &h->jpeg_scan, &h->jpeg_err, &h->det_hashes};
     for (DevBuf* b : all) release(*b);
     for (int i = 0; i < EV_COUNT; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
@@ -865,6 +1006,23 @@ int frp_fetch_results(frp_handle* h, int32_t B, int32_t max_faces, float* boxes,
     return fetch_results(h, boxes, kps, scores, counts, emb, match_idx, match_cos);
 }
 
+int frp_set_within(frp_handle* h, float min_cos, int32_t cap) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);
+    if (!within_args_ok(min_cos, cap)) return fail(h, FRP_ERR_INVALID, "set_within: min_cos must be >= -2 and cap in 1..FRP_MAX_TOPK");
+    h->within_min_cos = min_cos;
+    h->within_cap = cap;
+    return FRP_OK;
+}
+
+int frp_fetch_within(frp_handle* h, int32_t B, int32_t max_faces, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);
+    if (B != h->last_B || max_faces != h->last_K)
+        return fail(h, FRP_ERR_INVALID, "fetch_within: buffers sized for another batch (results were replaced by a later call)");
+    return fetch_within(h, cap, idx, cos, n_hits);
+}
+
 int frp_process_frames(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, int32_t W, int64_t row_stride,
                        int32_t max_faces, float det_thresh, float nms_iou, uint32_t flags, float* boxes, float* kps,
                        float* scores, int32_t* counts, float* emb, int32_t* match_idx, float* match_cos) {
@@ -1155,6 +1313,7 @@ static int match_common(frp_handle* h, const float* q, int M, float* all_scores_
     if (!q || M <= 0 || M > (1 << 20)) return fail(h, FRP_ERR_INVALID, "bad query arguments");
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     const int mpad = round_up(M, 32);
+    h->q16_of_pass = false;
     FRPCHK(ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2));
     HIPCHK(h, hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream));
     FRPCHK(upload_rows_normalized(h, q, M, (_Float16*)h->q16.p));
@@ -1184,6 +1343,7 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     const long N = h->g_rows;
     const Switches sw = read_switches();
+    h->q16_of_pass = false;
     int chunk = (int)std::max<long>(1, std::min<long>(M, (1L << 28) / N));
     ScopedBuf all, didx, dcos;
     int rc = ensure(h, all, (size_t)chunk * N * 4);
@@ -1218,6 +1378,51 @@ int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, i
     // cos_all holds M x n_cols floats: the gallery may have grown since the caller read its size
     if (n_cols != h->g_rows) return fail(h, FRP_ERR_INVALID, "match_scores: output sized for another gallery size");
     return match_common(h, q, M, cos_all, nullptr, nullptr);
+}
+
+int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!within_args_ok(min_cos, cap)) return fail(h, FRP_ERR_INVALID, "match_within: min_cos must be >= -2 and cap in 1..FRP_MAX_TOPK");
+    if (!q || !idx || !cos || !n_hits || M <= 0 || M > (1 << 20)) return fail(h, FRP_ERR_INVALID, "bad query arguments");
+    if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
+    const Switches sw = read_switches();
+    h->q16_of_pass = false;
+    const int chunk = std::min<int>(M, 65536);
+    ScopedBuf dcnt, didx, dcos;
+    int rc = ensure(h, dcnt, (size_t)chunk * 4);
+    if (rc == FRP_OK) rc = ensure(h, didx, (size_t)chunk * cap * 4);
+    if (rc == FRP_OK) rc = ensure(h, dcos, (size_t)chunk * cap * 4);
+    hipError_t e = hipSuccess;
+    std::vector<int> over;
+    for (int m0 = 0; rc == FRP_OK && e == hipSuccess && m0 < M; m0 += chunk) {
+        const int m = std::min(chunk, M - m0);
+        const int mpad = round_up(m, 32);
+        int32_t* nh = n_hits + m0;
+        rc = ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2);
+        if (rc != FRP_OK) break;
+        e = hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream);
+        if (e != hipSuccess) break;
+        rc = upload_rows_normalized(h, q + (size_t)m0 * FRP_EMB_DIM, m, (_Float16*)h->q16.p);
+        const WithinArgs w{min_cos, cap, (int32_t*)dcnt->p, (int32_t*)didx->p, (float*)dcos->p};
+        if (rc == FRP_OK) rc = run_match(h, sw, m, nullptr, nullptr, &w);
+        if (rc != FRP_OK) break;
+        e = hipMemcpyAsync(nh, dcnt->p, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) break;
+        over.clear();                       // the counts are on the host: lists that overflowed are rebuilt from their score rows
+        for (int i = 0; i < m; ++i)
+            if (nh[i] > cap) over.push_back(i);
+        if (!over.empty()) rc = rebuild_within_lists(h, (const _Float16*)h->q16.p, over, cap, (int32_t*)didx->p, (float*)dcos->p);
+        if (rc != FRP_OK) break;
+        e = hipMemcpyAsync(idx + (size_t)m0 * cap, didx->p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * cap, dcos->p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    (void)hipStreamSynchronize(h->stream);
+    if (rc != FRP_OK) return rc;
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("match within: ") + hipGetErrorString(e));
+    return FRP_OK;
 }
 
 int frp_get_counters(frp_handle* h, frp_counters* out) {

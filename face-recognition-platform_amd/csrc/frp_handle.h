@@ -61,6 +61,13 @@ struct frp_handle {
     double pend_flops = 0.0, pend_f8flops = 0.0;
     bool ev_pending = false;   // frp_process_resident's stage events are recorded but not yet read (see settle_events)
     bool last_matched = false;
+    // radius match (frp_set_within, FRP_FLAG_WITHIN): bound and list size for the flagged passes to come; the lists of the last one
+    float within_min_cos = 0.f;
+    int within_cap = 0;               // 0: frp_set_within has not been called
+    frp::DevBuf hit_cnt, hit_idx, hit_cos;   // [n], [n x cap], [n x cap] per compact face of the last flagged pass
+    int last_within_cap = 0;          // list size of the last pass, 0: it ran without FRP_FLAG_WITHIN
+    bool last_within_lists = false;   // ... and it matched (faces and a gallery): the buffers above hold its lists
+    bool q16_of_pass = false;         // q16 still holds that pass's queries (a list that overflowed is rebuilt from them at fetch time)
     int32_t* h_nfaces = nullptr;   // pinned
     unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
     size_t pin_cap = 0;

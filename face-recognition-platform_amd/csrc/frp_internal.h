@@ -325,7 +325,14 @@ struct MatchParams {
     float* all_scores;        // [M, N] or null
     int n_wg;
     const int32_t* n_dev;     // null, or the real query count (<= M) in device memory (top-1 path only)
+    // "within" epilogue (hit_count null: off; not together with all_scores): every row of a real query whose cosine is >= min_cos
+    float min_cos;            // >= -2 (cosines lie in [-1, 1]: -2 lists every row)
+    int cap;                  // list slots per query, 1..FRP_WITHIN_MAX_CAP
+    int32_t* hit_count;       // [M], zeroed on the stream before the pass: the TRUE number of such rows (may exceed cap)
+    int32_t* hit_idx;         // [M, cap] ordered by (cosine desc, row asc), -1 beyond min(count, cap); a query with count > cap holds
+    float* hit_cos;           // [M, cap] `cap` of its hits, which ones is a race: the caller rebuilds it (launch_topk_rows), -2.0 beyond
 };
+#define FRP_WITHIN_MAX_CAP 64    // == FRP_MAX_TOPK (frp.h): one lane per list entry in the sort, and what launch_topk_rows rebuilds
 int match_num_workgroups(long N);
 #define FRP_MATCH_TOP1_MAX 512   // queries per launch the persistent top-1 kernel covers (the only one that takes n_dev)
 // per_tile_only: never the persistent top-1 kernel (A/B runs: Switches::match_v1); a launch with n_dev then fails

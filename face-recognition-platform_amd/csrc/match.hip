@@ -32,7 +32,23 @@ __device__ __forceinline__ int q_lds_off(int row, int chunk) {   // 1 KiB rows, 
     return row * 1024 + ((chunk ^ (row & 15)) << 4);
 }
 
-__global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) {
+// The "within" epilogue of both MFMA kernels (radius match: every gallery row whose cosine is at or above a bound - the reference's
+// filter loop `d <= tolerance` over all targets, routes/camera.py:246-256, face_service.py:448-481 - instead of the best one): an
+// accumulator element that passes takes a slot of its query's list with a vector atomic on the query's counter.  The counter always
+// ends as the TRUE number of such rows; a list keeps the first `cap` arrivals, in arrival order - within_sort_kernel below puts
+// them into the matcher's total order, and the caller rebuilds the lists of queries whose count exceeds cap (which arrivals won
+// the slots is a race).  The score is the accumulator of the same MFMA chain: bit-identical to the frp_match_scores entry.
+__device__ __forceinline__ void within_emit(const MatchParams& p, int q, int g, float v) {
+    const int slot = atomicAdd(p.hit_count + q, 1);
+    if (slot < p.cap) {
+        p.hit_idx[(long)q * p.cap + slot] = g;
+        p.hit_cos[(long)q * p.cap + slot] = v;
+    }
+}
+
+// WITHIN: the same tiles, the same top-1 partials, plus the "within" epilogue (hit lists; no score matrix) - see below
+template <bool WITHIN>
+__device__ __forceinline__ void match_tiles(MatchParams p) {
     // two DISTINCT arrays: with one runtime-indexed array the compiler cannot tell the DMA target from the tile being
     // read and waits for the prefetch (vmcnt(0)) before the first fragment read of every tile
     __shared__ __attribute__((aligned(16))) unsigned char qs0[MT_Q * 1024];
@@ -101,8 +117,19 @@ __global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) {
             const long g = g0 + (e & 3) + 8 * (e >> 2) + 4 * fh;
             const float v = acc[e];
             if (g < p.N) {
-                if (p.all_scores && q < p.M) p.all_scores[(long)q * p.N + g] = v;
+                if (!WITHIN && p.all_scores && q < p.M) p.all_scores[(long)q * p.N + g] = v;
                 if (v > best) { best = v; bidx = (int)g; }   // rows visited in increasing g: ties keep the lower index
+            }
+        }
+        if constexpr (WITHIN) {
+            // `best` is this lane's maximum over its rows that exist: most tiles stop here.  Padded queries (q >= M) are zero rows
+            // and score exactly 0: never listed; rows clamped to N - 1 are skipped by g < N
+            if (best >= p.min_cos && q < p.M) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const long g = g0 + (e & 3) + 8 * (e >> 2) + 4 * fh;
+                    if (g < p.N && acc[e] >= p.min_cos) within_emit(p, q, (int)g, acc[e]);
+                }
             }
         }
         {   // combine the two half-waves (same query column)
@@ -130,6 +157,8 @@ __global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) {
         __builtin_amdgcn_s_barrier();
     }
 }
+__global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) { match_tiles<false>(p); }
+__global__ __launch_bounds__(256, 2) void match_within_kernel(MatchParams p) { match_tiles<true>(p); }
 
 // Top-1 only, M <= 512 queries (the streaming path: 320 faces per step): PERSISTENT workgroups of eight waves (one per CU;
 // a query tile in LDS serves 256 gallery rows) with the running winner of every query kept in REGISTERS across all the
@@ -147,17 +176,20 @@ __global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) {
 #define MT_MAXQT 16
 #define MT_NW 8            // waves per workgroup: one query tile in LDS serves 256 gallery rows
 static_assert(MT_MAXQT * MT_Q == FRP_MATCH_TOP1_MAX, "frp_internal.h: FRP_MATCH_TOP1_MAX");
-__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_kernel(MatchParams p) {
+template <bool WITHIN>
+__device__ __forceinline__ void match_top1_rounds(MatchParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char qs0[MT_Q * 1024];
     __shared__ __attribute__((aligned(16))) unsigned char qs1[MT_Q * 1024];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int fr = lane & 31, fh = lane >> 5;
     int nqt = p.Mpad / MT_Q;                                        // <= MT_MAXQT (launch_match)
+    int n_real = p.M;                                               // (read by the within epilogue only)
     if (p.n_dev) {                                                  // query count known on the device only: tiles that hold
         int n = *p.n_dev;                                           // real queries (p.M / p.Mpad are the capacity and the stride)
         n = n < 0 ? 0 : (n > p.M ? p.M : n);
         nqt = (n + MT_Q - 1) / MT_Q;
+        n_real = n;
     }
     const long nb = (p.N + 31) / 32;                                // 32-row gallery blocks
     const long wstride = (long)gridDim.x * MT_NW;
@@ -234,6 +266,15 @@ __global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_kernel(MatchParams p
                     for (int e = 0; e < 16; ++e)
                         if (acc[e] > best[qt]) { best[qt] = acc[e]; bidx[qt] = (int)(g0 + (e & 3) + 8 * (e >> 2) + 4 * fh); }
                 }
+                if constexpr (WITHIN) {
+                    // rows past N were set to -3 above (min_cos >= -2: launch_match), padded queries score exactly 0 and are
+                    // kept out by their index; a hit is rare, so most tiles stop at the comparison with the tile maximum
+                    if (tm >= p.min_cos && qt * MT_Q + fr < n_real) {
+#pragma unroll
+                        for (int e = 0; e < 16; ++e)
+                            if (acc[e] >= p.min_cos) within_emit(p, qt * MT_Q + fr, (int)(g0 + (e & 3) + 8 * (e >> 2) + 4 * fh), acc[e]);
+                    }
+                }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the next tile's DMA has had this tile to land
                 __builtin_amdgcn_s_barrier();
             }
@@ -268,6 +309,8 @@ __global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_kernel(MatchParams p
         p.part_idx[(long)blockIdx.x * p.Mpad + q] = bi;
     }
 }
+__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_kernel(MatchParams p) { match_top1_rounds<false>(p); }
+__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_within_kernel(MatchParams p) { match_top1_rounds<true>(p); }
 
 // one wave per query: reduce the per-workgroup partials
 __global__ __launch_bounds__(256) void match_reduce_kernel(MatchParams p) {
@@ -293,6 +336,31 @@ __global__ __launch_bounds__(256) void match_reduce_kernel(MatchParams p) {
     }
 }
 
+// one wave per query: the first min(count, cap) <= 64 entries of its hit list, one per lane, into (cosine descending, row
+// ascending) - the order of topk_rows_kernel and the oracle's stable argsort.  Rows are distinct, so the order is strict and a
+// lane's rank (the number of entries that precede its own) is its output position; the tail of the list is -1 / -2.0.
+__global__ __launch_bounds__(256) void within_sort_kernel(MatchParams p) {
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (q >= p.M) return;
+    int n = p.hit_count[q];
+    n = n < 0 ? 0 : (n > p.cap ? p.cap : n);
+    int32_t* idx = p.hit_idx + (long)q * p.cap;
+    float* cos = p.hit_cos + (long)q * p.cap;
+    const bool have = lane < n;
+    const int gi = have ? idx[lane] : 0x7fffffff;
+    const float gc = have ? cos[lane] : -__builtin_inff();
+    int rank = 0;
+    for (int j = 0; j < n; ++j) {                // n is the same in every lane of the wave
+        const float oc = __shfl(gc, j);
+        const int oi = __shfl(gi, j);
+        rank += (oc > gc || (oc == gc && oi < gi)) ? 1 : 0;
+    }
+    // (every lane has read its entry - the shuffles above depend on the loads - before any lane overwrites one)
+    if (have) { idx[rank] = gi; cos[rank] = gc; }
+    else if (lane < p.cap) { idx[lane] = -1; cos[lane] = -2.0f; }
+}
+
 static int match_cu_count(int dev) {
     static int cached[64] = {};
     if (dev < 0 || dev >= 64) return 0;
@@ -311,6 +379,9 @@ hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t st
         return hipErrorInvalidValue;
     if (p.Mpad % MT_Q != 0 || p.Mpad < p.M || p.n_wg != match_num_workgroups(p.N) || p.N > 0x7fffff00L)
         return hipErrorInvalidValue;
+    const bool within = p.hit_count != nullptr;
+    if (within && (!p.hit_idx || !p.hit_cos || p.cap < 1 || p.cap > FRP_WITHIN_MAX_CAP || !(p.min_cos >= -2.0f) || p.all_scores))
+        return hipErrorInvalidValue;
     MatchParams r = p;
     int dev = 0;
     if (p.n_dev && (p.all_scores || p.Mpad > MT_MAXQT * MT_Q || per_tile_only)) return hipErrorInvalidValue;   // top-1 kernel only
@@ -322,13 +393,18 @@ hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t st
         const int grid = (int)(want < (long)ncu ? want : (long)ncu);          // 8 waves x ~220 registers: one workgroup per CU
         if (ncu <= 0 || grid <= 0 || grid > p.n_wg) return hipErrorInvalidValue;
         r.n_wg = grid;
-        hipLaunchKernelGGL(match_top1_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p);
+        if (within) hipLaunchKernelGGL(match_top1_within_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p);
+        else hipLaunchKernelGGL(match_top1_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p);
     } else {
-        hipLaunchKernelGGL(match_kernel, dim3(p.n_wg), dim3(256), 0, stream, p);
+        if (within) hipLaunchKernelGGL(match_within_kernel, dim3(p.n_wg), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(match_kernel, dim3(p.n_wg), dim3(256), 0, stream, p);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(match_reduce_kernel, dim3((p.M + 3) / 4), dim3(256), 0, stream, r);
+    e = hipGetLastError();
+    if (e != hipSuccess || !within) return e;
+    hipLaunchKernelGGL(within_sort_kernel, dim3((p.M + 3) / 4), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -57,6 +57,35 @@ def cos_to_distance(cos) -> np.ndarray:
     return np.sqrt(np.maximum(0.0, 2.0 - 2.0 * np.asarray(cos, dtype=np.float64)))
 
 
+WITHIN_CAP = 64            # hit-list slots per face of the device radius match (frp.h: FRP_MAX_TOPK)
+
+
+def within_min_cos(tol: float) -> float:
+    """Cosine bound for the device radius match that keeps every row the host test `cos_to_distance(cos) <= tol` accepts:
+    d <= tol <=> cos >= 1 - tol^2 / 2 on unit rows; taken 1e-6 lower and rounded DOWN to float32 (the device compares in float32),
+    so rounding can only let extra rows through - the host re-applies `d <= tol` to what comes back.  -2 lists every row."""
+    m = 1.0 - 0.5 * float(tol) * float(tol) - 1e-6
+    if not m > -2.0:                      # tol >= sqrt(6) (or NaN): no cosine is excluded
+        return -2.0
+    return float(np.nextafter(np.float32(m), np.float32(-np.inf)))
+
+
+def within_to_matches(rows, cos, n_hits, tol: float, pos_of_row) -> List[Tuple[int, float]]:
+    """One query's device hit list (Engine.match_within / fetch_within: gallery rows, float32 cosines, the true hit count) ->
+    [(position, distance)] of the hits with distance <= tol, ordered by (distance, position): the order of a stable argsort
+    over distances laid out by position, which is what the full-row path does.  `pos_of_row[row]` is the position of the
+    row's name in the caller's target list, -1 for a row that is not among the targets."""
+    n = min(int(n_hits), len(rows))
+    if n <= 0:
+        return []
+    pos = np.asarray(pos_of_row)[np.asarray(rows[:n], dtype=np.int64)]
+    d = cos_to_distance(np.asarray(cos[:n]))
+    keep = (pos >= 0) & (d <= tol)
+    pos, d = pos[keep], d[keep]
+    order = np.lexsort((pos, d))          # last key first: by distance, ties by position
+    return list(zip(pos[order].tolist(), d[order].tolist()))
+
+
 def confidence_level(distance: float) -> str:                         # :486-492
     return "high" if distance < 0.4 else ("medium" if distance < 0.6 else "low")
 
@@ -130,6 +159,9 @@ class FaceService:
         self._metrics = {k: (0.0 if k.startswith("cumulative") else 0) for k in _METRIC_KEYS}
         self._comparison_history = deque(maxlen=5000)
         self._last_detection = threading.local()
+        # all_matches / batch_compare_faces on the device radius match (Engine.match_within, FLAG_WITHIN) where the engine has it;
+        # False: the full score rows on the host (the same results; also what a face with more than WITHIN_CAP hits falls back to)
+        self.use_within = True
         logger.info("FaceService initialized (model=%s, tolerance=%.3f)", self.model, self.tolerance)
 
     # ------------------------------------------------------------------ engine
@@ -471,6 +503,10 @@ class FaceService:
                     D = self._eng().gallery_distances(Q)[:, G.rows_of(targets)]
                 else:
                     Q = np.stack([np.asarray(q, dtype=np.float32).reshape(-1) for q in test_encodings])
+                    hits = self._within_hits(self._eng(), Q, targets, self.tolerance)
+                    if hits is not None:
+                        return [[{"target": targets[i], "match": True, "distance": d, "confidence": confidence_level(d)} for i, d in hl]
+                                for hl in hits]
                     D = cos_to_distance(self._eng().match_scores(Q)[:, G.rows_of(targets)])
         except Exception as e:
             logger.exception("Error in batch comparison: %s", e)
@@ -482,6 +518,28 @@ class FaceService:
             res.sort(key=lambda x: x["distance"])
             out.append(res)
         return out
+
+    def _pos_of_row(self, targets: List[str]) -> Optional[np.ndarray]:
+        """gallery row -> position in `targets` (-1: not a target); None when a name is listed twice (a row then has two positions)"""
+        G = self.ENCODINGS
+        rows = G.rows_of(targets)
+        pos = np.full(len(G), -1, dtype=np.int64)
+        pos[rows] = np.arange(len(rows))
+        return pos if int((pos >= 0).sum()) == len(rows) else None
+
+    def _within_hits(self, eng, Q: np.ndarray, targets: List[str], tol: float):
+        """per query [(position in targets, distance)] within tol by the device radius match (one gallery pass, hit lists only);
+        None: not on this path - switched off, an engine without it, or a query with more hits than a list holds (the
+        reference lists every target, so a list may not be cut: the caller takes the full-row path).  Gallery lock held."""
+        if not (self.use_within and hasattr(eng, "match_within")):
+            return None
+        pos_of_row = self._pos_of_row(targets)
+        if pos_of_row is None:
+            return None
+        idx, cos, n_hits = eng.match_within(Q, within_min_cos(tol), WITHIN_CAP)
+        if int(n_hits.max(initial=0)) > WITHIN_CAP:
+            return None
+        return [within_to_matches(idx[i], cos[i], n_hits[i], tol, pos_of_row) for i in range(len(Q))]
 
     def _get_confidence_level(self, distance: float) -> str:
         return confidence_level(distance)
@@ -576,6 +634,11 @@ class FaceService:
             have_gallery = len(G) > 0
             dt = DET_THRESH if det_thresh is None else det_thresh
             fl = 0 if have_gallery else native.FLAG_NO_MATCH
+            # all_matches on the device: the pass's own match kernel also lists every row within the bound (FLAG_WITHIN)
+            within = all_matches and have_gallery and self.use_within and hasattr(eng, "fetch_within")
+            if within:
+                eng.set_within(within_min_cos(tol), WITHIN_CAP)
+                fl |= native.FLAG_WITHIN
             if overlapped:
                 eng.process_resident(max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)       # asynchronous
                 nxt = take_next()
@@ -598,11 +661,18 @@ class FaceService:
                 out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
             n_gallery = len(G)
             row_names = {int(r): G.name_of_row(int(r)) for r in np.unique(out["match_idx"]) if r >= 0}
-            all_d = names = None
+            all_d = names = all_hits = None
             if all_matches and have_gallery and int(out["counts"].sum()) > 0:
-                Q = np.concatenate([out["emb"][b, :int(c)] for b, c in enumerate(out["counts"])])
                 names = G.names()
-                all_d = cos_to_distance(eng.match_scores(Q)[:, G.rows_of(names)])
+                if within:
+                    w_idx, w_cos, w_n = eng.fetch_within()
+                    live_w = np.arange(w_n.shape[1])[None, :] < np.asarray(out["counts"])[:, None]
+                    if int(w_n[live_w].max(initial=0)) <= WITHIN_CAP:       # else a list was cut: the full rows below
+                        pos_of_row = self._pos_of_row(names)
+                        all_hits = [within_to_matches(r, c, k, tol, pos_of_row) for r, c, k in zip(w_idx[live_w], w_cos[live_w], w_n[live_w])]
+                if all_hits is None:
+                    Q = np.concatenate([out["emb"][b, :int(c)] for b, c in enumerate(out["counts"])])
+                    all_d = cos_to_distance(eng.match_scores(Q)[:, G.rows_of(names)])
         def build():
             # One pass of array arithmetic for the whole batch (distance, bucket, threshold), ONE tolist() per field; the per-face
             # work left is building the dict (the reference builds N of them per face, camera.py:243-259).
@@ -631,7 +701,9 @@ class FaceService:
                             "confidence": conf_l[i] if h_ else None, "match": match_l[i]}
                     if all_matches:
                         hits = []
-                        if all_d is not None:
+                        if all_hits is not None:
+                            hits = [{"target": names[j], "distance": d, "confidence": confidence_level(d)} for j, d in all_hits[i]]
+                        elif all_d is not None:
                             dd = all_d[i]
                             order = np.argsort(dd, kind="stable")          # compare_faces sorts ascending (:432)
                             hits = [{"target": names[j], "distance": float(dd[j]), "confidence": confidence_level(float(dd[j]))}

@@ -24,7 +24,7 @@ EMB_DIM = 512
 CHIP = 112
 MAX_FACES_CAP = 128
 MAX_TOPK = 64
-FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH = 1, 2, 4
+FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN = 1, 2, 4, 8
 F32, F16, F64 = 0, 1, 2
 
 ABI_SYMBOLS = [
@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -199,6 +199,10 @@ def load_library() -> C.CDLL:
     lib.frp_embed_faces.argtypes = [vp, vp, i32, i32, i64, vp, i32, u32, vp]
     lib.frp_match.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.frp_match_scores.argtypes = [vp, vp, i32, vp, i64]
+    if hasattr(lib, "frp_match_within"):     # (an older build loaded through FRP_LIB as the A/B partner of tools/ab_bench.sh has none)
+        lib.frp_match_within.argtypes = [vp, vp, i32, f32, i32, vp, vp, vp]
+        lib.frp_set_within.argtypes = [vp, f32, i32]
+        lib.frp_fetch_within.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.frp_conv2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.frp_conv2d_f8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp]
     if hasattr(lib, "frp_kstep_lab"):            # the FRP_LAB build (libfrp_lab.so, include/frp_lab.h): tuning hooks
@@ -237,6 +241,8 @@ class Engine:
         # threads sharing one Engine take this lock around a whole sequence (`with eng.sequence(): ...`).  The
         # C side additionally checks every caller-sized buffer against the handle's state under its own mutex.
         self._seq = threading.RLock()
+        self._within_cap = 0             # set_within
+        self._last_shape = (0, 0)        # (B, K) of the last process / finish call (fetch_within)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -429,6 +435,7 @@ class Engine:
                                                _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]),
                                                _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
         self._det_batch = B
+        self._last_shape = (B, max_faces)
         return o
 
     def upload_frames(self, frames: np.ndarray):
@@ -459,6 +466,7 @@ class Engine:
     def process_resident(self, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4, flags: int = 0):
         self._chk(self._lib.frp_process_resident(self._h, max_faces, det_thresh, nms_iou, flags))
         self._last_k = max_faces
+        self._last_shape = (self._resident[0], max_faces)
 
     def synchronize(self):
         self._chk(self._lib.frp_synchronize(self._h))
@@ -511,6 +519,7 @@ class Engine:
         self._chk(self._lib.frp_finish_faces(self._h, B, _ptr(boxes), _ptr(kps), _ptr(scores), _ptr(counts), max_faces, flags,
                                              _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
         o.update(boxes=boxes, kps=kps, scores=scores, counts=counts)
+        self._last_shape = (B, max_faces)
         return o
 
     def process_frames_pyramid(self, frames, scales=(1.0, 0.5, 0.25), max_faces=10, det_thresh=0.5, nms_iou=0.4,
@@ -594,6 +603,35 @@ class Engine:
         cos = np.empty(shape, np.float32)
         self._chk(self._lib.frp_match(self._h, _ptr(q), q.shape[0], int(topk), _ptr(idx), _ptr(cos)))
         return idx, cos
+
+    def match_within(self, q: np.ndarray, min_cos: float, cap: int = 64):
+        """radius match -> (idx [M, cap], cos [M, cap], n_hits [M]): every gallery row whose cosine is >= min_cos, ordered by
+        (cosine desc, row asc); n_hits is the true count and may exceed cap (the list then holds the first cap of that order);
+        entries beyond min(n_hits, cap) hold -1 / -2.0"""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, EMB_DIM)
+        M, cap = q.shape[0], int(cap)
+        ok = 1 <= cap <= 64                     # (the library refuses the others: size the buffers for something harmless)
+        idx = np.empty((M, cap if ok else 1), np.int32)
+        cos = np.empty((M, cap if ok else 1), np.float32)
+        n_hits = np.empty((M,), np.int32)
+        self._chk(self._lib.frp_match_within(self._h, _ptr(q), M, float(min_cos), cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
+        return idx, cos, n_hits
+
+    def set_within(self, min_cos: float, cap: int = 64):
+        """bound and list size of the passes that run with FLAG_WITHIN from now on"""
+        self._chk(self._lib.frp_set_within(self._h, float(min_cos), int(cap)))
+        self._within_cap = int(cap)
+
+    def fetch_within(self):
+        """hit lists of the last pass that ran with FLAG_WITHIN (process_frames / process_resident / finish_faces)
+        -> (idx [B, K, cap], cos [B, K, cap], n_hits [B, K]); slots without a face have n_hits 0"""
+        B, K = self._last_shape
+        cap = self._within_cap
+        idx = np.empty((B, K, cap), np.int32)
+        cos = np.empty((B, K, cap), np.float32)
+        n_hits = np.empty((B, K), np.int32)
+        self._chk(self._lib.frp_fetch_within(self._h, B, K, cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
+        return idx, cos, n_hits
 
     def match_scores(self, q: np.ndarray) -> np.ndarray:
         """all cosines [M, N].  The output is sized from gallery_size(); the library re-checks that size under

@@ -52,6 +52,9 @@ typedef enum frp_dtype { FRP_F32 = 0, FRP_F16 = 1, FRP_F64 = 2 } frp_dtype;
 #define FRP_FLAG_RGB 2u        /* input frames are RGB (face_recognition.load_image_file order,
                                   face_service.py:139) instead of BGR (cv2 capture order, camera.py:205) */
 #define FRP_FLAG_NO_MATCH 4u   /* skip the gallery match (encode_face path, face_service.py:87-219) */
+#define FRP_FLAG_WITHIN 8u     /* besides the top-1: per face the list of ALL gallery rows whose cosine is at or above the bound of
+                                  frp_set_within, from the same gallery pass (frp_fetch_within; the caller's filter loop over every
+                                  target, camera.py:246-256) */
 
 typedef struct frp_handle frp_handle;
 
@@ -171,6 +174,21 @@ int frp_process_resident(frp_handle* h, int32_t max_faces, float det_thresh, flo
 int frp_fetch_results(frp_handle* h, int32_t B, int32_t max_faces, float* boxes, float* kps, float* scores, int32_t* counts,
                       float* emb, int32_t* match_idx, float* match_cos);
 int frp_synchronize(frp_handle* h);
+/* Radius match of the streaming passes (FRP_FLAG_WITHIN of frp_process_frames / frp_process_resident / frp_finish_faces): which
+ * enrolled rows lie within tolerance of a face, not only which one is nearest
+ * -> the filter `d <= tolerance` over all targets (camera.py:246-256; d <= tol <=> cos >= 1 - tol^2 / 2 on unit rows).
+ * frp_set_within stores the bound (min_cos >= -2, not NaN) and the list size (1 <= cap <= FRP_MAX_TOPK) for the flagged passes
+ * that follow; a flagged pass without it fails with FRP_ERR_INVALID.  The pass launches the same match kernel it would have
+ * launched, with an epilogue that lists (row, cosine) of every score >= min_cos; top-1, embeddings and everything else are
+ * unchanged, and without the flag nothing is.
+ * frp_fetch_within (B, max_faces checked as in frp_fetch_results, cap against the pass): per face slot n_hits [B*K] = the TRUE
+ * number of rows at or above the bound - it may exceed cap - and idx / cos [B*K x cap] = the first min(n_hits, cap) of them by
+ * (cosine descending, row ascending), -1 / -2.0 beyond; slots k >= counts[b], and every slot of a pass that did not match (no
+ * gallery, FRP_FLAG_NO_MATCH), give n_hits 0.  A cosine equals the frp_match_scores entry of that embedding's fp16 query bit for
+ * bit.  The list of a face with n_hits > cap is rebuilt here, from the embeddings the pass left on the device (one score row per
+ * such face + the top-k selection); FRP_ERR_INVALID if a later match / embed call on the handle has replaced them. */
+int frp_set_within(frp_handle* h, float min_cos, int32_t cap);
+int frp_fetch_within(frp_handle* h, int32_t B, int32_t max_faces, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits);
 
 /* Overlapped ingest for streaming callers (the camera loop keeps producing frames while the previous
  * batch is on the GPU, camera.py:277-305): the NEXT batch is copied host -> device on a private copy
@@ -279,6 +297,14 @@ int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* i
 /* n_cols: the gallery size cos_all was sized for; FRP_ERR_INVALID (nothing written) when the gallery has another size
  * by the time the call holds the handle -- re-read frp_gallery_size and retry */
 int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, int64_t n_cols);
+/* radius match: every gallery row whose cosine with a query is >= min_cos (min_cos >= -2, not NaN; -2 lists every row), M host
+ * queries normalised on upload as in frp_match, 1 <= cap <= FRP_MAX_TOPK.  n_hits [M] = the true number of such rows (may exceed
+ * cap); idx / cos [M x cap] = the first min(n_hits, cap) of them by (cosine descending, row ascending) - what frp_match(topk = cap)
+ * lists, cut at the bound - and -1 / -2.0 beyond; cosines bit-identical to frp_match_scores.  One gallery pass with the hit lists
+ * written by the match kernel's epilogue (M <= 512: the persistent kernel; above: the per-tile kernel, in chunks of 65536
+ * queries): no M x N matrix exists unless a query has more than cap hits - its list, and only its, is rebuilt from its score row.
+ * -> compare_faces' `d <= tolerance` over all targets, batch_compare_faces (face_service.py:409-432,448-481) */
+int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits);
 
 /* one convolution through the MFMA kernel on host tensors (kernel parity tests):
  * x [N,H,W,Cin] fp16, w [Cout][k][k][Cin] fp16, bias fp32 [Cout] or [9][Cout], out fp16 or fp32

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Gallery match (top-1), wall time per frp_match call and identity of results: persistent running-best kernel vs the per-tile kernel
-(FRP_MATCH_V1=1), N = 100k / 1M rows, M = 32 / 320 / 512 queries."""
+(FRP_MATCH_V1=1), N = 100k / 1M rows, M = 32 / 320 / 512 queries.
+    tools/match_probe.py within [N ...]
+the radius match instead: wall ms per call, copies included, of frp_match_within (cap 64, the bound of tolerance 0.6; every query
+is a noisy copy of a gallery row, so it has about one hit) against frp_match(topk=64), frp_match_scores and the plain top-1, M = 320,
+N = 100k / 1M; under `rocprofv3 --kernel-trace --stats` the same run gives match_top1_kernel against match_top1_within_kernel."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,6 +12,41 @@ import frp_amd_loader  # noqa
 from frp_amd import native
 eng = native.Engine(0)
 rng = np.random.default_rng(0)
+
+
+def within_mode(sizes):
+    from frp_amd.face_service import within_min_cos
+    M, cap, bound = 320, 64, within_min_cos(0.6)
+
+    def wall(fn, reps):
+        fn()
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        return (time.perf_counter() - t) / reps * 1e3
+
+    for N in sizes:
+        G = rng.standard_normal((N, 512)).astype(np.float32)
+        eng.gallery_set(G)
+        q = G[rng.integers(0, N, size=M)] + 0.3 * rng.standard_normal((M, 512)).astype(np.float32)
+        del G
+        idx, cos, n = eng.match_within(q, bound, cap)
+        i1, c1 = eng.match(q)
+        ik, ck = eng.match(q, topk=cap)
+        cut = ck >= np.float32(bound)
+        same = (np.array_equal(idx[:, 0], i1) and np.array_equal(n, cut.sum(1)) and np.array_equal(idx[cut], ik[cut])
+                and np.array_equal(cos[cut], ck[cut]))
+        t_w = wall(lambda: eng.match_within(q, bound, cap), 20)
+        t_1 = wall(lambda: eng.match(q), 20)
+        t_k = wall(lambda: eng.match(q, topk=cap), 3)
+        t_s = wall(lambda: eng.match_scores(q), 3)
+        print(f"N={N:8d} M={M}: match_within {t_w:8.3f} ms | top-1 {t_1:8.3f} ms | match(topk=64) {t_k:9.2f} ms | match_scores {t_s:9.2f} ms"
+              f" | hits per query {n.mean():.2f} (max {n.max()}) | lists equal top-k cut at the bound: {same}")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "within":
+    within_mode([int(a) for a in sys.argv[2:]] or [100_000, 1_000_000])
+    sys.exit(0)
 for N in (100_000, 1_000_000):
     eng.gallery_set(rng.standard_normal((N, 512)).astype(np.float32))
     for M in (32, 320, 512):

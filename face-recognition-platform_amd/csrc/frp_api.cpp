@@ -1166,6 +1166,9 @@ int frp_debug_det_prefix(frp_handle* h, int32_t n_ops, void* out_f16, int64_t ou
     const Switches sw = read_switches();
     const bool fused = h->det.det_stem && !sw.no_fused_stem;
     if (!fused) return fail(h, FRP_ERR_INVALID, "prefix runs need the fused stem");
+    // (the condition of run_det_stems) both stems in one launch: op 0's map stays in LDS, its buffer is never written
+    if (n_ops == 1 && h->det.det_stem12 && (Hc % 4) == 0 && (Wc % 4) == 0 && !sw.no_fused_stem12)
+        return fail(h, FRP_ERR_INVALID, "op 0 has no tensor while both stems run as one kernel: set FRP_NO_FUSED_STEM12 to read the stem1 map");
     FRPCHK(plan_net(h, h->det, B, Hc, Wc, fused));
     StemParams sp{};
     sp.frames = h->det_scaled ? (const uint8_t*)h->scaled.p : (const uint8_t*)h->frames.p;

@@ -236,6 +236,7 @@ class Engine:
             raise FrpError(rc, "frp_create failed (no usable HIP device?)")
         self._h = h
         self.device = device
+        self.max_batch = max_batch
         self.max_faces = max_faces
         # Multi-call sequences (upload -> process -> fetch, the pyramid) leave state on the handle between calls:
         # threads sharing one Engine take this lock around a whole sequence (`with eng.sequence(): ...`).  The
@@ -550,7 +551,9 @@ class Engine:
         return outs
 
     def det_prefix(self, n_ops: int) -> np.ndarray:
-        """diagnostic: the detector on the RESIDENT frames up to and including op n_ops - 1; that op's output [B,h,w,c] fp16"""
+        """diagnostic: the detector on the RESIDENT frames up to and including op n_ops - 1; that op's output [B,h,w,c] fp16.
+        By default both stems run as one kernel and the stem1 map (op 0) never reaches memory: n_ops == 1 raises FrpError
+        unless FRP_NO_FUSED_STEM12 is set (stem1 and stem2 as two launches); n_ops == 2 is the fused kernel's output."""
         th, tw, tc = C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(self._lib.frp_debug_det_prefix(self._h, n_ops, None, 0, C.byref(th), C.byref(tw), C.byref(tc)))
         a = np.empty((self._resident[0], th.value, tw.value, tc.value), dtype=np.float16)

@@ -271,7 +271,9 @@ int frp_finish_faces(frp_handle* h, int32_t B, const float* boxes, const float* 
 int frp_get_head_map(frp_handle* h, int32_t level, void* out_f16, int64_t out_bytes, int32_t* hl, int32_t* wl);
 /* diagnostic: runs the detector program on the resident frames up to and including op n_ops - 1 and returns that op's
  * output [B, th, tw, tc] fp16 (out_f16 NULL: dimensions only, the prefix still runs).  Buffers are shared between tensors,
- * so an inner tensor is only readable from a prefix run (tools/det_bisect.py: per-layer determinism / parity bisection) */
+ * so an inner tensor is only readable from a prefix run (tools/det_bisect.py: per-layer determinism / parity bisection).
+ * While the two stems run as one kernel (the default) op 0's map never reaches memory: n_ops == 1 fails with
+ * FRP_ERR_INVALID unless FRP_NO_FUSED_STEM12 is set; n_ops == 2 is then the output of that one kernel */
 int frp_debug_det_prefix(frp_handle* h, int32_t n_ops, void* out_f16, int64_t out_bytes, int32_t* th, int32_t* tw, int32_t* tc);
 /* diagnostic: enable != 0 - every later detector pass hashes each op's output right behind the op (one 64-bit slot per op,
  * 64 slots); out64 != NULL receives the hashes of the last pass (tools/det_hash_bisect.py: which op of a FULL pass differed) */

@@ -68,6 +68,8 @@ struct frp_handle {
     int last_within_cap = 0;          // list size of the last pass, 0: it ran without FRP_FLAG_WITHIN
     bool last_within_lists = false;   // ... and it matched (faces and a gallery): the buffers above hold its lists
     bool q16_of_pass = false;         // q16 still holds that pass's queries (a list that overflowed is rebuilt from them at fetch time)
+    // frp_face_quality: rectangles + tile prefix in, per-tile partials + per-rectangle sums out (its own: the last pass's results stay)
+    frp::DevBuf quality_in, quality_out;
     int32_t* h_nfaces = nullptr;   // pinned
     unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
     size_t pin_cap = 0;
@@ -156,7 +158,7 @@ public:
     DevBuf take() { return std::exchange(b, DevBuf()); }
 };
 
-// What the files of entry points share (frp_api.cpp, gallery_api.cpp, kernel_api.cpp)
+// What the files of entry points share (frp_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp)
 FRP_LOCAL void settle_events(frp_handle* h, bool stream_is_idle);   // frp_api.cpp
 // host fp32 rows -> unit fp16 rows at dst (device), via the scratch buffer (gallery_api.cpp)
 FRP_LOCAL int upload_rows_normalized(frp_handle* h, const float* rows, int64_t n, _Float16* dst);

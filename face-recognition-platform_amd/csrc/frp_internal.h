@@ -301,6 +301,25 @@ hipError_t launch_gallery_normalize(const float* in, _Float16* out, long N, int 
 hipError_t launch_gallery_widen(const _Float16* in, double* out, long N, int D, hipStream_t stream);
 hipError_t launch_gallery_distances(const double* rows, long N, const double* q, int M, double* out, hipStream_t stream);
 
+// Face quality (quality_kernels.hip; frp.h: frp_face_quality): per rectangle of the resident u8 frames the four integer sums behind
+// FaceService.assess_face_quality's blur and lighting scores - S1 = sum g, S2 = sum g^2, L1 = sum lap, L2 = sum lap^2 over the crop,
+// g the cv2 fixed-point grey value, lap the 5-point Laplacian of g with BORDER_REFLECT_101 at the edges of the CROP.
+// One workgroup per QUALITY_TILE_H x QUALITY_TILE_W tile of a crop (mirrored in native.py: the tests size their crops from them).
+#define QUALITY_TILE_H 32
+#define QUALITY_TILE_W 64
+struct QualityParams {
+    const uint8_t* frames;        // [B,H,W,3] u8, tightly packed, 4-byte aligned base
+    long long total_bytes;        // B*H*W*3: no byte at or beyond it is read
+    int B, H, W;
+    int rgb_in;                   // frames are RGB instead of BGR
+    const int32_t* rects;         // [n][5]: frame, top, right, bottom, left (validated by the caller: inside the frame, not empty)
+    const int32_t* tile_prefix;   // [n + 1]: tiles of the rectangles before r; [n] = n_tiles
+    int n, n_tiles;
+    long long* partials;          // [n_tiles][4]: every slot is written by its tile's workgroup (no memset, no atomics)
+    long long* sums;              // out [n][4]: S1, S2, L1, L2
+};
+hipError_t launch_face_quality(const QualityParams& p, hipStream_t stream);
+
 #ifdef FRP_LAB
 hipError_t launch_mfma_peak(const _Float16* src, float* dst, int blocks, int iters, hipStream_t stream);
 // the conv k-step's MFMA + ds_read_b128 mix without memory traffic or barriers (reads per 4 MFMAs: 4, 3 or 2)

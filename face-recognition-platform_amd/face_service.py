@@ -21,6 +21,7 @@ backend/app/services/async_task_manager.py:125): process_frames / process_frame.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import os
@@ -222,7 +223,36 @@ class FaceService:
         flags = (native.FLAG_RGB if rgb else 0) | (0 if match else native.FLAG_NO_MATCH)
         return self._eng().process_frames(images, max_faces=max_faces, det_thresh=DET_THRESH, nms_iou=NMS_IOU, flags=flags)
 
-    def encode_face(self, image_path_or_array, return_locations: bool = False) -> Dict[str, Any]:
+    @staticmethod
+    def _sequence_of(eng):
+        """the engine's multi-call lock (a pass and the face_quality call on its still-resident frames are one sequence)"""
+        seq = getattr(eng, "sequence", None)
+        return seq() if seq is not None else contextlib.nullcontext()
+
+    def _quality_of(self, eng, frames, faces: List[Tuple[int, Tuple[int, int, int, int]]], rgb: bool) -> List[Dict[str, Any]]:
+        """assess_face_quality for `faces` = [(frame index, (top, right, bottom, left))] of the batch `frames` ([B,H,W,3] in RGB or
+        BGR order, or a JpegBatch) that is RESIDENT on `eng`: one Engine.face_quality call for all rectangles the device takes;
+        the host method on the caller's pixels for the others (a location that clipping left empty) and for an engine without
+        face_quality (the tests' FakeEngine).  In the order of `faces`."""
+        if not faces:
+            return []
+        H, W = frames.hw if isinstance(frames, JpegBatch) else frames.shape[1:3]
+        pixels = [None if isinstance(frames, JpegBatch) else frames]
+
+        def on_host(b, loc):
+            if pixels[0] is None:
+                pixels[0] = frames.decode()
+            img = pixels[0][b]
+            return self.assess_face_quality(img if rgb else img[..., ::-1], loc)
+
+        on_dev = [hasattr(eng, "face_quality") and 0 <= loc[0] < loc[2] <= H and 0 <= loc[3] < loc[1] <= W for _, loc in faces]
+        sums = iter(eng.face_quality([(b, *loc) for (b, loc), ok in zip(faces, on_dev) if ok], rgb=rgb)) if any(on_dev) else None
+        return [self.quality_from_sums((H, W, 3), loc, (loc[2] - loc[0]) * (loc[1] - loc[3]), next(sums)) if ok else on_host(b, loc)
+                for (b, loc), ok in zip(faces, on_dev)]
+
+    def encode_face(self, image_path_or_array, return_locations: bool = False, return_quality: bool = False) -> Dict[str, Any]:
+        """return_quality: a "quality" list parallel to "encodings" - assess_face_quality of every face at its location, the pixel
+        half computed on the device from the frames the pass left resident (routes/face.py:199-217 calls the two back to back)"""
         start = time.time()
 
         def failure(msg):
@@ -233,13 +263,15 @@ class FaceService:
             is_path = isinstance(image_path_or_array, str)
             if is_path:
                 cached = self._get_from_cache(image_path_or_array)
-                if cached:
+                if cached and (not return_quality or "quality" in cached):     # (an entry without quality: a miss when it is asked for)
                     self._bump("cache_hits")
                     result = {"success": True, "face_count": len(cached.get("encodings", [])),
                               "encodings": cached.get("encodings", []), "message": "Retrieved from cache",
                               "cached": True, "processing_time": time.time() - start}
                     if return_locations:
                         result["locations"] = cached.get("locations", [])
+                    if return_quality:
+                        result["quality"] = cached["quality"]
                     return result
                 self._bump("cache_misses")
                 image = load_image_file(image_path_or_array)
@@ -249,44 +281,56 @@ class FaceService:
                 return failure("Invalid input type")
 
             t_enc = time.time()
-            out = self._detect_and_embed(image[None] if image.ndim == 3 else image)
-            n = int(out["counts"][0])
-            if n == 0:
-                self._bump("failed_encodings")
-                return failure("No faces detected in image")
-            h, w = image.shape[:2]
-            locations = [box_to_location(out["boxes"][0, k], h, w) for k in range(n)]
+            batch = image[None] if image.ndim == 3 else image
+            with (self._sequence_of(self._eng()) if return_quality else contextlib.nullcontext()):
+                out = self._detect_and_embed(batch)
+                n = int(out["counts"][0])
+                if n == 0:
+                    self._bump("failed_encodings")
+                    return failure("No faces detected in image")
+                h, w = image.shape[:2]
+                locations = [box_to_location(out["boxes"][0, k], h, w) for k in range(n)]
+                quality = self._quality_of(self._eng(), batch, [(0, loc) for loc in locations], rgb=True) if return_quality else None
             encodings = [out["emb"][0, k].astype(np.float64) for k in range(n)]
             enc_time = time.time() - t_enc
             with self._metrics_lock:
                 self._metrics["total_encodings"] += n
                 self._metrics["cumulative_encoding_time"] += enc_time
             if is_path:
-                self._add_to_cache(image_path_or_array, {"encodings": encodings, "locations": locations})
+                entry = {"encodings": encodings, "locations": locations}
+                if return_quality:
+                    entry["quality"] = quality
+                self._add_to_cache(image_path_or_array, entry)
             total = time.time() - start
             logger.info("Encoded %d face(s) in %.3fs (io+proc=%.3fs)", n, total, enc_time)
             result = {"success": True, "face_count": n, "encodings": encodings,
                       "message": f"Successfully encoded {n} face(s)", "processing_time": total}
             if return_locations:
                 result["locations"] = locations
+            if return_quality:
+                result["quality"] = quality
             return result
         except Exception as e:  # never raise across the API (:209-219)
             logger.exception("Error encoding face: %s", e)
             self._bump("failed_encodings")
             return failure(f"Error encoding face: {str(e)}")
 
-    def batch_encode_faces(self, image_paths: List[str], max_workers: int = BATCH_WORKERS) -> List[Dict[str, Any]]:
+    def batch_encode_faces(self, image_paths: List[str], max_workers: int = BATCH_WORKERS, return_quality: bool = False) -> List[Dict[str, Any]]:
         """:224-246.  The reference fans paths out over a 4-thread pool (one detect+embed per image,
         results in completion order); here uncached images of equal size are stacked into ONE device
-        batch (chunks of `max_workers * 8` frames) and results come back in input order."""
+        batch (chunks of `max_workers * 8` frames) and results come back in input order.
+        return_quality: as encode_face - one device quality call per chunk, on its still-resident frames."""
         start = time.time()
         results: List[Optional[Dict[str, Any]]] = [None] * len(image_paths)
         pending: Dict[Tuple[int, ...], List[Tuple[int, np.ndarray]]] = {}
         for i, path in enumerate(image_paths):
             try:
                 cached = self._get_from_cache(path) if isinstance(path, str) else None
+                if cached is not None and return_quality and "quality" not in cached:
+                    cached = None                                # an entry without quality: a miss when it is asked for
                 if cached is not None or not isinstance(path, str):
-                    results[i] = self.encode_face(path)          # cache hit / invalid input: the single-image path
+                    # cache hit / invalid input: the single-image path
+                    results[i] = self.encode_face(path, return_quality=True) if return_quality else self.encode_face(path)
                     continue
                 self._bump("cache_misses")
                 img = load_image_file(path)
@@ -302,7 +346,13 @@ class FaceService:
                 part = items[c0:c0 + chunk]
                 t0 = time.time()
                 try:
-                    out = self._detect_and_embed(np.stack([im for _, im in part]))
+                    stack = np.stack([im for _, im in part])
+                    with (self._sequence_of(self._eng()) if return_quality else contextlib.nullcontext()):
+                        out = self._detect_and_embed(stack)
+                        if return_quality:
+                            h, w = shape[:2]
+                            faces = [(bi, box_to_location(out["boxes"][bi, k], h, w)) for bi in range(len(part)) for k in range(int(out["counts"][bi]))]
+                            quality = iter(self._quality_of(self._eng(), stack, faces, rgb=True))
                 except Exception as e:
                     logger.exception("Batch encode failed: %s", e)
                     for i, _ in part:
@@ -324,9 +374,14 @@ class FaceService:
                     with self._metrics_lock:
                         self._metrics["total_encodings"] += n
                         self._metrics["cumulative_encoding_time"] += dt / len(part)
-                    self._add_to_cache(image_paths[i], {"encodings": encs, "locations": locs})
+                    entry = {"encodings": encs, "locations": locs}
+                    if return_quality:
+                        entry["quality"] = [next(quality) for _ in range(n)]
+                    self._add_to_cache(image_paths[i], entry)
                     results[i] = {"success": True, "face_count": n, "encodings": encs,
                                   "message": f"Successfully encoded {n} face(s)", "processing_time": time.time() - start}
+                    if return_quality:
+                        results[i]["quality"] = entry["quality"]
         for i, path in enumerate(image_paths):
             results[i]["image_path"] = path
         return results  # type: ignore[return-value]
@@ -345,9 +400,43 @@ class FaceService:
         lap = g[:-2, 1:-1] + g[2:, 1:-1] + g[1:-1, :-2] + g[1:-1, 2:] - 4.0 * g[1:-1, 1:-1]
         return float(lap.var())
 
+    @staticmethod
+    def _pixel_scores(lap_var: float, mean: float, std: float) -> Tuple[float, float]:
+        """(blur_score, lighting_score) from the Laplacian's variance and the grey crop's mean and standard deviation (:283-297)"""
+        blur_score = min(100.0, (lap_var / 500.0) * 100.0)
+        brightness = 100.0 - abs(mean - 128.0) / 128.0 * 100.0
+        contrast = min(100.0, (std / 50.0) * 100.0)
+        return blur_score, (brightness + contrast) / 2.0
+
     def assess_face_quality(self, image, face_location: Tuple[int, int, int, int]) -> Dict[str, Any]:
         top, right, bottom, left = face_location
-        height, width = image.shape[:2]
+        try:
+            crop = image[top:bottom, left:right]
+            if crop.size == 0 or crop.ndim != 3:
+                raise ValueError("empty crop")
+            gray = self._gray(crop)
+            blur_score, lighting_score = self._pixel_scores(self._laplacian_var(gray), float(np.mean(gray)), float(np.std(gray)))
+        except Exception as err:
+            logger.debug("Blur/lighting analysis error: %s", err)
+            blur_score = lighting_score = 50.0
+        return self._quality_result(image.shape, face_location, blur_score, lighting_score)
+
+    def quality_from_sums(self, shape, face_location: Tuple[int, int, int, int], n_pixels: int, sums) -> Dict[str, Any]:
+        """assess_face_quality with the pixel half done on the device (Engine.face_quality): `sums` = S1, S2, L1, L2 = sum g,
+        sum g^2, sum lap, sum lap^2 over the N = n_pixels grey values of the crop of an image of `shape`.  Variances as
+        (N*S2 - S1^2) / N^2 with the numerator in Python integers (N*L2 passes 2^63 for a 4K crop) and ONE float64 division each:
+        correctly rounded, where numpy's float64 passes over the crop are good to ~1e-13 relative."""
+        n = int(n_pixels)
+        s1, s2, l1, l2 = (int(v) for v in sums)
+        var_g = (n * s2 - s1 * s1) / (n * n)
+        var_lap = (n * l2 - l1 * l1) / (n * n)
+        blur_score, lighting_score = self._pixel_scores(var_lap, s1 / n, float(np.sqrt(var_g)))
+        return self._quality_result(shape, face_location, blur_score, lighting_score)
+
+    def _quality_result(self, shape, face_location, blur_score: float, lighting_score: float) -> Dict[str, Any]:
+        """the geometry terms (:257-275), the weighted score, the issue list and the history entry of one assessment"""
+        top, right, bottom, left = face_location
+        height, width = shape[:2]
         fw, fh = max(1, right - left), max(1, bottom - top)
         size_ratio = float(fw * fh) / float(width * height) if width * height > 0 else 0.0
         size_score = min(100.0, (size_ratio / 0.25) * 100.0)
@@ -356,18 +445,6 @@ class FaceService:
         position_score = max(0.0, (1.0 - off) * 100.0)
         aspect_ratio = min(fw, fh) / max(fw, fh)
         aspect_score = aspect_ratio * 100.0
-        try:
-            crop = image[top:bottom, left:right]
-            if crop.size == 0 or crop.ndim != 3:
-                raise ValueError("empty crop")
-            gray = self._gray(crop)
-            blur_score = min(100.0, (self._laplacian_var(gray) / 500.0) * 100.0)
-            brightness = 100.0 - abs(float(np.mean(gray)) - 128.0) / 128.0 * 100.0
-            contrast = min(100.0, (float(np.std(gray)) / 50.0) * 100.0)
-            lighting_score = (brightness + contrast) / 2.0
-        except Exception as err:
-            logger.debug("Blur/lighting analysis error: %s", err)
-            blur_score = lighting_score = 50.0
         overall = size_score * 0.25 + position_score * 0.2 + aspect_score * 0.2 + blur_score * 0.2 + lighting_score * 0.15
         issues: List[str] = []
         if size_ratio < 0.05:
@@ -605,16 +682,20 @@ class FaceService:
 
     # ------------------------------------------------------------------ streaming entry points (new)
     def process_frames(self, frames_bgr: np.ndarray, max_faces: int = 10, threshold: Optional[float] = None,
-                       det_thresh: Optional[float] = None, all_matches: bool = False) -> List[List[Dict[str, Any]]]:
+                       det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False) -> List[List[Dict[str, Any]]]:
         """The live-loop body of routes/camera.py:225-259 for a batch of BGR frames, with the
         per-face compare + filter reduced to a fused device top-1: per frame a list of
         {bbox, kps, score, embedding, target, distance, cosine, confidence, match}.
         all_matches=True additionally lists EVERY enrolled target within both the service
         tolerance and `threshold` (the reference's exact loop semantics, camera.py:246-256: a face
-        can hit several near-duplicate identities), ascending by distance, under "matches"."""
-        return self._process_frames_on(self._eng(), self.ENCODINGS.locked(), frames_bgr, max_faces, threshold, det_thresh, all_matches)
+        can hit several near-duplicate identities), ascending by distance, under "matches".
+        quality=True adds "quality" to every face: assess_face_quality (the reference's enrolment gate, routes/face.py:217) of the
+        frame at box_to_location(bbox), the pixel half from the batch's still-resident frames in one device call."""
+        return self._process_frames_on(self._eng(), self.ENCODINGS.locked(), frames_bgr, max_faces, threshold, det_thresh, all_matches,
+                                       quality=quality)
 
-    def _process_frames_on(self, eng, guard, frames_bgr, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None):
+    def _process_frames_on(self, eng, guard, frames_bgr, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None,
+                           quality=False):
         """`take_next` / `staged` (process_stream on a real engine): the overlapped-ingest form - this batch goes to the device
         through the engine's staging buffer (already there when the previous call staged it), the batch the lane will get
         next is claimed and its upload started on the copy stream while this batch's kernels run."""
@@ -649,16 +730,20 @@ class FaceService:
                 if idle is not None:
                     idle()                                             # the PREVIOUS batch's result dicts, under this batch's kernels
                 out = eng.fetch_results()                              # waits for the pass
+                qual = self._stream_quality(eng, frames_bgr, out) if quality else None      # (before the lane's next swap_frames)
             elif isinstance(frames_bgr, JpegBatch) and hasattr(eng, "upload_jpeg_async"):
                 with eng.sequence():
                     self._stage_on(eng, frames_bgr)
                     eng.swap_frames()
                     eng.process_resident(max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
                     out = eng.fetch_results()
+                    qual = self._stream_quality(eng, frames_bgr, out) if quality else None
             else:
                 if isinstance(frames_bgr, JpegBatch):
                     frames_bgr = frames_bgr.decode()                   # an engine without the device decoder (tests' FakeEngine)
-                out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
+                with (self._sequence_of(eng) if quality else contextlib.nullcontext()):
+                    out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
+                    qual = self._stream_quality(eng, frames_bgr, out) if quality else None
             n_gallery = len(G)
             row_names = {int(r): G.name_of_row(int(r)) for r in np.unique(out["match_idx"]) if r >= 0}
             all_d = names = all_hits = None
@@ -709,6 +794,8 @@ class FaceService:
                             hits = [{"target": names[j], "distance": float(dd[j]), "confidence": confidence_level(float(dd[j]))}
                                     for j in order if dd[j] <= tol]
                         face["matches"] = hits
+                    if qual is not None:
+                        face["quality"] = qual[i]
                     faces.append(face)
                     f_idx += 1
                 result.append(faces)
@@ -721,6 +808,14 @@ class FaceService:
         # process_stream: the dicts of this batch are built by the lane's thread while its NEXT batch is on the device
         # (lanes.Deferred); everything they need was taken above, under the guard.
         return lanes.Deferred(build) if overlapped else build()
+
+    def _stream_quality(self, eng, frames_bgr, out) -> List[Dict[str, Any]]:
+        """quality dicts of a fetched batch's faces, frame by frame (the order of the face dicts), from the frames still resident on `eng`"""
+        frames = frames_bgr if isinstance(frames_bgr, JpegBatch) or frames_bgr.ndim == 4 else frames_bgr[None]
+        H, W = frames.hw if isinstance(frames, JpegBatch) else frames.shape[1:3]
+        K = out["boxes"].shape[1]
+        faces = [(b, box_to_location(out["boxes"][b, k], H, W)) for b, c in enumerate(out["counts"]) for k in range(min(int(c), K))]
+        return self._quality_of(eng, frames, faces, rgb=False)
 
     @staticmethod
     def _stage_on(eng, batch) -> None:
@@ -737,7 +832,7 @@ class FaceService:
         eng.upload_frames_async(batch)
 
     def process_stream(self, batches, max_faces: int = 10, threshold: Optional[float] = None,
-                       det_thresh: Optional[float] = None, all_matches: bool = False):
+                       det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False):
         """process_frames for a stream of batches with TWO batches in flight on the GPU (lanes.py: a second handle and
         host thread; +7...13 % faces/s).  Yields one process_frames result per batch, in order.  Enrolment and deletion
         may run concurrently: they wait for the batches inside their device call and reach both gallery copies under
@@ -750,13 +845,13 @@ class FaceService:
         def on(eng):
             if not all(hasattr(eng, m) for m in ("upload_frames_async", "swap_frames", "process_resident", "fetch_results", "sequence")):
                 return lambda frames, take_next: self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold,
-                                                                         det_thresh, all_matches)
+                                                                         det_thresh, all_matches, quality=quality)
             staged = {}                         # which batch sits in this lane's staging buffer
 
             def fn(frames, take_next):
                 with eng.sequence():            # upload -> swap -> process -> fetch of one lane is one uninterrupted sequence
                     return self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold, det_thresh, all_matches,
-                                                   take_next, staged)
+                                                   take_next, staged, quality=quality)
             return fn
         return lanes.run_ordered(batches, [on(e) for e in engines], prefetch=True)
 

@@ -26,6 +26,7 @@ MAX_FACES_CAP = 128
 MAX_TOPK = 64
 FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN = 1, 2, 4, 8
 F32, F16, F64 = 0, 1, 2
+QUALITY_TILE_H, QUALITY_TILE_W = 32, 64      # csrc/frp_internal.h: one workgroup of the face-quality kernel covers this much of a crop
 
 ABI_SYMBOLS = [
     "frp_create", "frp_destroy", "frp_last_error", "frp_version", "frp_load_weights",
@@ -36,7 +37,7 @@ ABI_SYMBOLS = [
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -203,6 +204,8 @@ def load_library() -> C.CDLL:
         lib.frp_match_within.argtypes = [vp, vp, i32, f32, i32, vp, vp, vp]
         lib.frp_set_within.argtypes = [vp, f32, i32]
         lib.frp_fetch_within.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    if hasattr(lib, "frp_face_quality"):     # (as above: an older A/B partner build has none)
+        lib.frp_face_quality.argtypes = [vp, vp, i32, u32, vp]
     lib.frp_conv2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.frp_conv2d_f8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp]
     if hasattr(lib, "frp_kstep_lab"):            # the FRP_LAB build (libfrp_lab.so, include/frp_lab.h): tuning hooks
@@ -635,6 +638,15 @@ class Engine:
         n_hits = np.empty((B, K), np.int32)
         self._chk(self._lib.frp_fetch_within(self._h, B, K, cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
         return idx, cos, n_hits
+
+    def face_quality(self, rects, rgb: bool = False) -> np.ndarray:
+        """blur / lighting sums of rectangles (frame, top, right, bottom, left) of the RESIDENT frames, as uploaded (rgb: their
+        channel order) -> int64 [n, 4]: S1 = sum g, S2 = sum g^2, L1 = sum lap, L2 = sum lap^2 over each crop (frp.h: frp_face_quality;
+        face_service.FaceService.quality_from_sums turns them into the reference's scores).  The last pass's results stay fetchable."""
+        r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 5)
+        sums = np.zeros((r.shape[0], 4), np.int64)
+        self._chk(self._lib.frp_face_quality(self._h, _ptr(r), r.shape[0], FLAG_RGB if rgb else 0, _ptr(sums)))
+        return sums
 
     def match_scores(self, q: np.ndarray) -> np.ndarray:
         """all cosines [M, N].  The output is sized from gallery_size(); the library re-checks that size under

@@ -308,6 +308,19 @@ int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, i
  * -> compare_faces' `d <= tolerance` over all targets, batch_compare_faces (face_service.py:409-432,448-481) */
 int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits);
 
+/* Face quality: the blur and lighting sums of rectangles of the RESIDENT frames (those of the last frp_upload_frames / frp_swap_frames /
+ * frp_process_frames), as uploaded.
+ * replaces the pixel half of FaceService.assess_face_quality (face_service.py:276-297): the grey conversion, cv2.Laplacian and the
+ * mean / variance passes over the crop.  rects [n*5] = frame, top, right, bottom, left (the css order of face_locations); per
+ * rectangle sums [n*4] = S1, S2, L1, L2 = sum g, sum g^2, sum lap, sum lap^2 over the crop's pixels, with
+ * g = (R*4899 + G*9617 + B*1868 + 8192) >> 14 (R and B by FRP_FLAG_RGB, the only flag allowed) and lap = up + down + left + right -
+ * 4*centre on g, BORDER_REFLECT_101 at the edges of the crop.  Exact integers: var(g) = (N*S2 - S1^2) / N^2 for the N pixels of the
+ * crop, the Laplacian's variance alike.  Queued on the handle's stream behind a pending pass; waits; the handle's last results stay
+ * fetchable (frp_fetch_results, frp_fetch_within).  n == 0: FRP_OK, nothing launched.  FRP_ERR_INVALID - nothing launched, nothing
+ * written, the message names the rectangle - without resident frames, for n < 0, another flag, or a rectangle outside
+ * 0 <= frame < B, 0 <= top < bottom <= H, 0 <= left < right <= W. */
+int frp_face_quality(frp_handle* h, const int32_t* rects, int32_t n, uint32_t flags, int64_t* sums);
+
 /* one convolution through the MFMA kernel on host tensors (kernel parity tests):
  * x [N,H,W,Cin] fp16, w [Cout][k][k][Cin] fp16, bias fp32 [Cout] or [9][Cout], out fp16 or fp32
  * flags (0: what the engine would launch for this shape, as set by the environment switches of INTEGRATION.md):

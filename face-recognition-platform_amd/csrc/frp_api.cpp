@@ -1,6 +1,6 @@
 // C-ABI host runtime of libfrp.so: handle, weight/program blob, the detect -> align -> embed -> match
-// pipeline on one HIP stream, per-stage HIP-event timing.  The gallery snapshots and the multi-GPU
-// all-gather: gallery_api.cpp; the stand-alone kernel entry points and the lab hooks: kernel_api.cpp.
+// pipeline on one HIP stream, per-stage HIP-event timing.  Frame ingest: ingest_api.cpp; the gallery snapshots and the
+// multi-GPU all-gather: gallery_api.cpp; the stand-alone kernel entry points and the lab hooks: kernel_api.cpp.
 // Interface and the reference call sites each entry point replaces: include/frp.h.
 #include <hip/hip_runtime.h>
 
@@ -12,14 +12,11 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include <thread>
-#include <atomic>
 
 #include "frp.h"
 #include "frp_blob.h"
 #include "frp_internal.h"
 #include "frp_handle.h"
-#include "jpeg_host.h"
 
 using namespace frp;
 
@@ -52,25 +49,6 @@ float logit_threshold(float t) {
     if (!(t > 0.f)) return -INFINITY;
     if (t >= 1.f) return INFINITY;
     return (float)std::log((double)t / (1.0 - (double)t));
-}
-
-void rec(frp_handle* h, int which) {
-    if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream);
-}
-
-int upload_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride) {
-    if (!bgr || B <= 0 || H <= 0 || W <= 0 || row_stride < (int64_t)W * 3) return fail(h, FRP_ERR_INVALID, "bad frame arguments");
-    if (B > 1024) return fail(h, FRP_ERR_INVALID, "batch too large (max 1024 frames per call)");
-    FRPCHK(ensure(h, h->frames, (size_t)B * H * W * 3));
-    rec(h, EV_START);
-    HIPCHK(h, hipMemcpy2DAsync(h->frames.p, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, (size_t)B * H,
-                               hipMemcpyHostToDevice, h->stream));
-    rec(h, EV_H2D);
-    h->rB = B; h->rH = H; h->rW = W;
-    h->dH = H; h->dW = W; h->det_scaled = false;
-    h->canvas_h = round_up(H, 32);
-    h->canvas_w = round_up(W, 32);
-    return FRP_OK;
 }
 
 // choose the detector source: the resident frames (Hs,Ws == frame size) or a bilinear resize of them
@@ -614,18 +592,7 @@ int frp_create(int device, const frp_config* cfg, frp_handle** out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->n_cu = prop.multiProcessorCount;
     }
-    // The copy stream gets its own PRIORITY class: the runtime multiplexes the streams of one class onto a few hardware
-    // queues (4 by default), and next to torch's and RCCL's streams in the process the staged upload shared a queue with
-    // the compute stream and serialised behind the step's kernels (overlapped loop 18.7-20.6 instead of 14.7 ms per
-    // step; GPU_MAX_HW_QUEUES=8 restored it).  A stream of another priority class is not pooled with them.
-    if (ok) {
-        int lo = 0, hi = 0;
-        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (e == hipSuccess && hi != lo) ok = hipStreamCreateWithPriority(&h->copy_stream, hipStreamNonBlocking, hi) == hipSuccess;
-        else ok = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) == hipSuccess;
-    }
-    ok = ok && hipEventCreateWithFlags(&h->ev_next_ready, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&h->ev_next_free, hipEventDisableTiming) == hipSuccess;
+    ok = ok && init_ingest(h);
     if (!ok) { frp_destroy(h); return FRP_ERR_HIP; }
     h->ctr.struct_size = sizeof(frp_counters);
     *out = h;
@@ -636,27 +603,19 @@ void frp_destroy(frp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+    if (h->in.copy_stream) (void)hipStreamSynchronize(h->in.copy_stream);
     dist_shutdown(h);
     drop_graphs(h);
     for (DevBuf& b : h->det.bufs) release(b);
     for (DevBuf& b : h->emb.bufs) release(b);
-    DevBuf* all[] = {&h->wdata, &h->frames, &h->frames_next, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
+    DevBuf* all[] = {&h->wdata, &h->frames, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
                      &h->q16, &h->part_cos, &h->part_idx, &h->best_cos, &h->best_idx, &h->hit_cnt, &h->hit_idx, &h->hit_cos, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
-                     &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->jpeg_coef, &h->jpeg_planes, &h->jpeg_scan, &h->jpeg_err, &h->det_hashes,
-                     &h->quality_in, &h->quality_out};
+                     &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->det_hashes, &h->quality_in, &h->quality_out};
     for (DevBuf* b : all) release(*b);
     for (int i = 0; i < EV_COUNT; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-    for (int i = 0; i < 2; ++i) {
-        if (h->jpeg_pin[i]) (void)hipHostFree(h->jpeg_pin[i]);
-        if (h->ev_jpeg_h2d[i]) (void)hipEventDestroy(h->ev_jpeg_h2d[i]);
-    }
     if (h->h_nfaces) (void)hipHostFree(h->h_nfaces);
     if (h->pin_stage) (void)hipHostFree(h->pin_stage);
-    for (void* p : h->pinned) (void)hipHostFree(p);
-    if (h->ev_next_ready) (void)hipEventDestroy(h->ev_next_ready);
-    if (h->ev_next_free) (void)hipEventDestroy(h->ev_next_free);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
+    release_ingest(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -687,294 +646,11 @@ int frp_load_weights(frp_handle* h, const void* blob, size_t bytes) {
 }
 
 // ---------------------------------------------------------------- hot path
-int frp_upload_frames(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, int32_t W, int64_t row_stride) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h);
-    FRPCHK(upload_frames(h, bgr, B, H, W, row_stride));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return FRP_OK;
-}
-
-void* frp_host_alloc(frp_handle* h, size_t bytes) {
-    if (!h || bytes == 0) return nullptr;
-    Guard g(h);
-    void* p = nullptr;
-    if (hipSetDevice(h->device) != hipSuccess || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-        fail(h, FRP_ERR_OOM, "hipHostMalloc failed");
-        return nullptr;
-    }
-    h->pinned.push_back(p);
-    return p;
-}
-
-void frp_host_free(frp_handle* h, void* p) {
-    if (!h || !p) return;
-    Guard g(h);
-    for (size_t i = 0; i < h->pinned.size(); ++i)
-        if (h->pinned[i] == p) {
-            (void)hipStreamSynchronize(h->copy_stream);
-            (void)hipHostFree(p);
-            h->pinned.erase(h->pinned.begin() + (long)i);
-            return;
-        }
-}
-
-int frp_upload_frames_async(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, int32_t W, int64_t row_stride) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h, false);      // copy stream only: does not re-record the stage events, so a pending pass is not drained
-                            // (with the timers on, settling here made the upload of batch t+1 wait for batch t)
-    if (!bgr || B <= 0 || H <= 0 || W <= 0 || row_stride < (int64_t)W * 3) return fail(h, FRP_ERR_INVALID, "bad frame arguments");
-    if (B > 1024) return fail(h, FRP_ERR_INVALID, "batch too large (max 1024 frames per call)");
-    const size_t need = (size_t)B * H * W * 3;
-    if (need > h->frames_next.cap || !h->frames_next.p) {
-        // growing the staging buffer: nothing may still be copying into / computing from it
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        FRPCHK(ensure(h, h->frames_next, need));
-    }
-    // the staging buffer was the resident one until the last swap: wait for the work enqueued before it
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_next_free, 0));
-    HIPCHK(h, hipMemcpy2DAsync(h->frames_next.p, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, (size_t)B * H,
-                               hipMemcpyHostToDevice, h->copy_stream));
-    HIPCHK(h, hipEventRecord(h->ev_next_ready, h->copy_stream));
-    h->nB = B; h->nH = H; h->nW = W;
-    h->next_valid = true;
-    return FRP_OK;
-}
-
-int frp_jpeg_info_get(const uint8_t* data, size_t size, frp_jpeg_info* info) {
-    if (!data || !info) return FRP_ERR_INVALID;
-    return jpeg_info(data, size, info, nullptr);
-}
-
-int frp_jpeg_coefficients(const uint8_t* data, size_t size, int16_t* coef, size_t coef_elems, uint16_t* qtab, frp_jpeg_info* info) {
-    if (!data || !coef || !qtab) return FRP_ERR_INVALID;
-    return jpeg_decode_coefficients(data, size, coef, coef_elems, qtab, info, nullptr);
-}
-
-// Device entropy decode of a batch whose frames all carry restart intervals (round 5; jpeg_kernels.hip: jpeg_huffman_kernel): the host
-// parses headers and finds the RSTn markers (one memchr pass), the COMPRESSED scans go to the device (~0.5 MB per 1080p frame instead of
-// 6.3 MB of coefficients), one thread per interval decodes, and the host waits only for the per-image error flags (a corrupt stream
-// must be reported by this call, as on the host path) before the pixel kernels are queued.  -> FRP_OK, an error, or 1 = "not this
-// batch" (not switched on, no restart intervals, too few of them to fill a wave): the caller takes the host decoder.
-namespace {
-int upload_jpeg_device(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, const frp_jpeg_info& I, int turn,
-                       JpegParams& p, size_t total_host_layout, size_t q_off) {
-    // When: one thread per interval decodes 32 x 1080p frames in 17.8 ms at one interval per MCU row (120 MCUs), 4.5 ms at 30 MCUs,
-    // 1.25 ms at 8 (profiles/r5/jpeg_device_entropy.txt) - the time goes with the LENGTH of an interval, and 16 host threads take
-    // 9-12 ms: by default the device decodes streams whose intervals are at most 32 MCUs and the host the others.
-    // FRP_JPEG_DEVICE_HUFFMAN=1 (read once): the device whatever the interval (takes the entropy decode off the host's cores; at
-    // one interval per row it is slower than the pipeline consumes frames), =0: never.
-    const int mode = process_switches().jpeg_device_huffman;
-    if (mode < 0 || I.restart_interval <= 0 || (mode == 0 && I.restart_interval > 32)) return 1;
-    const long mcus = (long)I.mcus_x * I.mcus_y;
-    const long n_int = (mcus + I.restart_interval - 1) / I.restart_interval;
-    if ((long)B * n_int < 64 || n_int > 0x7fffff) return 1;
-    std::vector<JpegDevicePlan> plans((size_t)B);
-    std::vector<JpegHuffTableDev> tabs((size_t)B * 6);
-    for (int i = 0; i < B; ++i) {
-        std::string e;
-        if (!jpegs[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": null image");
-        const int rc = jpeg_plan_device_decode(jpegs[i], sizes[i], plans[i], tabs.data() + (size_t)i * 6, &e);
-        if (rc != FRP_OK) {
-            if (plans[i].info.restart_interval <= 0 && plans[i].info.width > 0) return 1;          // a frame without intervals: host path for the batch
-            return fail(h, rc, "JPEG " + std::to_string(i) + ": " + e);
-        }
-        const frp_jpeg_info& Ii = plans[i].info;
-        if (Ii.width != I.width || Ii.height != I.height || Ii.components != I.components || Ii.h_samp[0] != I.h_samp[0] || Ii.v_samp[0] != I.v_samp[0])
-            return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": geometry differs from image 0 (one batch = one frame size and sampling)");
-        if (Ii.restart_interval != I.restart_interval) return 1;
-    }
-    // staging layout: scans | interval offsets | tables | quantisation tables | error flags (read back)
-    std::vector<size_t> soff((size_t)B + 1, 0);
-    for (int i = 0; i < B; ++i) soff[i + 1] = (soff[i] + plans[i].scan_bytes + 15) & ~(size_t)15;
-    if (soff[B] >= 0xfffffff0u) return 1;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_int = up(soff[B]), o_tab = up(o_int + (size_t)B * (n_int + 1) * 4), o_q = up(o_tab + (size_t)B * 6 * sizeof(JpegHuffTableDev)),
-                 o_err = up(o_q + (size_t)B * 192 * 2), stage_total = o_err + (size_t)B * 4;
-    if (h->jpeg_h2d_pending[turn]) {
-        HIPCHK(h, hipEventSynchronize(h->ev_jpeg_h2d[turn]));
-        h->jpeg_h2d_pending[turn] = false;
-    }
-    if (stage_total > h->jpeg_pin_cap[turn]) {
-        if (h->jpeg_pin[turn]) { (void)hipHostFree(h->jpeg_pin[turn]); h->jpeg_pin[turn] = nullptr; h->jpeg_pin_cap[turn] = 0; }
-        if (hipHostMalloc(&h->jpeg_pin[turn], stage_total, hipHostMallocDefault) != hipSuccess) return fail(h, FRP_ERR_OOM, "hipHostMalloc (JPEG staging) failed");
-        h->jpeg_pin_cap[turn] = stage_total;
-    }
-    if (!h->ev_jpeg_h2d[turn]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_jpeg_h2d[turn], hipEventDisableTiming));
-    char* st = (char*)h->jpeg_pin[turn];
-    uint32_t* io = (uint32_t*)(st + o_int);
-    for (int i = 0; i < B; ++i) {
-        memcpy(st + soff[i], plans[i].scan, plans[i].scan_bytes);
-        for (long k = 0; k <= n_int; ++k) io[(size_t)i * (n_int + 1) + k] = (uint32_t)(soff[i] + plans[i].int_off[(size_t)k]);
-        memcpy(st + o_q + (size_t)i * 384, plans[i].qtab, 384);
-    }
-    memcpy(st + o_tab, tabs.data(), tabs.size() * sizeof(JpegHuffTableDev));
-    const size_t need = (size_t)B * I.height * I.width * 3;
-    if (need > h->frames_next.cap || !h->frames_next.p || total_host_layout > h->jpeg_coef.cap || (size_t)B * p.plane_img > h->jpeg_planes.cap ||
-        o_err > h->jpeg_scan.cap || (size_t)B * 4 > h->jpeg_err.cap) {
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));     // growing buffers: nothing may still be copying into / computing from them
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        FRPCHK(ensure(h, h->frames_next, need));
-        FRPCHK(ensure(h, h->jpeg_coef, total_host_layout));
-        FRPCHK(ensure(h, h->jpeg_planes, (size_t)B * p.plane_img));
-        FRPCHK(ensure(h, h->jpeg_scan, o_err));
-        FRPCHK(ensure(h, h->jpeg_err, (size_t)B * 4));
-    }
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_next_free, 0));
-    HIPCHK(h, hipMemcpyAsync(h->jpeg_scan.p, st, o_err, hipMemcpyHostToDevice, h->copy_stream));
-    HIPCHK(h, hipMemsetAsync(h->jpeg_coef.p, 0, q_off, h->copy_stream));
-    HIPCHK(h, hipMemcpyAsync((char*)h->jpeg_coef.p + q_off, (char*)h->jpeg_scan.p + o_q, (size_t)B * 384, hipMemcpyDeviceToDevice, h->copy_stream));
-    HIPCHK(h, hipMemsetAsync(h->jpeg_err.p, 0, (size_t)B * 4, h->copy_stream));
-    JpegHuffParams hp{};
-    hp.scan = (const uint8_t*)h->jpeg_scan.p;
-    hp.int_off = (const uint32_t*)((const char*)h->jpeg_scan.p + o_int);
-    hp.tables = (const JpegHuffTableDev*)((const char*)h->jpeg_scan.p + o_tab);
-    hp.coef = (int16_t*)h->jpeg_coef.p;
-    hp.err = (int32_t*)h->jpeg_err.p;
-    hp.coef_per_image = (long)jpeg_coef_elems(I);
-    hp.B = B; hp.n_int = (int)n_int; hp.ri = I.restart_interval;
-    hp.mcus_x = I.mcus_x; hp.mcus_y = I.mcus_y; hp.components = I.components;
-    for (int c = 0; c < 3; ++c) { hp.hs[c] = I.h_samp[c]; hp.vs[c] = I.v_samp[c]; hp.bx[c] = p.bx[c]; hp.comp_off[c] = p.plane_off[c]; }
-    hipError_t e = launch_jpeg_huffman(hp, h->copy_stream);
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg huffman: ") + hipGetErrorString(e));
-    HIPCHK(h, hipMemcpyAsync(st + o_err, h->jpeg_err.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->copy_stream));
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));          // the flags decide this call's return value (and the staging buffer is free again)
-    const int32_t* flags = (const int32_t*)(st + o_err);
-    for (int i = 0; i < B; ++i)
-        if (flags[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": corrupt or truncated entropy-coded data");
-    p.coef = (const int16_t*)h->jpeg_coef.p;
-    p.qtab = (const uint16_t*)((const char*)h->jpeg_coef.p + q_off);
-    p.planes = (uint8_t*)h->jpeg_planes.p;
-    p.frames = (uint8_t*)h->frames_next.p;
-    e = launch_jpeg_decode(p, h->copy_stream);
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg decode: ") + hipGetErrorString(e));
-    HIPCHK(h, hipEventRecord(h->ev_next_ready, h->copy_stream));
-    h->nB = B; h->nH = I.height; h->nW = I.width;
-    h->next_valid = true;
-    h->ctr_jpeg_device_batches += 1;
-    return FRP_OK;
-}
-}  // namespace
-
-int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h, false);      // copy stream only (as frp_upload_frames_async)
-    if (!jpegs || !sizes || B <= 0 || B > 1024) return fail(h, FRP_ERR_INVALID, "bad JPEG batch arguments");
-    frp_jpeg_info I{};
-    std::string err;
-    if (!jpegs[0] || jpeg_info(jpegs[0], sizes[0], &I, &err) != FRP_OK) return fail(h, FRP_ERR_INVALID, "JPEG 0: " + err);
-    const size_t ce = jpeg_coef_elems(I);
-    // staging: [B] coefficients (int16) then [B][3][64] tables (uint16), 16-byte aligned parts
-    const size_t coef_bytes = (size_t)B * ce * 2, q_off = (coef_bytes + 255) & ~(size_t)255, total = q_off + (size_t)B * 3 * 64 * 2;
-    const int turn = h->jpeg_turn;
-    h->jpeg_turn ^= 1;
-    JpegParams p{};
-    p.B = B; p.W = I.width; p.H = I.height; p.components = I.components;
-    p.hs = I.h_samp[0]; p.vs = I.v_samp[0];
-    p.cw = (I.width + p.hs - 1) / p.hs;
-    p.ch = (I.height + p.vs - 1) / p.vs;
-    long off = 0;
-    for (int c = 0; c < I.components; ++c) {
-        p.bx[c] = I.mcus_x * I.h_samp[c];
-        p.by[c] = I.mcus_y * I.v_samp[c];
-        p.blocks_per_image += p.bx[c] * p.by[c];
-        p.plane_off[c] = off;
-        off += (long)p.bx[c] * p.by[c] * 64;
-    }
-    p.plane_img = off;
-    {   // restart-interval streams: entropy decode on the device
-        const int dr = upload_jpeg_device(h, jpegs, sizes, B, I, turn, p, total, q_off);
-        if (dr != 1) return dr;
-    }
-    if (h->jpeg_h2d_pending[turn]) {                 // the copy of the batch before the previous one read this staging buffer
-        HIPCHK(h, hipEventSynchronize(h->ev_jpeg_h2d[turn]));
-        h->jpeg_h2d_pending[turn] = false;
-    }
-    if (total > h->jpeg_pin_cap[turn]) {
-        if (h->jpeg_pin[turn]) { (void)hipHostFree(h->jpeg_pin[turn]); h->jpeg_pin[turn] = nullptr; h->jpeg_pin_cap[turn] = 0; }
-        if (hipHostMalloc(&h->jpeg_pin[turn], total, hipHostMallocDefault) != hipSuccess) return fail(h, FRP_ERR_OOM, "hipHostMalloc (JPEG staging) failed");
-        h->jpeg_pin_cap[turn] = total;
-    }
-    if (!h->ev_jpeg_h2d[turn]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_jpeg_h2d[turn], hipEventDisableTiming));
-    int16_t* coef = (int16_t*)h->jpeg_pin[turn];
-    uint16_t* qtab = (uint16_t*)((char*)h->jpeg_pin[turn] + q_off);
-    // entropy decoding: one image per task on host threads (the images are independent; within one the bit stream is serial)
-    std::vector<int> rcs((size_t)B, FRP_OK);
-    std::vector<std::string> errs((size_t)B);
-    {
-        const int nth = std::max(1, std::min<int>(B, (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()))));
-        std::atomic<int> next{0};
-        auto work = [&]() {
-            for (int i = next.fetch_add(1); i < B; i = next.fetch_add(1)) {
-                frp_jpeg_info Ii{};
-                if (!jpegs[i]) { rcs[i] = FRP_ERR_INVALID; errs[i] = "null image"; continue; }
-                rcs[i] = jpeg_decode_coefficients(jpegs[i], sizes[i], coef + (size_t)i * ce, ce, qtab + (size_t)i * 192, &Ii, &errs[i]);
-                if (rcs[i] == FRP_OK && (Ii.width != I.width || Ii.height != I.height || Ii.components != I.components ||
-                                         Ii.h_samp[0] != I.h_samp[0] || Ii.v_samp[0] != I.v_samp[0])) {
-                    rcs[i] = FRP_ERR_INVALID;
-                    errs[i] = "geometry differs from image 0 (one batch = one frame size and sampling)";
-                }
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < nth; ++t) th.emplace_back(work);
-        work();
-        for (auto& t : th) t.join();
-    }
-    for (int i = 0; i < B; ++i)
-        if (rcs[i] != FRP_OK) return fail(h, rcs[i], "JPEG " + std::to_string(i) + ": " + errs[i]);
-    const size_t need = (size_t)B * I.height * I.width * 3;
-    if (need > h->frames_next.cap || !h->frames_next.p || total > h->jpeg_coef.cap || (size_t)B * off > h->jpeg_planes.cap) {
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));     // growing buffers: nothing may still be copying into / computing from them
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        FRPCHK(ensure(h, h->frames_next, need));
-        FRPCHK(ensure(h, h->jpeg_coef, total));
-        FRPCHK(ensure(h, h->jpeg_planes, (size_t)B * off));
-    }
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->ev_next_free, 0));     // the staging frame buffer was the resident one until the last swap
-    HIPCHK(h, hipMemcpyAsync(h->jpeg_coef.p, h->jpeg_pin[turn], total, hipMemcpyHostToDevice, h->copy_stream));
-    HIPCHK(h, hipEventRecord(h->ev_jpeg_h2d[turn], h->copy_stream));
-    h->jpeg_h2d_pending[turn] = true;
-    p.coef = (const int16_t*)h->jpeg_coef.p;
-    p.qtab = (const uint16_t*)((const char*)h->jpeg_coef.p + q_off);
-    p.planes = (uint8_t*)h->jpeg_planes.p;
-    p.frames = (uint8_t*)h->frames_next.p;
-    hipError_t e = launch_jpeg_decode(p, h->copy_stream);
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg decode: ") + hipGetErrorString(e));
-    HIPCHK(h, hipEventRecord(h->ev_next_ready, h->copy_stream));
-    h->nB = B; h->nH = I.height; h->nW = I.width;
-    h->next_valid = true;
-    return FRP_OK;
-}
-
 // diagnostic: network passes replayed from a captured hipGraph (run_net)
 int64_t frp_debug_graph_replays(frp_handle* h) {
     if (!h) return -1;
     Guard g(h);
     return h->graph_replays;
-}
-
-// diagnostic: how many frp_upload_jpeg_async batches had their entropy decode on the device (restart-interval streams)
-int64_t frp_debug_jpeg_device_batches(frp_handle* h) {
-    if (!h) return -1;
-    Guard g(h, false);
-    return h->ctr_jpeg_device_batches;
-}
-
-int frp_swap_frames(frp_handle* h) {
-    if (!h) return FRP_ERR_INVALID;
-    Guard g(h, false);      // enqueues a wait + an event on the compute stream; the stage events stay as recorded
-    if (!h->next_valid) return fail(h, FRP_ERR_INVALID, "no staged frames (call frp_upload_frames_async)");
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_next_ready, 0));     // compute waits for the staged copy
-    std::swap(h->frames, h->frames_next);
-    HIPCHK(h, hipEventRecord(h->ev_next_free, h->stream));            // ... and the old resident buffer is free after
-    h->rB = h->nB; h->rH = h->nH; h->rW = h->nW;                       // everything enqueued so far
-    h->dH = h->rH; h->dW = h->rW; h->det_scaled = false;
-    h->canvas_h = round_up(h->rH, 32);
-    h->canvas_w = round_up(h->rW, 32);
-    h->next_valid = false;
-    return FRP_OK;
 }
 
 int frp_process_resident(frp_handle* h, int32_t max_faces, float det_thresh, float nms_iou, uint32_t flags) {

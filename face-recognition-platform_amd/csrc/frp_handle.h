@@ -15,6 +15,26 @@
 
 enum { EV_START = 0, EV_H2D, EV_PRE, EV_DET, EV_DEC, EV_ALIGN, EV_EMB, EV_L2, EV_MATCH, EV_D2H, EV_COUNT };
 
+struct Ingest {   // frame ingest (ingest_api.cpp: nothing else reads or writes these; init_ingest / release_ingest make and free them)
+    // overlapped ingest: the NEXT batch is copied on its own stream while the current one is processed
+    frp::DevBuf frames_next;
+    int nB = 0, nH = 0, nW = 0;
+    bool next_valid = false;
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_next_ready = nullptr, ev_next_free = nullptr;
+    std::vector<void*> pinned;       // frp_host_alloc blocks, freed with the handle
+    // JPEG ingest (frp_upload_jpeg_async): page-locked coefficient staging, device coefficients / tables / sample planes
+    // (two staging buffers in turn: the host decodes batch t+1 while the copy of batch t still reads the other one)
+    void* jpeg_pin[2] = {nullptr, nullptr};
+    size_t jpeg_pin_cap[2] = {0, 0};
+    int jpeg_turn = 0;
+    frp::DevBuf jpeg_coef, jpeg_planes;
+    int64_t ctr_jpeg_device_batches = 0;   // batches whose entropy decode ran on the device (frp_debug_jpeg_device_batches)
+    frp::DevBuf jpeg_scan, jpeg_err;      // device entropy decode (restart-interval streams): compressed scans + interval offsets + tables; per-image error flags
+    hipEvent_t ev_jpeg_h2d[2] = {nullptr, nullptr};     // the copy out of jpeg_pin[i] has finished
+    bool jpeg_h2d_pending[2] = {false, false};
+};
+
 struct frp_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -30,13 +50,7 @@ struct frp_handle {
     frp::DevBuf frames;
     int rB = 0, rH = 0, rW = 0;
     int n_cu = 256;                   // compute units of the device (queried once at create)
-    // overlapped ingest: the NEXT batch is copied on its own stream while the current one is processed
-    frp::DevBuf frames_next;
-    int nB = 0, nH = 0, nW = 0;
-    bool next_valid = false;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_next_ready = nullptr, ev_next_free = nullptr;
-    std::vector<void*> pinned;       // frp_host_alloc blocks, freed with the handle
+    Ingest in;                        // the staged NEXT batch, the copy stream, the JPEG staging
     // detector source: the resident frames, or a resized copy of them (pyramid scales)
     frp::DevBuf scaled;
     int dH = 0, dW = 0;              // dims of the detector source
@@ -77,16 +91,6 @@ struct frp_handle {
     frp::DevBuf gallery;
     int64_t g_rows = 0;
     frp::DevBuf g_reserved;               // frp_gallery_reserve: filled by the caller, swapped in by frp_gallery_commit
-    // JPEG ingest (frp_upload_jpeg_async): page-locked coefficient staging, device coefficients / tables / sample planes
-    // (two staging buffers in turn: the host decodes batch t+1 while the copy of batch t still reads the other one)
-    void* jpeg_pin[2] = {nullptr, nullptr};
-    size_t jpeg_pin_cap[2] = {0, 0};
-    int jpeg_turn = 0;
-    frp::DevBuf jpeg_coef, jpeg_planes;
-    int64_t ctr_jpeg_device_batches = 0;   // batches whose entropy decode ran on the device (frp_debug_jpeg_device_batches)
-    frp::DevBuf jpeg_scan, jpeg_err;      // device entropy decode (restart-interval streams): compressed scans + interval offsets + tables; per-image error flags
-    hipEvent_t ev_jpeg_h2d[2] = {nullptr, nullptr};     // the copy out of jpeg_pin[i] has finished
-    bool jpeg_h2d_pending[2] = {false, false};
     // exact compat rows (frp_gallery_exact): float64 [g_rows x 512] as enrolled, next to the unit fp16 snapshot
     bool g_exact = false;
     frp::DevBuf gx, gx_q, gx_out;
@@ -158,8 +162,13 @@ public:
     DevBuf take() { return std::exchange(b, DevBuf()); }
 };
 
-// What the files of entry points share (frp_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp)
+// What the files of entry points share (frp_api.cpp, ingest_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp)
 FRP_LOCAL void settle_events(frp_handle* h, bool stream_is_idle);   // frp_api.cpp
+inline void rec(frp_handle* h, int which) { if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream); }   // a stage event (timers on)
+FRP_LOCAL bool init_ingest(frp_handle* h);                          // ingest_api.cpp: the copy stream and its events (frp_create)
+FRP_LOCAL void release_ingest(frp_handle* h);                       // ... and everything `in` holds (frp_destroy)
+FRP_LOCAL int upload_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride);   // into the resident buffer, stream-ordered
+FRP_LOCAL void set_resident(frp_handle* h, int B, int H, int W);    // B frames of H x W are resident now; the detector reads them at full size
 // host fp32 rows -> unit fp16 rows at dst (device), via the scratch buffer (gallery_api.cpp)
 FRP_LOCAL int upload_rows_normalized(frp_handle* h, const float* rows, int64_t n, _Float16* dst);
 FRP_LOCAL void dist_shutdown(frp_handle* h);                        // gallery_api.cpp: drops the handle's RCCL communicator, if any

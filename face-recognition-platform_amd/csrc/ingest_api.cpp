@@ -1,0 +1,330 @@
+// Frame ingest of libfrp.so: the blocking upload into the resident buffer, the staged upload of the NEXT batch on the copy stream (raw
+// frames out of pageable or page-locked memory; JPEG stills with the entropy decode on host threads or on the device), the swap that
+// makes the staged batch resident.  Everything here works on h->in (frp_handle.h: struct Ingest); the pass that reads the resident
+// frames: frp_api.cpp.  Sizes and offsets of the JPEG buffers: jpeg_host.cpp (jpeg_batch_layout, jpeg_device_stage_layout).
+#include <atomic>
+#include <cstring>
+#include <initializer_list>
+#include <thread>
+
+#include "frp_handle.h"
+#include "jpeg_host.h"
+
+using namespace frp;
+
+bool frp::init_ingest(frp_handle* h) {
+    Ingest& in = h->in;
+    // The copy stream gets its own PRIORITY class: the runtime multiplexes the streams of one class onto a few hardware
+    // queues (4 by default), and next to torch's and RCCL's streams in the process the staged upload shared a queue with
+    // the compute stream and serialised behind the step's kernels (overlapped loop 18.7-20.6 instead of 14.7 ms per
+    // step; GPU_MAX_HW_QUEUES=8 restored it).  A stream of another priority class is not pooled with them.
+    int lo = 0, hi = 0;
+    bool ok;
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
+        ok = hipStreamCreateWithPriority(&in.copy_stream, hipStreamNonBlocking, hi) == hipSuccess;
+    else
+        ok = hipStreamCreateWithFlags(&in.copy_stream, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&in.ev_next_ready, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&in.ev_next_free, hipEventDisableTiming) == hipSuccess;
+    return ok;
+}
+
+void frp::release_ingest(frp_handle* h) {       // (frp_destroy has waited for both streams)
+    Ingest& in = h->in;
+    for (DevBuf* b : {&in.frames_next, &in.jpeg_coef, &in.jpeg_planes, &in.jpeg_scan, &in.jpeg_err}) release(*b);
+    for (void* p : in.pinned) (void)hipHostFree(p);
+    for (void* p : in.jpeg_pin)
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : {in.ev_jpeg_h2d[0], in.ev_jpeg_h2d[1], in.ev_next_ready, in.ev_next_free})
+        if (e) (void)hipEventDestroy(e);
+    if (in.copy_stream) (void)hipStreamDestroy(in.copy_stream);
+}
+
+void frp::set_resident(frp_handle* h, int B, int H, int W) {
+    h->rB = B; h->rH = H; h->rW = W;
+    h->dH = H; h->dW = W; h->det_scaled = false;
+    h->canvas_h = round_up(H, 32);
+    h->canvas_w = round_up(W, 32);
+}
+
+namespace {
+
+int check_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride) {
+    if (!bgr || B <= 0 || H <= 0 || W <= 0 || row_stride < (int64_t)W * 3) return fail(h, FRP_ERR_INVALID, "bad frame arguments");
+    if (B > 1024) return fail(h, FRP_ERR_INVALID, "batch too large (max 1024 frames per call)");
+    return FRP_OK;
+}
+
+// The staging sequence of a batch: grow_staged, begin_staging, its copies and kernels on the copy stream, end_staging (not reached on
+// an error return: the staged dims and next_valid stay).  Growing buffers: nothing may still be copying into / computing from them, so
+// BOTH streams are waited for first (ensure() waits for the compute stream only: a running staged copy would write into freed memory).
+struct Staged { DevBuf* buf; size_t bytes; };
+int grow_staged(frp_handle* h, std::initializer_list<Staged> bufs) {
+    if (std::none_of(bufs.begin(), bufs.end(), [](const Staged& s) { return s.bytes > s.buf->cap || !s.buf->p; })) return FRP_OK;
+    HIPCHK(h, hipStreamSynchronize(h->in.copy_stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (const Staged& s : bufs) FRPCHK(ensure(h, *s.buf, s.bytes));
+    return FRP_OK;
+}
+// the staging frame buffer was the resident one until the last swap: the copy stream waits for the work enqueued before it
+int begin_staging(frp_handle* h) {
+    HIPCHK(h, hipStreamWaitEvent(h->in.copy_stream, h->in.ev_next_free, 0));
+    return FRP_OK;
+}
+int end_staging(frp_handle* h, int B, int H, int W) {
+    HIPCHK(h, hipEventRecord(h->in.ev_next_ready, h->in.copy_stream));
+    h->in.nB = B; h->in.nH = H; h->in.nW = W;
+    h->in.next_valid = true;
+    return FRP_OK;
+}
+
+// the page-locked JPEG staging block of `turn`, at least `bytes` large: the copy of the batch before the previous one read it
+int jpeg_staging_turn(frp_handle* h, int turn, size_t bytes, void** out) {
+    Ingest& in = h->in;
+    if (in.jpeg_h2d_pending[turn]) HIPCHK(h, hipEventSynchronize(in.ev_jpeg_h2d[turn]));
+    in.jpeg_h2d_pending[turn] = false;
+    if (bytes > in.jpeg_pin_cap[turn]) {
+        if (in.jpeg_pin[turn]) { (void)hipHostFree(in.jpeg_pin[turn]); in.jpeg_pin[turn] = nullptr; in.jpeg_pin_cap[turn] = 0; }
+        if (hipHostMalloc(&in.jpeg_pin[turn], bytes, hipHostMallocDefault) != hipSuccess) return fail(h, FRP_ERR_OOM, "hipHostMalloc (JPEG staging) failed");
+        in.jpeg_pin_cap[turn] = bytes;
+    }
+    if (!in.ev_jpeg_h2d[turn]) HIPCHK(h, hipEventCreateWithFlags(&in.ev_jpeg_h2d[turn], hipEventDisableTiming));
+    *out = in.jpeg_pin[turn];
+    return FRP_OK;
+}
+
+const char* const kGeometryDiffers = "geometry differs from image 0 (one batch = one frame size and sampling)";
+bool same_geometry(const frp_jpeg_info& a, const frp_jpeg_info& b) {
+    return a.width == b.width && a.height == b.height && a.components == b.components && a.h_samp[0] == b.h_samp[0] && a.v_samp[0] == b.v_samp[0];
+}
+
+// the pixel kernels (dequantise, inverse DCT, upsample, YCbCr -> BGR) from the device coefficients into the staging frame buffer
+int launch_pixels(frp_handle* h, JpegParams p, size_t q_off) {
+    p.coef = (const int16_t*)h->in.jpeg_coef.p;
+    p.qtab = (const uint16_t*)((const char*)h->in.jpeg_coef.p + q_off);
+    p.planes = (uint8_t*)h->in.jpeg_planes.p;
+    p.frames = (uint8_t*)h->in.frames_next.p;
+    const hipError_t e = launch_jpeg_decode(p, h->in.copy_stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg decode: ") + hipGetErrorString(e));
+    return FRP_OK;
+}
+
+}  // namespace
+
+int frp::upload_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride) {
+    FRPCHK(check_frames(h, bgr, B, H, W, row_stride));
+    FRPCHK(ensure(h, h->frames, (size_t)B * H * W * 3));
+    rec(h, EV_START);
+    HIPCHK(h, hipMemcpy2DAsync(h->frames.p, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, (size_t)B * H,
+                               hipMemcpyHostToDevice, h->stream));
+    rec(h, EV_H2D);
+    set_resident(h, B, H, W);
+    return FRP_OK;
+}
+
+extern "C" {
+
+int frp_upload_frames(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, int32_t W, int64_t row_stride) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    FRPCHK(upload_frames(h, bgr, B, H, W, row_stride));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return FRP_OK;
+}
+
+void* frp_host_alloc(frp_handle* h, size_t bytes) {
+    if (!h || bytes == 0) return nullptr;
+    Guard g(h);
+    void* p = nullptr;
+    if (hipSetDevice(h->device) != hipSuccess || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
+        fail(h, FRP_ERR_OOM, "hipHostMalloc failed");
+        return nullptr;
+    }
+    h->in.pinned.push_back(p);
+    return p;
+}
+
+void frp_host_free(frp_handle* h, void* p) {
+    if (!h || !p) return;
+    Guard g(h);
+    for (size_t i = 0; i < h->in.pinned.size(); ++i)
+        if (h->in.pinned[i] == p) {
+            (void)hipStreamSynchronize(h->in.copy_stream);
+            (void)hipHostFree(p);
+            h->in.pinned.erase(h->in.pinned.begin() + (long)i);
+            return;
+        }
+}
+
+int frp_upload_frames_async(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, int32_t W, int64_t row_stride) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);      // copy stream only: does not re-record the stage events, so a pending pass is not drained
+                            // (with the timers on, settling here made the upload of batch t+1 wait for batch t)
+    FRPCHK(check_frames(h, bgr, B, H, W, row_stride));
+    FRPCHK(grow_staged(h, {{&h->in.frames_next, (size_t)B * H * W * 3}}));
+    FRPCHK(begin_staging(h));
+    HIPCHK(h, hipMemcpy2DAsync(h->in.frames_next.p, (size_t)W * 3, bgr, (size_t)row_stride, (size_t)W * 3, (size_t)B * H,
+                               hipMemcpyHostToDevice, h->in.copy_stream));
+    return end_staging(h, B, H, W);
+}
+
+int frp_jpeg_info_get(const uint8_t* data, size_t size, frp_jpeg_info* info) {
+    if (!data || !info) return FRP_ERR_INVALID;
+    return jpeg_info(data, size, info, nullptr);
+}
+
+int frp_jpeg_coefficients(const uint8_t* data, size_t size, int16_t* coef, size_t coef_elems, uint16_t* qtab, frp_jpeg_info* info) {
+    if (!data || !coef || !qtab) return FRP_ERR_INVALID;
+    return jpeg_decode_coefficients(data, size, coef, coef_elems, qtab, info, nullptr);
+}
+
+namespace {   // Inside extern "C" this unnamed namespace does not hide the name: libfrp.so exports upload_jpeg_device by accident.  Kept
+              // only because this move leaves the set of exports as it is; a change that cleans the ABI moves it out of extern "C".
+// Device entropy decode of a batch whose frames all carry restart intervals (round 5; jpeg_kernels.hip: jpeg_huffman_kernel): the host
+// parses headers and finds the RSTn markers (one memchr pass), the COMPRESSED scans go to the device (~0.5 MB per 1080p frame instead of
+// 6.3 MB of coefficients), one thread per interval decodes, and the host waits only for the per-image error flags (a corrupt stream
+// must be reported by this call, as on the host path) before the pixel kernels are queued.  -> FRP_OK, an error, or 1 = "not this
+// batch" (not switched on, no restart intervals, too few of them to fill a wave): the caller takes the host decoder.
+int upload_jpeg_device(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, const frp_jpeg_info& I, int turn,
+                       const JpegParams& p, const JpegBatchLayout& L) {
+    // When: one thread per interval decodes 32 x 1080p frames in 17.8 ms at one interval per MCU row (120 MCUs), 4.5 ms at 30 MCUs,
+    // 1.25 ms at 8 (profiles/r5/jpeg_device_entropy.txt) - the time goes with the LENGTH of an interval, and 16 host threads take
+    // 9-12 ms: by default the device decodes streams whose intervals are at most 32 MCUs and the host the others.
+    // FRP_JPEG_DEVICE_HUFFMAN=1 (read once): the device whatever the interval (takes the entropy decode off the host's cores; at
+    // one interval per row it is slower than the pipeline consumes frames), =0: never.
+    const int mode = process_switches().jpeg_device_huffman;
+    if (mode < 0 || I.restart_interval <= 0 || (mode == 0 && I.restart_interval > 32)) return 1;
+    const long n_int = ((long)I.mcus_x * I.mcus_y + I.restart_interval - 1) / I.restart_interval;
+    if ((long)B * n_int < 64 || n_int > 0x7fffff) return 1;
+    std::vector<JpegDevicePlan> plans((size_t)B);
+    std::vector<JpegHuffTableDev> tabs((size_t)B * 6);
+    std::vector<size_t> scan_bytes((size_t)B);
+    for (int i = 0; i < B; ++i) {
+        std::string e;
+        if (!jpegs[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": null image");
+        const int rc = jpeg_plan_device_decode(jpegs[i], sizes[i], plans[i], tabs.data() + (size_t)i * 6, &e);
+        if (rc != FRP_OK) {
+            if (plans[i].info.restart_interval <= 0 && plans[i].info.width > 0) return 1;          // a frame without intervals: host path for the batch
+            return fail(h, rc, "JPEG " + std::to_string(i) + ": " + e);
+        }
+        if (!same_geometry(plans[i].info, I)) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": " + kGeometryDiffers);
+        if (plans[i].info.restart_interval != I.restart_interval) return 1;
+        scan_bytes[i] = plans[i].scan_bytes;
+    }
+    const JpegDeviceStageLayout S = jpeg_device_stage_layout(B, n_int, scan_bytes.data());
+    if (S.too_large) return 1;
+    Ingest& in = h->in;
+    void* pin = nullptr;
+    FRPCHK(jpeg_staging_turn(h, turn, S.stage_total, &pin));
+    char* st = (char*)pin;
+    uint32_t* io = (uint32_t*)(st + S.o_int);
+    for (int i = 0; i < B; ++i) {
+        memcpy(st + S.soff[i], plans[i].scan, plans[i].scan_bytes);
+        for (long k = 0; k <= n_int; ++k) io[(size_t)i * (n_int + 1) + k] = (uint32_t)(S.soff[i] + plans[i].int_off[(size_t)k]);
+        memcpy(st + S.o_q + (size_t)i * 384, plans[i].qtab, 384);
+    }
+    memcpy(st + S.o_tab, tabs.data(), tabs.size() * sizeof(JpegHuffTableDev));
+    FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img},
+                           {&in.jpeg_scan, S.o_err}, {&in.jpeg_err, (size_t)B * 4}}));
+    FRPCHK(begin_staging(h));
+    HIPCHK(h, hipMemcpyAsync(in.jpeg_scan.p, st, S.o_err, hipMemcpyHostToDevice, in.copy_stream));
+    HIPCHK(h, hipMemsetAsync(in.jpeg_coef.p, 0, L.q_off, in.copy_stream));
+    HIPCHK(h, hipMemcpyAsync((char*)in.jpeg_coef.p + L.q_off, (char*)in.jpeg_scan.p + S.o_q, (size_t)B * 384, hipMemcpyDeviceToDevice, in.copy_stream));
+    HIPCHK(h, hipMemsetAsync(in.jpeg_err.p, 0, (size_t)B * 4, in.copy_stream));
+    JpegHuffParams hp{};
+    hp.scan = (const uint8_t*)in.jpeg_scan.p;
+    hp.int_off = (const uint32_t*)((const char*)in.jpeg_scan.p + S.o_int);
+    hp.tables = (const JpegHuffTableDev*)((const char*)in.jpeg_scan.p + S.o_tab);
+    hp.coef = (int16_t*)in.jpeg_coef.p;
+    hp.err = (int32_t*)in.jpeg_err.p;
+    hp.coef_per_image = (long)L.coef_elems;
+    hp.B = B; hp.n_int = (int)n_int; hp.ri = I.restart_interval;
+    hp.mcus_x = I.mcus_x; hp.mcus_y = I.mcus_y; hp.components = I.components;
+    for (int c = 0; c < 3; ++c) { hp.hs[c] = I.h_samp[c]; hp.vs[c] = I.v_samp[c]; hp.bx[c] = L.bx[c]; hp.comp_off[c] = L.plane_off[c]; }
+    const hipError_t e = launch_jpeg_huffman(hp, in.copy_stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg huffman: ") + hipGetErrorString(e));
+    HIPCHK(h, hipMemcpyAsync(st + S.o_err, in.jpeg_err.p, (size_t)B * 4, hipMemcpyDeviceToHost, in.copy_stream));
+    HIPCHK(h, hipStreamSynchronize(in.copy_stream));   // the flags decide this call's return value (and the staging block is free again: no jpeg_h2d_pending)
+    const int32_t* flags = (const int32_t*)(st + S.o_err);
+    for (int i = 0; i < B; ++i)
+        if (flags[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": corrupt or truncated entropy-coded data");
+    FRPCHK(launch_pixels(h, p, L.q_off));
+    FRPCHK(end_staging(h, B, I.height, I.width));
+    in.ctr_jpeg_device_batches += 1;
+    return FRP_OK;
+}
+}  // namespace
+
+int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);      // copy stream only (as frp_upload_frames_async)
+    if (!jpegs || !sizes || B <= 0 || B > 1024) return fail(h, FRP_ERR_INVALID, "bad JPEG batch arguments");
+    frp_jpeg_info I{};
+    std::string err;
+    if (!jpegs[0] || jpeg_info(jpegs[0], sizes[0], &I, &err) != FRP_OK) return fail(h, FRP_ERR_INVALID, "JPEG 0: " + err);
+    const JpegBatchLayout L = jpeg_batch_layout(I, B);
+    Ingest& in = h->in;
+    const int turn = in.jpeg_turn;      // flips once per call, whichever decoder takes the batch and whether it succeeds
+    in.jpeg_turn ^= 1;
+    JpegParams p{};
+    p.B = B; p.W = I.width; p.H = I.height; p.components = I.components;
+    p.hs = I.h_samp[0]; p.vs = I.v_samp[0];
+    p.cw = L.cw; p.ch = L.ch; p.blocks_per_image = L.blocks_per_image; p.plane_img = L.plane_img;
+    for (int c = 0; c < 3; ++c) { p.bx[c] = L.bx[c]; p.by[c] = L.by[c]; p.plane_off[c] = L.plane_off[c]; }
+    const int dr = upload_jpeg_device(h, jpegs, sizes, B, I, turn, p, L);     // restart-interval streams: entropy decode on the device
+    if (dr != 1) return dr;
+    void* pin = nullptr;
+    FRPCHK(jpeg_staging_turn(h, turn, L.total, &pin));
+    int16_t* coef = (int16_t*)pin;
+    uint16_t* qtab = (uint16_t*)((char*)pin + L.q_off);
+    // entropy decoding: one image per task on host threads (the images are independent; within one the bit stream is serial)
+    std::vector<int> rcs((size_t)B, FRP_OK);
+    std::vector<std::string> errs((size_t)B);
+    {
+        const int nth = std::max(1, std::min<int>(B, (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()))));
+        std::atomic<int> next{0};
+        auto work = [&]() {
+            for (int i = next.fetch_add(1); i < B; i = next.fetch_add(1)) {
+                frp_jpeg_info Ii{};
+                if (!jpegs[i]) { rcs[i] = FRP_ERR_INVALID; errs[i] = "null image"; continue; }
+                rcs[i] = jpeg_decode_coefficients(jpegs[i], sizes[i], coef + (size_t)i * L.coef_elems, L.coef_elems, qtab + (size_t)i * 192, &Ii, &errs[i]);
+                if (rcs[i] == FRP_OK && !same_geometry(Ii, I)) { rcs[i] = FRP_ERR_INVALID; errs[i] = kGeometryDiffers; }
+            }
+        };
+        std::vector<std::thread> th;
+        for (int t = 1; t < nth; ++t) th.emplace_back(work);
+        work();
+        for (auto& t : th) t.join();
+    }
+    for (int i = 0; i < B; ++i)
+        if (rcs[i] != FRP_OK) return fail(h, rcs[i], "JPEG " + std::to_string(i) + ": " + errs[i]);
+    FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img}}));
+    FRPCHK(begin_staging(h));
+    HIPCHK(h, hipMemcpyAsync(in.jpeg_coef.p, pin, L.total, hipMemcpyHostToDevice, in.copy_stream));
+    HIPCHK(h, hipEventRecord(in.ev_jpeg_h2d[turn], in.copy_stream));
+    in.jpeg_h2d_pending[turn] = true;
+    FRPCHK(launch_pixels(h, p, L.q_off));
+    return end_staging(h, B, I.height, I.width);
+}
+
+// diagnostic: how many frp_upload_jpeg_async batches had their entropy decode on the device (restart-interval streams)
+int64_t frp_debug_jpeg_device_batches(frp_handle* h) {
+    if (!h) return -1;
+    Guard g(h, false);
+    return h->in.ctr_jpeg_device_batches;
+}
+
+int frp_swap_frames(frp_handle* h) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);      // enqueues a wait + an event on the compute stream; the stage events stay as recorded
+    Ingest& in = h->in;
+    if (!in.next_valid) return fail(h, FRP_ERR_INVALID, "no staged frames (call frp_upload_frames_async)");
+    HIPCHK(h, hipStreamWaitEvent(h->stream, in.ev_next_ready, 0));     // compute waits for the staged copy
+    std::swap(h->frames, in.frames_next);
+    HIPCHK(h, hipEventRecord(in.ev_next_free, h->stream));            // ... and the old resident buffer is free after
+    set_resident(h, in.nB, in.nH, in.nW);                              // everything enqueued so far
+    in.next_valid = false;
+    return FRP_OK;
+}
+
+}  // extern "C"

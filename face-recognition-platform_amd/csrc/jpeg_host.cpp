@@ -325,6 +325,40 @@ size_t jpeg_coef_elems(const frp_jpeg_info& I) {
     return e;
 }
 
+JpegBatchLayout jpeg_batch_layout(const frp_jpeg_info& I, int B) {
+    JpegBatchLayout L{};
+    L.coef_elems = jpeg_coef_elems(I);
+    L.coef_bytes = (size_t)B * L.coef_elems * 2;
+    L.q_off = (L.coef_bytes + 255) & ~(size_t)255;
+    L.total = L.q_off + (size_t)B * 3 * 64 * 2;
+    const int hs = I.h_samp[0], vs = I.v_samp[0];
+    L.cw = (I.width + hs - 1) / hs;
+    L.ch = (I.height + vs - 1) / vs;
+    long off = 0;
+    for (int c = 0; c < I.components; ++c) {
+        L.bx[c] = I.mcus_x * I.h_samp[c];
+        L.by[c] = I.mcus_y * I.v_samp[c];
+        L.blocks_per_image += L.bx[c] * L.by[c];
+        L.plane_off[c] = off;
+        off += (long)L.bx[c] * L.by[c] * 64;
+    }
+    L.plane_img = off;
+    return L;
+}
+
+JpegDeviceStageLayout jpeg_device_stage_layout(int B, long n_int, const size_t* scan_bytes) {
+    JpegDeviceStageLayout S{std::vector<size_t>((size_t)B + 1, 0)};
+    for (int i = 0; i < B; ++i) S.soff[i + 1] = (S.soff[i] + scan_bytes[i] + 15) & ~(size_t)15;
+    S.too_large = S.soff[B] >= 0xfffffff0u;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    S.o_int = up(S.soff[B]);
+    S.o_tab = up(S.o_int + (size_t)B * (n_int + 1) * 4);
+    S.o_q = up(S.o_tab + (size_t)B * 6 * sizeof(JpegHuffTableDev));
+    S.o_err = up(S.o_q + (size_t)B * 192 * 2);
+    S.stage_total = S.o_err + (size_t)B * 4;
+    return S;
+}
+
 int jpeg_info(const uint8_t* data, size_t size, frp_jpeg_info* out, std::string* err) {
     JpegHeaderInternal H;
     const int rc = parse_headers(data, size, H);

@@ -1,4 +1,4 @@
-// Host half of the JPEG ingest (jpeg_host.cpp): header parsing + Huffman decoding of baseline JPEG stills.
+// Host half of the JPEG ingest (jpeg_host.cpp): header parsing + Huffman decoding of baseline JPEG stills, the buffer layouts of a batch.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,5 +34,29 @@ struct JpegDevicePlan {
     std::vector<uint32_t> int_off;      // [n_int + 1] offsets from `scan`
 };
 int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& plan, JpegHuffTableDev* tables6, std::string* err);
+
+#define FRP_JPEG_LOCAL __attribute__((visibility("hidden")))   // for ingest_api.cpp and the test harness: not among the library's exports
+
+// Where a batch of B images of one geometry lies (frp_upload_jpeg_async; plain arithmetic on header fields, so the sanitizer harness
+// reaches it).  Coefficient staging, the same on the host and on the device: [B][coef_elems] int16, then at q_off (256-byte aligned)
+// [B][3][64] uint16 quantisation tables; `total` bytes in all.  Sample planes of the pixel kernels: per image the components back to
+// back (plane_off, plane_img bytes per image), bx x by blocks each (whole MCUs); cw x ch = real extent of the chroma planes.
+struct JpegBatchLayout {
+    size_t coef_elems, coef_bytes, q_off, total;
+    int bx[3], by[3];
+    long plane_off[3], plane_img;
+    int blocks_per_image, cw, ch;
+};
+FRP_JPEG_LOCAL JpegBatchLayout jpeg_batch_layout(const frp_jpeg_info& info, int B);
+
+// Page-locked staging of the device entropy decode: scans (16-byte aligned each, soff[B + 1]) | interval offsets [B][n_int + 1] u32 |
+// Huffman tables [B][6] | quantisation tables, 384 bytes per image | error flags [B] i32 (read back) - every part 256-byte aligned.
+// The first o_err bytes go to the device.  too_large: the scans do not fit 32-bit offsets (the batch takes the host decoder).
+struct JpegDeviceStageLayout {
+    std::vector<size_t> soff;
+    size_t o_int, o_tab, o_q, o_err, stage_total;
+    bool too_large;
+};
+FRP_JPEG_LOCAL JpegDeviceStageLayout jpeg_device_stage_layout(int B, long n_int, const size_t* scan_bytes);
 
 }  // namespace frp

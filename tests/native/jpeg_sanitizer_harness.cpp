@@ -1,7 +1,8 @@
 // Sanitizer harness of the JPEG host decoder (csrc/jpeg_host.cpp, plain C++: no HIP): built by tests/test_jpeg.py with
 // g++ -fsanitize=address,undefined and run over a corpus of damaged files.  Every input is copied into a heap block of EXACTLY its
 // size (so a read one byte past the file is a heap-buffer-overflow report, not a lucky zero), parsed, and - if the headers pass -
-// entropy-decoded into an exactly sized coefficient buffer.  Prints one line per file; exits non-zero only through a sanitizer report.
+// entropy-decoded into an exactly sized coefficient buffer; for every file that decodes, the buffer layouts of a batch of such images
+// are checked too.  Prints one summary line; exits non-zero only through a sanitizer report or a layout violation.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,8 +13,60 @@
 #include "frp.h"
 #include "jpeg_host.h"
 
+// The buffer layouts of a batch of B such images (jpeg_batch_layout, jpeg_device_stage_layout): the parts in order, none overlapping
+// the next, each at its alignment, the last one ending at the total, and no product wrapping.  A violation ends the run non-zero.
+#define LAYOUT_CHECK(cond)                                                                            \
+    do {                                                                                              \
+        if (!(cond)) { fprintf(stderr, "%s: B %d: layout check failed: %s\n", path, B, #cond); exit(3); } \
+    } while (0)
+
+static void check_layouts(const char* path, const frp_jpeg_info& info, const frp::JpegDevicePlan* plan, size_t file_bytes) {
+    for (int B : {1, 3, 32}) {
+        const frp::JpegBatchLayout L = frp::jpeg_batch_layout(info, B);
+        const unsigned __int128 b = (unsigned)B;
+        LAYOUT_CHECK(L.coef_elems == frp::jpeg_coef_elems(info));
+        LAYOUT_CHECK(b * L.coef_elems * 2 == L.coef_bytes);                              // (no wrap)
+        LAYOUT_CHECK(L.q_off >= L.coef_bytes && L.q_off - L.coef_bytes < 256 && L.q_off % 256 == 0);
+        LAYOUT_CHECK(L.total == L.q_off + (size_t)B * 384 && L.total > L.q_off);
+        long end = 0;
+        int blocks = 0;
+        for (int c = 0; c < info.components; ++c) {
+            LAYOUT_CHECK(L.bx[c] > 0 && L.by[c] > 0 && L.plane_off[c] == end && L.plane_off[c] % 8 == 0);
+            LAYOUT_CHECK((__int128)L.bx[c] * L.by[c] * 64 <= (__int128)0x7fffffffffffffffLL - end);
+            end += (long)L.bx[c] * L.by[c] * 64;
+            blocks += L.bx[c] * L.by[c];
+        }
+        LAYOUT_CHECK(L.plane_img == end && L.blocks_per_image == blocks && (size_t)blocks * 64 == L.coef_elems);
+        LAYOUT_CHECK(b * (unsigned __int128)L.plane_img == (size_t)B * L.plane_img);     // B * plane_img does not wrap
+        LAYOUT_CHECK(L.cw > 0 && L.ch > 0 && L.cw <= L.bx[0] * 8 && L.ch <= L.by[0] * 8);
+        // scan sizes: the file's own where it has restart intervals, else made up from the file size
+        const long n_int = plan ? (long)plan->int_off.size() - 1 : 1 + (long)(file_bytes % 7);
+        std::vector<size_t> scans((size_t)B);
+        for (int i = 0; i < B; ++i) scans[i] = plan ? plan->scan_bytes : (file_bytes + 13 * (size_t)i) % 100003;
+        const frp::JpegDeviceStageLayout S = frp::jpeg_device_stage_layout(B, n_int, scans.data());
+        LAYOUT_CHECK(S.soff.size() == (size_t)B + 1 && S.soff[0] == 0 && !S.too_large);
+        for (int i = 0; i < B; ++i) LAYOUT_CHECK(S.soff[i] % 16 == 0 && S.soff[i + 1] >= S.soff[i] + scans[i]);
+        LAYOUT_CHECK(S.o_int >= S.soff[B] && S.o_tab >= S.o_int + (size_t)B * (n_int + 1) * 4);
+        LAYOUT_CHECK(S.o_q >= S.o_tab + (size_t)B * 6 * sizeof(frp::JpegHuffTableDev) && S.o_err >= S.o_q + (size_t)B * 384);
+        LAYOUT_CHECK(S.o_int % 256 == 0 && S.o_tab % 256 == 0 && S.o_q % 256 == 0 && S.o_err % 256 == 0);
+        LAYOUT_CHECK(S.stage_total == S.o_err + (size_t)B * 4);
+    }
+}
+
+// The one answer of jpeg_device_stage_layout that no file of the corpus reaches: scans that end at or beyond 0xfffffff0 bytes do not
+// fit the kernel's 32-bit offsets (pure arithmetic: nothing of that size is allocated).
+static void check_too_large() {
+    const char* path = "(made-up scan sizes)";
+    const int B = 2;
+    const size_t fits[B] = {0x7ffffff0u, 0x7fffffe1u}, over[B] = {0x7ffffff0u, 0x7ffffff1u};
+    const frp::JpegDeviceStageLayout F = frp::jpeg_device_stage_layout(B, 1, fits), O = frp::jpeg_device_stage_layout(B, 1, over);
+    LAYOUT_CHECK(F.soff[B] == 0xffffffe0u && !F.too_large && F.o_int == 0x100000000ull);
+    LAYOUT_CHECK(O.soff[B] == 0xfffffff0u && O.too_large);
+}
+
 int main(int argc, char** argv) {
     int decoded = 0, refused = 0;
+    check_too_large();
     for (int i = 1; i < argc; ++i) {
         FILE* f = fopen(argv[i], "rb");
         if (!f) continue;
@@ -46,6 +99,7 @@ int main(int argc, char** argv) {
                 for (size_t k = 0; k + 1 < plan.int_off.size(); ++k) sum += plan.scan[plan.int_off[k] < plan.scan_bytes ? plan.int_off[k] : 0];
                 if (plan.scan_bytes) sum += plan.scan[plan.scan_bytes - 1];
             }
+            if (rc == FRP_OK) check_layouts(argv[i], info, rc2 == FRP_OK ? &plan : nullptr, (size_t)n);
         }
         if (rc == FRP_OK) ++decoded; else ++refused;
         free(buf);

@@ -411,6 +411,100 @@ def test_overlapped_ingest_equals_plain_calls(engine):
         engine.swap_frames()                              # nothing staged
 
 
+def test_mixed_ingest_kinds_back_to_back_equal_plain_calls(engine):
+    """The overlapped loop of the test above with a different INGEST KIND for every consecutive batch - raw frames from page-locked
+    and from pageable memory, JPEG stills with the entropy decode on host threads (no restart markers) and on the device (one
+    interval per MCU) - so that every kind stages behind every other one on the same handle.  The sizes grow (3 x 96 x 160: every
+    staging buffer is regrown while a pass is in flight) and shrink again (4 x 64 x 96: nothing grows, both page-locked JPEG turns
+    are reused at a smaller size), and one batch is refused by the call (an image cut inside a restart interval) before a good batch
+    of each JPEG kind.  Every accepted batch gives exactly the results of a plain process_frames call on the same pixels (for a JPEG
+    batch: the PIL-decoded BGR frames), and the device-decode counter advances by exactly the accepted device-path batches."""
+    import io
+    from PIL import Image
+    from frp_amd import native
+    from frp_amd.native import FrpError
+    assert os.environ.get("FRP_JPEG_DEVICE_HUFFMAN") == "1"
+    rng = np.random.default_rng(77)
+    raw, blob = get_raw_and_blob((1, 2, 2, 2), (1, 1, 1, 1))
+    engine.load_weights(blob)
+    engine.gallery_set(rng.standard_normal((200, 512)).astype(np.float32))
+    K, flags = 3, native.FLAG_FORCED_K
+
+    def stills(B, H, W, **kw):
+        out = []
+        for _ in range(B):
+            img = np.clip(rng.normal(120, 55, (H // 8 + 1, W // 8 + 1, 3)).repeat(8, 0).repeat(8, 1)[:H, :W] + rng.normal(0, 7, (H, W, 3)), 0, 255)
+            b = io.BytesIO()
+            Image.fromarray(img.astype(np.uint8)).save(b, "JPEG", quality=88, subsampling=2, **kw)
+            out.append(b.getvalue())
+        return out
+
+    def pil_bgr(jpegs):
+        return np.stack([np.ascontiguousarray(np.array(Image.open(io.BytesIO(d)).convert("RGB"))[..., ::-1]) for d in jpegs])
+
+    small, large = (4, 64, 96), (3, 96, 160)
+    kinds = [("pinned", small), ("jpeg-host", small), ("jpeg-device", small), ("pageable", small), ("jpeg-device", small), ("jpeg-host", small),
+             ("jpeg-device", large), ("jpeg-host", large), ("jpeg-device", small), ("jpeg-host", small),
+             ("refused", small), ("jpeg-device", small), ("jpeg-host", small)]
+    assert all(a[0] != b[0] for a, b in zip(kinds[:-1], kinds[1:]))
+    batches = []                                        # (kind, what the upload call gets, the frames process_frames gets)
+    for kind, shape in kinds:
+        if kind in ("pinned", "pageable"):
+            f = _frames(rng, *shape)
+            batches.append((kind, f, f))
+        elif kind == "refused":
+            good = stills(*shape, restart_marker_blocks=1)
+            d = good[2]
+            sos = d.find(b"\xff\xda")
+            rst = [i for i in range(sos, len(d) - 1) if d[i] == 0xFF and 0xD0 <= d[i + 1] <= 0xD7]
+            assert len(rst) == 23                       # 24 MCUs, one interval each
+            cut = d[:rst[3] + 2 + (rst[4] - rst[3]) // 2] + d[rst[4]:]          # half of interval 4 is missing
+            batches.append((kind, good[:2] + [cut] + good[3:], None))
+        else:
+            j = stills(*shape, **(dict(restart_marker_blocks=1) if kind == "jpeg-device" else {}))
+            assert native.jpeg_info(j[0])["restart_interval"] == (1 if kind == "jpeg-device" else 0)
+            batches.append((kind, j, pil_bgr(j)))
+    want = [None if f is None else engine.process_frames(f, max_faces=K, flags=flags) for _, _, f in batches]
+    n0 = engine.jpeg_device_batches()
+    pinned = engine.host_frames(*small)
+    accepted_on_device = 0
+
+    def upload(i):
+        """stage batch i by its kind; the refused batch raises, leaves nothing staged, and the batch behind it goes in its place"""
+        nonlocal accepted_on_device
+        kind, src, _ = batches[i]
+        if kind == "refused":
+            with pytest.raises(FrpError, match="JPEG 2"):
+                engine.upload_jpeg_async(src)
+            return upload(i + 1)
+        if kind == "pinned":
+            pinned[...] = src
+            engine.upload_frames_async(pinned)
+        elif kind == "pageable":
+            engine.upload_frames_async(src)
+        else:
+            engine.upload_jpeg_async(src)
+            accepted_on_device += kind == "jpeg-device"
+        assert engine.jpeg_device_batches() == n0 + accepted_on_device, (i, kind)
+        return i
+
+    cur = upload(0)
+    engine.swap_frames()
+    checked = 0
+    while cur is not None:
+        nxt = upload(cur + 1) if cur + 1 < len(batches) else None          # overlaps the processing of batch `cur`
+        engine.process_resident(max_faces=K, flags=flags)
+        got = engine.fetch_results()
+        for key in ("boxes", "kps", "scores", "counts", "emb", "match_idx", "match_cos"):
+            assert np.array_equal(got[key], want[cur][key]), (cur, batches[cur][0], key)
+        checked += 1
+        if nxt is not None:
+            engine.swap_frames()
+        cur = nxt
+    assert checked == len(batches) - 1
+    assert engine.jpeg_device_batches() == n0 + 5
+
+
 def test_no_faces_and_no_gallery(engine):
     raw, blob = get_raw_and_blob((1, 2, 2, 2), (1, 1, 1, 1))
     engine.load_weights(blob)

@@ -610,7 +610,8 @@ void frp_destroy(frp_handle* h) {
     for (DevBuf& b : h->emb.bufs) release(b);
     DevBuf* all[] = {&h->wdata, &h->frames, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
                      &h->q16, &h->part_cos, &h->part_idx, &h->best_cos, &h->best_idx, &h->hit_cnt, &h->hit_idx, &h->hit_cos, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
-                     &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->det_hashes, &h->quality_in, &h->quality_out};
+                     &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->det_hashes, &h->quality_in, &h->quality_out,
+                     &h->jenc_in, &h->jenc_coef, &h->jenc_work, &h->jenc_bits, &h->jenc_out};
     for (DevBuf* b : all) release(*b);
     for (int i = 0; i < EV_COUNT; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->h_nfaces) (void)hipHostFree(h->h_nfaces);

@@ -84,6 +84,8 @@ struct frp_handle {
     bool q16_of_pass = false;         // q16 still holds that pass's queries (a list that overflowed is rebuilt from them at fetch time)
     // frp_face_quality: rectangles + tile prefix in, per-tile partials + per-rectangle sums out (its own: the last pass's results stay)
     frp::DevBuf quality_in, quality_out;
+    // frp_encode_jpeg: rectangles + tables in, quantised coefficients, the scans' work arrays, the unstuffed bit stream, the files (its own)
+    frp::DevBuf jenc_in, jenc_coef, jenc_work, jenc_bits, jenc_out;
     int32_t* h_nfaces = nullptr;   // pinned
     unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
     size_t pin_cap = 0;
@@ -162,7 +164,7 @@ public:
     DevBuf take() { return std::exchange(b, DevBuf()); }
 };
 
-// What the files of entry points share (frp_api.cpp, ingest_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp)
+// What the files of entry points share (frp_api.cpp, ingest_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp, jpeg_encode_api.cpp)
 FRP_LOCAL void settle_events(frp_handle* h, bool stream_is_idle);   // frp_api.cpp
 inline void rec(frp_handle* h, int which) { if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream); }   // a stage event (timers on)
 FRP_LOCAL bool init_ingest(frp_handle* h);                          // ingest_api.cpp: the copy stream and its events (frp_create)

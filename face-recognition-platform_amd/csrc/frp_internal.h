@@ -320,6 +320,63 @@ struct QualityParams {
 };
 hipError_t launch_face_quality(const QualityParams& p, hipStream_t stream);
 
+// JPEG encoder (jpeg_encode_kernels.hip; frp.h: frp_encode_jpeg): rectangles of the resident u8 frames -> baseline JPEG scans with libjpeg's
+// integer arithmetic.  One image per rectangle; blocks, restart intervals and bit-stream words are numbered over ALL images of a call.
+struct JpegEncImage {
+    int frame, top, left, h, w;   // the rectangle (validated by the caller: inside the frame, not empty)
+    int mx, my;                   // MCU grid
+    int n_int;                    // restart intervals of the image (1 without restart markers)
+    int int0;                     // intervals of the images before it
+    int pad_;
+    long long blk0;               // blocks of the images before it (a block = 64 coefficients)
+};
+struct JpegEncTables {            // built on the host (jpeg_encode_api.cpp)
+    uint32_t dc[2][16];           // (length << 16) | code by magnitude category; luminance, chrominance
+    uint32_t ac[2][256];          // ... by run / size symbol
+    uint16_t q[2][64];            // quantisation tables, natural order
+};
+struct JpegEncParams {
+    const uint8_t* frames;        // [B,H,W,3] u8, tightly packed
+    long long total_bytes;        // B*H*W*3: no byte at or beyond it is read
+    int B, H, W;
+    int rgb_in;
+    const JpegEncImage* img;      // [n]
+    const JpegEncTables* tab;
+    int n;
+    int hs, vs;                   // luma sampling factors: 2 x 2 (4:2:0) or 1 x 1 (4:4:4); chroma is 1 x 1
+    int ri;                       // MCUs per restart interval, 0: none
+    long long n_blocks;           // of all images
+    long long n_int;              // intervals of all images
+    int16_t* coef;                // [n_blocks][64] natural order; per image: component by component over the MCU-padded grid
+    // entropy stage (null for the forward half alone)
+    uint32_t* blk_bits;                   // [n_blocks], in SCAN order within each image: bits of the block's codes
+    unsigned long long* bit_prefix;       // [n_blocks + 1]: exclusive sums of blk_bits
+    unsigned long long* group_tot;        // scratch of the prefix sums
+    unsigned long long* int_word;         // [n_int + 1]: first 32-bit word of the interval's unstuffed bits in `words`; [n_int] = words used
+    uint32_t* int_bytes;                  // [n_int]: unstuffed bytes, the final 1-padding included
+    unsigned long long* int_ff0;          // [n_int]: 0xFF bytes of `words` before the interval's first
+    uint32_t* int_outb;                   // [n_int]: bytes the interval takes in the file: stuffed, + 2 for the RSTm behind it
+    unsigned long long* int_out;          // [n_int + 1]: exclusive sums of int_outb
+    unsigned long long* img_off;          // [n + 1]: int_out at every image's first interval; [n] = all scan bytes
+    uint32_t* words;                      // the unstuffed bit stream, most significant bit first in each word (zeroed before the pack)
+    unsigned long long n_words;           // allocated words: no word at or beyond it is touched
+    uint32_t* ff_chunk;                   // [n_chunks]: 0xFF bytes per JE_CHUNK_WORDS words
+    unsigned long long* ff_prefix;        // [n_chunks + 1]
+    long long n_chunks;
+    const unsigned long long* scan_base;  // [n]: where the image's scan starts in `out`
+    uint8_t* out;
+    unsigned long long out_bytes;         // allocated bytes: no byte at or beyond it is written
+};
+#define JE_CHUNK_WORDS 256
+size_t jpeg_enc_scan_groups(long long n);       // entries of group_tot a prefix sum over n elements needs
+hipError_t launch_jpeg_enc_forward(const JpegEncParams& p, hipStream_t stream);
+// block bits + their prefix sums; bit_prefix[n_blocks] is the size of everything
+hipError_t launch_jpeg_enc_measure(const JpegEncParams& p, hipStream_t stream);
+// (words zeroed, n_words >= (bit_prefix[n_blocks] >> 5) + n_int + 1): bit packing, 0xFF counts, the intervals' places -> img_off
+hipError_t launch_jpeg_enc_pack(const JpegEncParams& p, hipStream_t stream);
+// stuffed bytes and restart markers into out
+hipError_t launch_jpeg_enc_emit(const JpegEncParams& p, hipStream_t stream);
+
 #ifdef FRP_LAB
 hipError_t launch_mfma_peak(const _Float16* src, float* dst, int blocks, int iters, hipStream_t stream);
 // the conv k-step's MFMA + ds_read_b128 mix without memory traffic or barriers (reads per 4 MFMAs: 4, 3 or 2)

@@ -1,0 +1,336 @@
+// frp_jpeg_encode_headers, frp_encode_jpeg, frp_encode_jpeg_coefficients (include/frp.h): baseline JPEG files of rectangles of the
+// resident frames.  The header segments are written here, in PIL's order; the scans come from jpeg_encode_kernels.hip.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "frp.h"
+#include "frp_handle.h"
+
+using namespace frp;
+
+namespace {
+
+const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// ITU-T T.81 Annex K.1 / K.2, natural order
+const uint8_t kBaseQ[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+// Annex K.3: BITS and HUFFVAL of the DC / AC tables, luminance then chrominance
+const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+const uint8_t kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
+     0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
+     0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+     0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+     0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+     0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+     0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
+     0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+     0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+     0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+     0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+     0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+     0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+     0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+
+// libjpeg's jpeg_quality_scaling + jpeg_add_quant_table (baseline: 1..255)
+void quant_tables(int quality, uint16_t q[2][64]) {
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int t = 0; t < 2; ++t)
+        for (int i = 0; i < 64; ++i) q[t][i] = (uint16_t)std::min(255, std::max(1, (kBaseQ[t][i] * s + 50) / 100));
+}
+
+// Annex C: (length << 16) | code per symbol
+void huff_codes(const uint8_t* bits, const uint8_t* vals, uint32_t* out) {
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < bits[len - 1]; ++i) out[vals[k++]] = ((uint32_t)len << 16) | code++;
+        code <<= 1;
+    }
+}
+
+void build_tables(int quality, JpegEncTables& t) {
+    std::memset(&t, 0, sizeof(t));
+    for (int i = 0; i < 2; ++i) {
+        huff_codes(kDcBits[i], kDcVals, t.dc[i]);
+        huff_codes(kAcBits[i], kAcVals[i], t.ac[i]);
+    }
+    quant_tables(quality, t.q);
+}
+
+bool sampling_ok(int subsampling, int& hs, int& vs) {
+    if (subsampling == FRP_JPEG_420) { hs = vs = 2; return true; }
+    if (subsampling == FRP_JPEG_444) { hs = vs = 1; return true; }
+    return false;
+}
+
+struct Seg {           // appends big-endian segments
+    std::vector<uint8_t> b;
+    void u8(int v) { b.push_back((uint8_t)v); }
+    void u16(int v) { u8(v >> 8); u8(v & 255); }
+    void marker(int m, int payload) { u8(0xFF); u8(m); u16(payload + 2); }
+};
+
+// SOI, APP0 (JFIF 1.01, no density), DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, DRI when restart_mcus > 0, SOS
+std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs, int restart_mcus) {
+    Seg s;
+    s.u8(0xFF); s.u8(0xD8);
+    s.marker(0xE0, 14);
+    for (char c : {'J', 'F', 'I', 'F'}) s.u8(c);
+    s.u8(0); s.u8(1); s.u8(1); s.u8(0); s.u16(1); s.u16(1); s.u8(0); s.u8(0);
+    uint16_t q[2][64];
+    quant_tables(quality, q);
+    for (int t = 0; t < 2; ++t) {
+        s.marker(0xDB, 65);
+        s.u8(t);
+        for (int i = 0; i < 64; ++i) s.u8(q[t][kZigzag[i]]);
+    }
+    s.marker(0xC0, 15);
+    s.u8(8); s.u16(height); s.u16(width); s.u8(3);
+    s.u8(1); s.u8((hs << 4) | vs); s.u8(0);
+    s.u8(2); s.u8(0x11); s.u8(1);
+    s.u8(3); s.u8(0x11); s.u8(1);
+    for (int t = 0; t < 2; ++t) {
+        s.marker(0xC4, 1 + 16 + 12);
+        s.u8(t);
+        for (int i = 0; i < 16; ++i) s.u8(kDcBits[t][i]);
+        for (int i = 0; i < 12; ++i) s.u8(kDcVals[i]);
+        s.marker(0xC4, 1 + 16 + 162);
+        s.u8(0x10 | t);
+        for (int i = 0; i < 16; ++i) s.u8(kAcBits[t][i]);
+        for (int i = 0; i < 162; ++i) s.u8(kAcVals[t][i]);
+    }
+    if (restart_mcus > 0) {
+        s.marker(0xDD, 2);
+        s.u16(restart_mcus);
+    }
+    s.marker(0xDA, 10);
+    s.u8(3); s.u8(1); s.u8(0x00); s.u8(2); s.u8(0x11); s.u8(3); s.u8(0x11); s.u8(0); s.u8(63); s.u8(0);
+    return s.b;
+}
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// validation + geometry shared by the two entry points; FRP_OK with n == 0 means: nothing to do
+int plan(frp_handle* h, const char* who, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags,
+         std::vector<JpegEncImage>& img, JpegEncParams& p) {
+    const std::string w(who);
+    if (h->rB <= 0 || !h->frames.p) return fail(h, FRP_ERR_INVALID, w + ": no resident frames");
+    if (n < 0) return fail(h, FRP_ERR_INVALID, w + ": n < 0");
+    if (flags & ~FRP_FLAG_RGB) return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB");
+    if (quality < 1 || quality > 100) return fail(h, FRP_ERR_INVALID, w + ": quality outside 1..100");
+    int hs = 0, vs = 0;
+    if (!sampling_ok(subsampling, hs, vs)) return fail(h, FRP_ERR_INVALID, w + ": subsampling is neither FRP_JPEG_420 nor FRP_JPEG_444");
+    if (restart_mcus < 0 || restart_mcus > 65535) return fail(h, FRP_ERR_INVALID, w + ": restart_mcus outside 0..65535");
+    if (n == 0) return FRP_OK;
+    if (!rects) return fail(h, FRP_ERR_INVALID, w + ": null rects");
+    img.resize((size_t)n);
+    long long blocks = 0, ints = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t *r = rects + (size_t)i * 5, f = r[0], top = r[1], right = r[2], bottom = r[3], left = r[4];
+        if (!(f >= 0 && f < h->rB && top >= 0 && top < bottom && bottom <= h->rH && left >= 0 && left < right && right <= h->rW) ||
+            bottom - top > 65535 || right - left > 65535)
+            return fail(h, FRP_ERR_INVALID, w + ": rectangle " + std::to_string(i) + " (frame " + std::to_string(f) + ", top " +
+                        std::to_string(top) + ", right " + std::to_string(right) + ", bottom " + std::to_string(bottom) + ", left " +
+                        std::to_string(left) + ") is empty or outside the " + std::to_string(h->rB) + " resident frames of " +
+                        std::to_string(h->rH) + " x " + std::to_string(h->rW));
+        JpegEncImage& I = img[(size_t)i];
+        I = JpegEncImage{};
+        I.frame = f; I.top = top; I.left = left; I.h = bottom - top; I.w = right - left;
+        I.mx = (I.w + 8 * hs - 1) / (8 * hs);
+        I.my = (I.h + 8 * vs - 1) / (8 * vs);
+        const long long mcus = (long long)I.mx * I.my;
+        I.n_int = restart_mcus ? (int)((mcus + restart_mcus - 1) / restart_mcus) : 1;
+        I.int0 = (int)ints;
+        I.blk0 = blocks;
+        blocks += mcus * (hs * vs + 2);
+        ints += I.n_int;
+        if (blocks >= (1LL << 26) || ints >= (1LL << 26)) return fail(h, FRP_ERR_INVALID, w + ": more than 2^26 blocks or restart intervals in one call");
+    }
+    p = JpegEncParams{};
+    p.frames = (const uint8_t*)h->frames.p;
+    p.B = h->rB; p.H = h->rH; p.W = h->rW;
+    p.total_bytes = (long long)h->rB * h->rH * h->rW * 3;
+    p.rgb_in = (flags & FRP_FLAG_RGB) ? 1 : 0;
+    p.n = n;
+    p.hs = hs; p.vs = vs;
+    p.ri = restart_mcus;
+    p.n_blocks = blocks;
+    p.n_int = ints;
+    return FRP_OK;
+}
+
+// rectangles + tables (+ room for the scans' places) to the device, the coefficient buffer; queues the forward half
+int forward(frp_handle* h, const std::vector<JpegEncImage>& img, int quality, JpegEncParams& p, std::vector<uint8_t>& up) {
+    const size_t img_bytes = align16(img.size() * sizeof(JpegEncImage)), tab_bytes = align16(sizeof(JpegEncTables));
+    up.assign(img_bytes + tab_bytes, 0);
+    std::memcpy(up.data(), img.data(), img.size() * sizeof(JpegEncImage));
+    JpegEncTables t;
+    build_tables(quality, t);
+    std::memcpy(up.data() + img_bytes, &t, sizeof(t));
+    FRPCHK(ensure(h, h->jenc_in, up.size() + align16(img.size() * sizeof(unsigned long long))));
+    FRPCHK(ensure(h, h->jenc_coef, (size_t)p.n_blocks * 64 * sizeof(int16_t)));
+    uint8_t* in = (uint8_t*)h->jenc_in.p;
+    p.img = (const JpegEncImage*)in;
+    p.tab = (const JpegEncTables*)(in + img_bytes);
+    p.scan_base = (const unsigned long long*)(in + img_bytes + tab_bytes);
+    p.coef = (int16_t*)h->jenc_coef.p;
+    HIPCHK(h, hipMemcpyAsync(h->jenc_in.p, up.data(), up.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_jpeg_enc_forward(p, h->stream));
+    return FRP_OK;
+}
+
+// after a failed step: nothing of this call stays queued behind the caller's buffers
+int drain(frp_handle* h, int rc) {
+    (void)hipStreamSynchronize(h->stream);
+    settle_events(h, true);
+    return rc;
+}
+
+int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags, uint8_t* out,
+           int64_t out_cap, int64_t* offsets) {
+    std::vector<JpegEncImage> img;
+    std::vector<uint8_t> up;
+    JpegEncParams p;
+    FRPCHK(plan(h, "encode_jpeg", rects, n, quality, subsampling, restart_mcus, flags, img, p));
+    if (out_cap < 0) return fail(h, FRP_ERR_INVALID, "encode_jpeg: out_cap < 0");
+    if (!offsets) return fail(h, FRP_ERR_INVALID, "encode_jpeg: null offsets");
+    if (n == 0) {
+        offsets[0] = 0;
+        return FRP_OK;
+    }
+    FRPCHK(forward(h, img, quality, p, up));
+    // the work arrays of the entropy half, carved out of one allocation
+    const size_t nb = (size_t)p.n_blocks, ni = (size_t)p.n_int;
+    const size_t groups = jpeg_enc_scan_groups((long long)std::max(nb, ni)) + 64;      // (the 0xFF chunks are fewer than the blocks: see n_words)
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t at = off; off += align16(bytes); return at; };
+    const size_t o_bits = carve(nb * 4), o_pre = carve((nb + 1) * 8), o_grp = carve(groups * 8), o_iw = carve((ni + 1) * 8), o_ib = carve(ni * 4),
+                 o_if = carve(ni * 8), o_io = carve(ni * 4), o_ip = carve((ni + 1) * 8), o_img = carve(((size_t)n + 1) * 8);
+    FRPCHK(ensure(h, h->jenc_work, off));
+    uint8_t* wk = (uint8_t*)h->jenc_work.p;
+    p.blk_bits = (uint32_t*)(wk + o_bits);
+    p.bit_prefix = (unsigned long long*)(wk + o_pre);
+    p.group_tot = (unsigned long long*)(wk + o_grp);
+    p.int_word = (unsigned long long*)(wk + o_iw);
+    p.int_bytes = (uint32_t*)(wk + o_ib);
+    p.int_ff0 = (unsigned long long*)(wk + o_if);
+    p.int_outb = (uint32_t*)(wk + o_io);
+    p.int_out = (unsigned long long*)(wk + o_ip);
+    p.img_off = (unsigned long long*)(wk + o_img);
+    // 1. bits per block and their prefix sums: the size of the unstuffed stream
+    unsigned long long total_bits = 0;
+    hipError_t e = launch_jpeg_enc_measure(p, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total_bits, p.bit_prefix + nb, sizeof(total_bits), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg measure: ") + hipGetErrorString(e)));
+    // a block codes at most 20 + 63 * 26 bits: anything beyond that is not a size
+    if (total_bits > (unsigned long long)nb * 1658ull) return drain(h, fail(h, FRP_ERR_HIP, "encode_jpeg: implausible bit count"));
+    // 2. the stream in words (every interval starts on a word of its own), 0xFF counts per chunk, the intervals' places
+    p.n_words = (total_bits >> 5) + ni + 1;
+    p.n_chunks = (long long)((p.n_words + JE_CHUNK_WORDS - 1) / JE_CHUNK_WORDS);
+    if (jpeg_enc_scan_groups(p.n_chunks) > groups) return drain(h, fail(h, FRP_ERR_INVALID, "encode_jpeg: stream too long"));
+    const size_t words_bytes = align16((size_t)p.n_words * 4), chunk_bytes = align16((size_t)p.n_chunks * 4);
+    int rc = ensure(h, h->jenc_bits, words_bytes + chunk_bytes + align16(((size_t)p.n_chunks + 1) * 8));
+    if (rc != FRP_OK) return drain(h, rc);
+    uint8_t* bw = (uint8_t*)h->jenc_bits.p;
+    p.words = (uint32_t*)bw;
+    p.ff_chunk = (uint32_t*)(bw + words_bytes);
+    p.ff_prefix = (unsigned long long*)(bw + words_bytes + chunk_bytes);
+    std::vector<unsigned long long> scan_off((size_t)n + 1);
+    e = hipMemsetAsync(p.words, 0, words_bytes, h->stream);
+    if (e == hipSuccess) e = launch_jpeg_enc_pack(p, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(scan_off.data(), p.img_off, scan_off.size() * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg pack: ") + hipGetErrorString(e)));
+    // 3. the files' places: headers + scan + EOI each
+    std::vector<std::vector<uint8_t>> hdr((size_t)n);
+    std::vector<unsigned long long> scan_base((size_t)n);
+    int64_t at = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        hdr[(size_t)i] = headers(img[(size_t)i].w, img[(size_t)i].h, quality, p.hs, p.vs, restart_mcus);
+        const unsigned long long scan = scan_off[(size_t)i + 1] - scan_off[(size_t)i];
+        // stuffing at most doubles a stream, and every interval adds a marker: anything beyond that is not a size
+        if (scan_off[(size_t)i + 1] < scan_off[(size_t)i] || scan > 2ull * ((total_bits >> 3) + 4ull * ni) + 16)
+            return drain(h, fail(h, FRP_ERR_HIP, "encode_jpeg: implausible scan size"));
+        offsets[i] = at;
+        scan_base[(size_t)i] = (unsigned long long)at + hdr[(size_t)i].size();
+        at += (int64_t)(hdr[(size_t)i].size() + scan + 2);
+    }
+    offsets[n] = at;
+    if (at > out_cap) return drain(h, fail(h, FRP_ERR_INVALID, "encode_jpeg: the files take " + std::to_string(at) + " bytes, out_cap is " + std::to_string(out_cap)));
+    if (!out) return drain(h, fail(h, FRP_ERR_INVALID, "encode_jpeg: null out"));
+    rc = ensure(h, h->jenc_out, (size_t)at);
+    if (rc != FRP_OK) return drain(h, rc);
+    p.out = (uint8_t*)h->jenc_out.p;
+    p.out_bytes = (unsigned long long)at;
+    e = hipMemcpyAsync((void*)p.scan_base, scan_base.data(), scan_base.size() * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = launch_jpeg_enc_emit(p, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, p.out, (size_t)at, hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg emit: ") + hipGetErrorString(e)));
+    if (e2 != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg sync: ") + hipGetErrorString(e2)));
+    for (int32_t i = 0; i < n; ++i) {                        // the host's part of every file: what precedes the scan, and EOI
+        std::memcpy(out + offsets[i], hdr[(size_t)i].data(), hdr[(size_t)i].size());
+        out[offsets[i + 1] - 2] = 0xFF;
+        out[offsets[i + 1] - 1] = 0xD9;
+    }
+    settle_events(h, true);
+    return FRP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t frp_jpeg_encode_headers(int32_t width, int32_t height, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint8_t* out, int64_t cap) {
+    int hs = 0, vs = 0;
+    if (width < 1 || width > 65535 || height < 1 || height > 65535 || quality < 1 || quality > 100 || !sampling_ok(subsampling, hs, vs) ||
+        restart_mcus < 0 || restart_mcus > 65535 || !out || cap < 0)
+        return FRP_ERR_INVALID;
+    const std::vector<uint8_t> b = headers(width, height, quality, hs, vs, restart_mcus);
+    if ((int64_t)b.size() > cap) return FRP_ERR_INVALID;
+    std::memcpy(out, b.data(), b.size());
+    return (int64_t)b.size();
+}
+
+int frp_encode_jpeg(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint32_t flags,
+                    uint8_t* out, int64_t out_cap, int64_t* offsets) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);      // queued behind whatever pass is pending; its stage events are read after this call's own wait
+    return encode(h, rects, n, quality, subsampling, restart_mcus, flags, out, out_cap, offsets);
+}
+
+int frp_encode_jpeg_coefficients(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, uint32_t flags,
+                                 int16_t* coef, int64_t coef_elems) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);
+    std::vector<JpegEncImage> img;
+    std::vector<uint8_t> up;
+    JpegEncParams p;
+    FRPCHK(plan(h, "encode_jpeg_coefficients", rects, n, quality, subsampling, 0, flags, img, p));
+    if (n == 0) return FRP_OK;
+    if (!coef || coef_elems != p.n_blocks * 64)
+        return fail(h, FRP_ERR_INVALID, "encode_jpeg_coefficients: the rectangles have " + std::to_string(p.n_blocks * 64) + " coefficients, coef_elems is " +
+                    std::to_string(coef_elems));
+    FRPCHK(forward(h, img, quality, p, up));
+    hipError_t e = hipMemcpyAsync(coef, p.coef, (size_t)coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("encode_jpeg_coefficients: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("encode_jpeg_coefficients sync: ") + hipGetErrorString(e2));
+    settle_events(h, true);
+    return FRP_OK;
+}
+
+}  // extern "C"

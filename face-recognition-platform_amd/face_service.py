@@ -250,6 +250,48 @@ class FaceService:
         return [self.quality_from_sums((H, W, 3), loc, (loc[2] - loc[0]) * (loc[1] - loc[3]), next(sums)) if ok else on_host(b, loc)
                 for (b, loc), ok in zip(faces, on_dev)]
 
+    # ------------------------------------------------------------------ pictures back out (routes/camera.py:73-87,148-149)
+    def snapshot_jpeg(self, frame: int = 0, quality: int = 95) -> Optional[bytes]:
+        """the /snapshot route's cv2.imencode('.jpg', frame, [IMWRITE_JPEG_QUALITY, q]) for a frame that is RESIDENT on the engine
+        (BGR, as the camera loop uploads it), encoded on the device.  None, and a log line, when it cannot be encoded."""
+        try:
+            eng = self._eng()
+            with self._sequence_of(eng):
+                _, H, W = eng._resident
+                return eng.encode_jpeg([(int(frame), 0, W, H, 0)], quality=quality)[0]
+        except Exception as e:
+            logger.exception("Error encoding snapshot of frame %s: %s", frame, e)
+            return None
+
+    def encode_frames(self, quality: int = 95) -> List[bytes]:
+        """every resident frame as a JPEG (gen_frames_from_cap's cv2.imencode per frame; mjpeg.multipart_part frames one for /feed),
+        in one device call.  [] and a log line on failure."""
+        try:
+            eng = self._eng()
+            with self._sequence_of(eng):
+                B, H, W = eng._resident
+                return eng.encode_jpeg([(b, 0, W, H, 0) for b in range(B)], quality=quality)
+        except Exception as e:
+            logger.exception("Error encoding the resident frames: %s", e)
+            return []
+
+    def face_thumbnails(self, faces: List[Tuple[int, Tuple[int, int, int, int]]], margin: float = 0.0, quality: int = 95) -> List[bytes]:
+        """JPEG crops of `faces` = [(frame index, (top, right, bottom, left))] out of the resident frames, each grown by `margin`
+        times its height / width on every side and clipped to the frame; one device call.  [] and a log line on failure (a face
+        that clipping leaves empty is one)."""
+        try:
+            eng = self._eng()
+            with self._sequence_of(eng):
+                _, H, W = eng._resident
+                rects = []
+                for b, (top, right, bottom, left) in faces:
+                    dy, dx = int(round(margin * (bottom - top))), int(round(margin * (right - left)))
+                    rects.append((int(b), max(0, int(top) - dy), min(W, int(right) + dx), min(H, int(bottom) + dy), max(0, int(left) - dx)))
+                return eng.encode_jpeg(rects, quality=quality) if rects else []
+        except Exception as e:
+            logger.exception("Error encoding face thumbnails: %s", e)
+            return []
+
     def encode_face(self, image_path_or_array, return_locations: bool = False, return_quality: bool = False) -> Dict[str, Any]:
         """return_quality: a "quality" list parallel to "encodings" - assess_face_quality of every face at its location, the pixel
         half computed on the device from the frames the pass left resident (routes/face.py:199-217 calls the two back to back)"""

@@ -402,6 +402,12 @@ def write_avi(frames: Sequence[bytes], hw: Tuple[int, int], fps: int = 25) -> by
     return b"RIFF" + struct.pack("<I", len(body)) + body
 
 
+def multipart_part(jpeg: bytes) -> bytes:
+    """one part of the reference's multipart /feed response (gen_frames_from_cap, routes/camera.py:73-87; the response's
+    mimetype is multipart/x-mixed-replace; boundary=frame): what the route yields per encoded frame"""
+    return b"--frame\r\nContent-Type: image/jpeg\r\n\r\n" + bytes(jpeg) + b"\r\n"
+
+
 def write_multipart(frames: Sequence[bytes], boundary: bytes = b"frpframe", with_length: bool = True) -> bytes:
     """the body an IP camera sends for `multipart/x-mixed-replace; boundary=...`: tests and tools only"""
     out = bytearray()

@@ -26,6 +26,7 @@ MAX_FACES_CAP = 128
 MAX_TOPK = 64
 FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN = 1, 2, 4, 8
 F32, F16, F64 = 0, 1, 2
+JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}      # include/frp.h: FRP_JPEG_420, FRP_JPEG_444
 QUALITY_TILE_H, QUALITY_TILE_W = 32, 64      # csrc/frp_internal.h: one workgroup of the face-quality kernel covers this much of a crop
 
 ABI_SYMBOLS = [
@@ -37,7 +38,7 @@ ABI_SYMBOLS = [
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -108,6 +109,22 @@ def jpeg_coefficients(data: bytes):
     if rc != 0:
         raise FrpError(rc, "corrupt JPEG scan data")
     return info, coef, q
+
+
+def _subsampling_code(subsampling) -> int:
+    """"4:2:0" / "4:4:4" -> the library's constant; anything else goes through as -1 for the library to refuse"""
+    return JPEG_SUBSAMPLING.get(subsampling, -1)
+
+
+def jpeg_encode_headers(width: int, height: int, quality: int = 95, subsampling: str = "4:2:0", restart_mcus: int = 0) -> bytes:
+    """the segments the encoder puts in front of a scan - SOI, APP0, DQT x 2, SOF0, DHT x 4, DRI (restart_mcus > 0), SOS: include/frp.h
+    frp_jpeg_encode_headers.  Needs no GPU."""
+    buf = np.zeros(1024, np.uint8)
+    n = load_library().frp_jpeg_encode_headers(int(width), int(height), int(quality), _subsampling_code(subsampling), int(restart_mcus),
+                                               _ptr(buf), buf.size)
+    if n < 0:
+        raise FrpError(int(n), "jpeg_encode_headers: argument out of range")
+    return buf[:n].tobytes()
 
 
 class FrpError(RuntimeError):
@@ -206,6 +223,11 @@ def load_library() -> C.CDLL:
         lib.frp_fetch_within.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     if hasattr(lib, "frp_face_quality"):     # (as above: an older A/B partner build has none)
         lib.frp_face_quality.argtypes = [vp, vp, i32, u32, vp]
+    if hasattr(lib, "frp_encode_jpeg"):      # (as above)
+        lib.frp_jpeg_encode_headers.argtypes = [i32, i32, i32, i32, i32, vp, i64]
+        lib.frp_jpeg_encode_headers.restype = i64
+        lib.frp_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, u32, vp, i64, vp]
+        lib.frp_encode_jpeg_coefficients.argtypes = [vp, vp, i32, i32, i32, u32, vp, i64]
     lib.frp_conv2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.frp_conv2d_f8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp]
     if hasattr(lib, "frp_kstep_lab"):            # the FRP_LAB build (libfrp_lab.so, include/frp_lab.h): tuning hooks
@@ -647,6 +669,37 @@ class Engine:
         sums = np.zeros((r.shape[0], 4), np.int64)
         self._chk(self._lib.frp_face_quality(self._h, _ptr(r), r.shape[0], FLAG_RGB if rgb else 0, _ptr(sums)))
         return sums
+
+    def encode_jpeg(self, rects, quality: int = 95, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False):
+        """baseline JPEG files of rectangles (frame, top, right, bottom, left) of the RESIDENT frames, as uploaded (rgb: their channel
+        order) -> list[bytes], one complete file per rectangle, byte for byte what libjpeg (PIL, cv2.imencode) writes for those pixels
+        (frp.h: frp_encode_jpeg).  The first call guesses the size; a second one with the reported size follows when it was too small."""
+        r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 5)
+        n = r.shape[0]
+        offsets = np.zeros(n + 1, np.int64)
+        px = int(np.clip((r[:, 3] - r[:, 1]).astype(np.int64), 0, None) @ np.clip((r[:, 2] - r[:, 4]).astype(np.int64), 0, None)) if n else 0
+        cap = 1024 * n + px + 4096
+        for _ in range(2):
+            out = np.empty(cap, np.uint8)
+            rc = self._lib.frp_encode_jpeg(self._h, _ptr(r), n, int(quality), _subsampling_code(subsampling), int(restart_mcus),
+                                           FLAG_RGB if rgb else 0, _ptr(out), cap, _ptr(offsets))
+            if rc == 0 or offsets[n] <= cap:
+                break
+            cap = int(offsets[n])
+        self._chk(rc)
+        return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+
+    def encode_jpeg_coefficients(self, rects, quality: int = 95, subsampling: str = "4:2:0", rgb: bool = False) -> np.ndarray:
+        """parity: the quantised coefficients of the same rectangles before entropy coding (frp.h: frp_encode_jpeg_coefficients) -
+        int16, one image after the other, each in the layout of jpeg_coefficients"""
+        r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 5)
+        f = {"4:2:0": 16, "4:4:4": 8}.get(subsampling, 8)
+        per = 6 if f == 16 else 3
+        n = sum(-(-int(b - t) // f) * -(-int(rt - lf) // f) * per * 64 for _, t, rt, b, lf in r.tolist() if b > t and rt > lf)
+        coef = np.zeros(n, np.int16)
+        self._chk(self._lib.frp_encode_jpeg_coefficients(self._h, _ptr(r), r.shape[0], int(quality), _subsampling_code(subsampling),
+                                                         FLAG_RGB if rgb else 0, _ptr(coef), n))
+        return coef
 
     def match_scores(self, q: np.ndarray) -> np.ndarray:
         """all cosines [M, N].  The output is sized from gallery_size(); the library re-checks that size under

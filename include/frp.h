@@ -321,6 +321,31 @@ int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, in
  * 0 <= frame < B, 0 <= top < bottom <= H, 0 <= left < right <= W. */
 int frp_face_quality(frp_handle* h, const int32_t* rects, int32_t n, uint32_t flags, int64_t* sums);
 
+/* JPEG encoder: rectangles of the RESIDENT frames (as for frp_face_quality) -> baseline JPEG files, one per rectangle, with libjpeg's
+ * integer arithmetic at its defaults (jccolor / jcsample / jfdctint / jcdctmgr, Annex K tables scaled by `quality`, one interleaved
+ * Huffman scan): byte for byte the scan PIL / cv2.imencode writes for the same pixels.
+ * replaces: cv2.imencode('.jpg', frame) of the multipart /feed (routes/camera.py:73-87) and of /snapshot (camera.py:148-149) - and
+ * the 6.2 MB per 1080p frame that had to cross PCIe before a host encoder could run.
+ * subsampling: FRP_JPEG_420 (what cv2 and PIL write by default) or FRP_JPEG_444.  restart_mcus = r > 0: DRI = r MCUs, RSTm markers. */
+#define FRP_JPEG_420 420
+#define FRP_JPEG_444 444
+/* The segments in front of the scan, in PIL's order: SOI, APP0 (JFIF 1.01), DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, DRI (r > 0 only), SOS.
+ * Needs no handle.  Returns the byte count (<= 1024), or FRP_ERR_INVALID - nothing written - when cap is too small or an argument is
+ * out of range (width / height 1..65535, quality 1..100, restart_mcus 0..65535). */
+int64_t frp_jpeg_encode_headers(int32_t width, int32_t height, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint8_t* out, int64_t cap);
+/* rects [n*5] = frame, top, right, bottom, left, validated as in frp_face_quality (the message names the rectangle); pixels are BGR,
+ * RGB with FRP_FLAG_RGB (the only flag allowed).  out: the n complete files back to back; offsets [n+1]: offsets[i] = where file i
+ * starts, offsets[n] = the total.  When the total exceeds out_cap: FRP_ERR_INVALID, offsets filled, out untouched - call again with
+ * room for offsets[n].  n == 0: FRP_OK, nothing launched.  Any argument out of range: FRP_ERR_INVALID, nothing launched, nothing
+ * written.  Queued on the handle's stream behind a pending pass; waits; the handle's last results stay fetchable. */
+int frp_encode_jpeg(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint32_t flags,
+                    uint8_t* out, int64_t out_cap, int64_t* offsets);
+/* parity: the quantised coefficients of the same rectangles before entropy coding - int16, natural order, per image the layout of
+ * frp_jpeg_coefficients (per component [blocks_y][blocks_x][64] over the MCU-padded grid, components back to back), one image after
+ * the other; coef_elems must be their exact number */
+int frp_encode_jpeg_coefficients(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, uint32_t flags,
+                                 int16_t* coef, int64_t coef_elems);
+
 /* one convolution through the MFMA kernel on host tensors (kernel parity tests):
  * x [N,H,W,Cin] fp16, w [Cout][k][k][Cin] fp16, bias fp32 [Cout] or [9][Cout], out fp16 or fp32
  * flags (0: what the engine would launch for this shape, as set by the environment switches of INTEGRATION.md):

@@ -116,8 +116,12 @@ __global__ __launch_bounds__(256) void align_kernel(AlignParams p) {
     static_assert(kPart * ALIGN_SPLIT == FRP_CHIP_PIX, "chip rows must split evenly");
     for (int i = part * kPart + threadIdx.x; i < (part + 1) * kPart; i += blockDim.x) {
         const int v = i / 112, u = i - v * 112;
-        const float sx = i00 * (float)u + i01 * (float)v + itx;
-        const float sy = i10 * (float)u + i11 * (float)v + ity;
+        // Clamped to the frame plus a border BEFORE the float -> int conversion: landmarks are device data (forced-K decodes whatever
+        // the head holds: NaN, inf, 1e30) and (int)floorf of an out-of-range float, 3 * x0 and y0 + 1 would be undefined.  Both taps of a
+        // clamped coordinate lie outside the image (x0 <= -2 or x0 >= W + 1) exactly as before the clamp: weight 0, no output bit
+        // changes.  fmaxf / fminf return the other operand for NaN, so NaN lands on a bound.
+        const float sx = fminf(fmaxf(i00 * (float)u + i01 * (float)v + itx, -2.f), (float)(p.W + 1));
+        const float sy = fminf(fmaxf(i10 * (float)u + i11 * (float)v + ity, -2.f), (float)(p.H + 1));
         const float fx0 = floorf(sx), fy0 = floorf(sy);
         const int x0 = (int)fx0, y0 = (int)fy0;
         const float ax = sx - fx0, ay = sy - fy0;

@@ -961,6 +961,54 @@ int frp_align(frp_handle* h, const uint8_t* bgr, int32_t H, int32_t W, int64_t r
     return FRP_OK;
 }
 
+// Diagnostic (tests/test_gpu_align_exact.py): the align launch of run_faces - compacted face list, frame of each slot, frame stride, the
+// count on the host or in device memory - on the resident frames, into a scratch buffer of B x K chips filled with 0xFF bytes (fp16
+// NaN: a chip the launch did not write is recognisable) that is copied back whole.  No weights needed, nothing embedded.
+int frp_debug_align_resident(frp_handle* h, const float* kps, const int32_t* counts, int32_t max_faces, uint32_t flags,
+                             int32_t device_count, void* chips_f16, int64_t out_bytes) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "no resident frames (call frp_upload_frames)");
+    if (!kps || !counts || max_faces <= 0 || max_faces > FRP_MAX_FACES_CAP) return fail(h, FRP_ERR_INVALID, "bad face list");
+    const int B = h->rB, K = max_faces;
+    int n = 0;
+    for (int b = 0; b < B; ++b) {
+        if (counts[b] < 0 || counts[b] > K) return fail(h, FRP_ERR_INVALID, "face count out of range");
+        n += counts[b];
+    }
+    const size_t s = (size_t)B * K, bytes = s * FRP_CHIP_PIX * 8 * 2;
+    if (!chips_f16 || out_bytes < (int64_t)bytes) return fail(h, FRP_ERR_INVALID, "chip buffer too small");
+    if (h->last_nfaces < 0) {           // a device-count pass still owns h->nfaces / h_nfaces: settle it first (as run_faces does)
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        FRPCHK(resolve_count(h));
+    }
+    FRPCHK(ensure_results(h, B, K));
+    FRPCHK(ensure(h, h->scratch, bytes));
+    HIPCHK(h, hipMemcpyAsync(h->kps.p, kps, s * 40, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->counts.p, counts, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+    hipError_t e = launch_compact_faces((const int32_t*)h->counts.p, B, K, (int32_t*)h->face_slot.p, (int32_t*)h->nfaces.p, h->stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("compact_faces: ") + hipGetErrorString(e));
+    HIPCHK(h, hipMemsetAsync(h->scratch.p, 0xFF, bytes, h->stream));
+    AlignParams ap{};
+    ap.frames = (const uint8_t*)h->frames.p;
+    ap.B = B; ap.H = h->rH; ap.W = h->rW;
+    ap.row_stride = (long)h->rW * 3;
+    ap.frame_stride = (long)h->rH * h->rW * 3;
+    ap.kps = (const float*)h->kps.p;
+    ap.counts = (const int32_t*)h->counts.p;
+    ap.max_faces = K;
+    ap.face_slot = (const int32_t*)h->face_slot.p;
+    ap.n_faces = device_count ? B * K : n;
+    ap.n_dev = device_count ? (const int32_t*)h->nfaces.p : nullptr;
+    ap.rgb_in = (flags & FRP_FLAG_RGB) ? 1 : 0;
+    ap.chips = (_Float16*)h->scratch.p;
+    e = launch_align(ap, h->stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("align: ") + hipGetErrorString(e));
+    HIPCHK(h, hipMemcpyAsync(chips_f16, h->scratch.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return FRP_OK;
+}
+
 int frp_embed_faces(frp_handle* h, const uint8_t* bgr, int32_t H, int32_t W, int64_t row_stride, const float* kps, int32_t M,
                     uint32_t flags, float* emb) {
     if (!h) return FRP_ERR_INVALID;

@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "frp_gallery_size", "frp_gallery_get", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact",
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
-    "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_embed_aligned", "frp_embed_faces",
+    "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
     "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
@@ -213,6 +213,8 @@ def load_library() -> C.CDLL:
     lib.frp_debug_det_hashes.argtypes = [vp, i32, vp]
     lib.frp_decode_heads.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u32, vp, vp, vp, vp, vp]
     lib.frp_align.argtypes = [vp, vp, i32, i32, i64, vp, i32, u32, vp]
+    if hasattr(lib, "frp_debug_align_resident"):     # (as frp_match_within below: an older A/B partner build has none)
+        lib.frp_debug_align_resident.argtypes = [vp, vp, vp, i32, u32, i32, vp, i64]
     lib.frp_embed_aligned.argtypes = [vp, vp, i32, vp]
     lib.frp_embed_faces.argtypes = [vp, vp, i32, i32, i64, vp, i32, u32, vp]
     lib.frp_match.argtypes = [vp, vp, i32, i32, vp, vp]
@@ -607,6 +609,19 @@ class Engine:
         k = np.ascontiguousarray(kps, dtype=np.float32).reshape(-1, 10)
         out = np.empty((k.shape[0], CHIP, CHIP, 8), dtype=np.float16)
         self._chk(self._lib.frp_align(self._h, _ptr(frames), H, W, rs, _ptr(k), k.shape[0], flags, _ptr(out)))
+        return out
+
+    def align_resident(self, kps: np.ndarray, counts, flags: int = 0, device_count: bool = False) -> np.ndarray:
+        """diagnostic: the pipeline's own align launch on the RESIDENT frames for landmarks kps [B,K,5,2] and counts [B]; device_count:
+        launched for the capacity with the count in device memory.  -> all B*K chips [B*K,112,112,8] fp16: the first sum(counts),
+        frame-major, are the faces; a chip the launch did not write holds 0xFFFF."""
+        B = self._resident[0]
+        k = np.ascontiguousarray(kps, dtype=np.float32)
+        K = k.size // (B * 10)
+        k = k.reshape(B, K, 10)
+        c = np.ascontiguousarray(counts, np.int32).reshape(B)
+        out = np.empty((B * K, CHIP, CHIP, 8), dtype=np.float16)
+        self._chk(self._lib.frp_debug_align_resident(self._h, _ptr(k), _ptr(c), K, flags, 1 if device_count else 0, _ptr(out), out.nbytes))
         return out
 
     def embed_aligned(self, chips_bgr_u8: np.ndarray) -> np.ndarray:

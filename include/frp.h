@@ -286,6 +286,13 @@ int frp_decode_heads(frp_handle* h, const void* head8, const void* head16, const
  * -> insightface norm_crop behind face_encodings (camera.py:237) */
 int frp_align(frp_handle* h, const uint8_t* bgr, int32_t H, int32_t W, int64_t row_stride,
               const float* kps, int32_t M, uint32_t flags, void* chips_f16);
+/* diagnostic: the pipeline's own align launch (compacted face list, frame of each slot, frame stride) on the RESIDENT frames [B,H,W,3]
+ * for caller-supplied landmarks kps [B, max_faces, 10] and counts [B]; no weights needed.  device_count == 0: launched for
+ * sum(counts) faces; != 0: launched for the capacity B * max_faces with the count read from device memory, as the threshold-mode
+ * pipeline does.  chips_f16 receives all B * max_faces chips [112,112,8] fp16 (out_bytes >= that): the first sum(counts), frame-major,
+ * are the aligned faces, every chip behind them holds the fill 0xFFFF (parity tests) */
+int frp_debug_align_resident(frp_handle* h, const float* kps, const int32_t* counts, int32_t max_faces, uint32_t flags,
+                             int32_t device_count, void* chips_f16, int64_t out_bytes);
 /* aligned u8 BGR chips [M,112,112,3] -> unit embeddings [M,512] */
 int frp_embed_aligned(frp_handle* h, const uint8_t* chips, int32_t M, float* emb);
 /* landmarks on one frame -> unit embeddings [M,512] (face_encodings with known faces) */

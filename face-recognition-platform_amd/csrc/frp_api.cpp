@@ -1154,6 +1154,49 @@ int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, in
     return FRP_OK;
 }
 
+// Diagnostic (tests/test_gpu_match_exact.py): run_match on queries handed over as fp16 bits - no normalisation, so a test chooses both
+// operands of every product - with the count on the host (n_device < 0: with `scores` the per-tile kernel and its all_scores epilogue,
+// without what launch_match routes) or in device memory (n_device >= 0: launched for the capacity M, as the threshold-mode pipeline
+// does; refused wherever launch_match has no such form).  The result buffers are filled with 0xFF bytes before the launch and M
+// entries are copied back: an entry no kernel wrote is recognisable.
+int frp_debug_match_f16(frp_handle* h, const void* q_f16, int32_t M, int32_t n_device, int32_t* idx, float* cos, float* scores,
+                        int64_t n_cols) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!q_f16 || !idx || !cos || M <= 0 || M > (1 << 20)) return fail(h, FRP_ERR_INVALID, "bad query arguments");
+    if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
+    if (scores && n_cols != h->g_rows) return fail(h, FRP_ERR_INVALID, "debug_match_f16: output sized for another gallery size");
+    const Switches sw = read_switches();
+    const int mpad = round_up(M, 32);
+    if (n_device >= 0 && (scores || mpad > FRP_MATCH_TOP1_MAX || sw.match_v1 || n_device > M))
+        return fail(h, FRP_ERR_INVALID, "debug_match_f16: no device-count form of this launch");
+    h->q16_of_pass = false;
+    FRPCHK(ensure(h, h->q16, (size_t)mpad * FRP_EMB_DIM * 2));
+    FRPCHK(ensure(h, h->best_cos, (size_t)mpad * 4));
+    FRPCHK(ensure(h, h->best_idx, (size_t)mpad * 4));
+    ScopedBuf all, count;
+    if (scores) FRPCHK(ensure(h, all, (size_t)M * h->g_rows * 4));
+    if (n_device >= 0) FRPCHK(ensure(h, count, 4));
+    HIPCHK(h, hipMemsetAsync(h->q16.p, 0, (size_t)mpad * FRP_EMB_DIM * 2, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->q16.p, q_f16, (size_t)M * FRP_EMB_DIM * 2, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->best_cos.p, 0xFF, (size_t)mpad * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->best_idx.p, 0xFF, (size_t)mpad * 4, h->stream));
+    if (scores) HIPCHK(h, hipMemsetAsync(all->p, 0xFF, (size_t)M * h->g_rows * 4, h->stream));
+    const int32_t n_host = n_device;          // (read by the copy below: alive until the synchronize at the end)
+    hipError_t e = hipSuccess;
+    if (n_device >= 0) e = hipMemcpyAsync(count->p, &n_host, 4, hipMemcpyHostToDevice, h->stream);
+    int rc = e == hipSuccess ? run_match(h, sw, M, (float*)all->p, n_device >= 0 ? (const int32_t*)count->p : nullptr) : FRP_OK;
+    if (rc == FRP_OK && e == hipSuccess) {
+        e = hipMemcpyAsync(idx, h->best_idx.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cos, h->best_cos.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess && scores) e = hipMemcpyAsync(scores, all->p, (size_t)M * h->g_rows * 4, hipMemcpyDeviceToHost, h->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (rc != FRP_OK) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(h, FRP_ERR_HIP, "debug_match_f16: copy failed");
+    return FRP_OK;
+}
+
 int frp_get_counters(frp_handle* h, frp_counters* out) {
     if (!h || !out) return FRP_ERR_INVALID;
     Guard g(h);

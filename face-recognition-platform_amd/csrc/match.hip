@@ -331,8 +331,11 @@ __global__ __launch_bounds__(256) void match_reduce_kernel(MatchParams p) {
         if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
     }
     if (lane == 0) {
-        p.best_cos[q] = best;
-        p.best_idx[q] = bidx == 0x7fffffff ? -1 : bidx;
+        // no row compared greater than the initial best (every score of the query is NaN): -1 / -2.0, the "nothing here" of
+        // topk_rows_kernel and within_sort_kernel (frp.h: frp_match) - the -3.0 the search starts from stays inside the kernels
+        const bool found = bidx != 0x7fffffff;
+        p.best_cos[q] = found ? best : -2.0f;
+        p.best_idx[q] = found ? bidx : -1;
     }
 }
 

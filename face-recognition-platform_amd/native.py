@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -219,6 +219,8 @@ def load_library() -> C.CDLL:
     lib.frp_embed_faces.argtypes = [vp, vp, i32, i32, i64, vp, i32, u32, vp]
     lib.frp_match.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.frp_match_scores.argtypes = [vp, vp, i32, vp, i64]
+    if hasattr(lib, "frp_debug_match_f16"):  # (as frp_match_within below: an older A/B partner build has none)
+        lib.frp_debug_match_f16.argtypes = [vp, vp, i32, i32, vp, vp, vp, i64]
     if hasattr(lib, "frp_match_within"):     # (an older build loaded through FRP_LIB as the A/B partner of tools/ab_bench.sh has none)
         lib.frp_match_within.argtypes = [vp, vp, i32, f32, i32, vp, vp, vp]
         lib.frp_set_within.argtypes = [vp, f32, i32]
@@ -659,6 +661,24 @@ class Engine:
         n_hits = np.empty((M,), np.int32)
         self._chk(self._lib.frp_match_within(self._h, _ptr(q), M, float(min_cos), cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
         return idx, cos, n_hits
+
+    def match_f16(self, q16: np.ndarray, n_device: Optional[int] = None, scores: bool = False):
+        """diagnostic: the matcher on queries given as fp16 bits [M, 512], copied as they are (no normalisation) -> (idx [M], cos [M])
+        or, with scores, (idx, cos, S [M, N]: the per-tile kernel's score matrix).  n_device: launched for the capacity M with that
+        count in device memory (frp.h: frp_debug_match_f16 - refused where the launch has no such form).  The device buffers hold
+        0xFF bytes before the launch: an entry no kernel wrote comes back as idx -1 / cos bits 0xFFFFFFFF."""
+        q = np.ascontiguousarray(q16)
+        if q.dtype != np.float16:
+            raise TypeError("match_f16 takes float16 rows: the bits are the operands")
+        q = q.reshape(-1, EMB_DIM)
+        M = q.shape[0]
+        idx = np.empty((M,), np.int32)
+        cos = np.empty((M,), np.float32)
+        n = self.gallery_size()
+        S = np.empty((M, n), np.float32) if scores else None
+        self._chk(self._lib.frp_debug_match_f16(self._h, _ptr(q), M, -1 if n_device is None else int(n_device), _ptr(idx), _ptr(cos),
+                                                _ptr(S) if scores else None, n))
+        return (idx, cos, S) if scores else (idx, cos)
 
     def set_within(self, min_cos: float, cap: int = 64):
         """bound and list size of the passes that run with FLAG_WITHIN from now on"""

@@ -293,13 +293,23 @@ int frp_align(frp_handle* h, const uint8_t* bgr, int32_t H, int32_t W, int64_t r
  * are the aligned faces, every chip behind them holds the fill 0xFFFF (parity tests) */
 int frp_debug_align_resident(frp_handle* h, const float* kps, const int32_t* counts, int32_t max_faces, uint32_t flags,
                              int32_t device_count, void* chips_f16, int64_t out_bytes);
+/* diagnostic: the matcher on M queries handed over as fp16 bits [M x 512] - copied as they are, NOT normalised - against the gallery.
+ * n_device < 0: the count M is a launch argument; with `scores` (M x n_cols floats, n_cols as in frp_match_scores) the per-tile kernel
+ * and its score matrix, without it the kernel frp_match(topk = 1) would take (FRP_MATCH_V1 is honoured).  n_device >= 0: launched for
+ * the capacity M with the count n_device <= M read from device memory, as the threshold-mode pipeline does; FRP_ERR_INVALID where
+ * that form does not exist (with `scores`, more than 512 queries after rounding up to 32, FRP_MATCH_V1 set).  idx / cos [M]: the
+ * device buffers are filled with 0xFF bytes before the launch, so an entry the kernels did not write reads -1 / 0xFFFFFFFF (parity tests) */
+int frp_debug_match_f16(frp_handle* h, const void* q_f16, int32_t M, int32_t n_device, int32_t* idx, float* cos, float* scores,
+                        int64_t n_cols);
 /* aligned u8 BGR chips [M,112,112,3] -> unit embeddings [M,512] */
 int frp_embed_aligned(frp_handle* h, const uint8_t* chips, int32_t M, float* emb);
 /* landmarks on one frame -> unit embeddings [M,512] (face_encodings with known faces) */
 int frp_embed_faces(frp_handle* h, const uint8_t* bgr, int32_t H, int32_t W, int64_t row_stride,
                     const float* kps, int32_t M, uint32_t flags, float* emb);
 /* cosine top-k (1 <= topk <= FRP_MAX_TOPK) of M queries vs the gallery, ordered by (cosine descending, row
- * ascending): idx / cos are [M x topk]; entries beyond the gallery size are -1 / -2.0
+ * ascending): idx / cos are [M x topk]; entries beyond the gallery size are -1 / -2.0.  A NaN score is never selected: a query
+ * with a NaN or an infinite component (its normalised row holds a NaN) gets -1 / -2.0 in every entry, for topk == 1 as well
+ * (the same "nothing here" as frp_match_within's list tails), and a gallery row that holds a NaN is never returned
  * -> face_recognition.face_distance + argmin / argpartition (face_service.py:410,599-603) */
 int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* idx, float* cos);
 /* all cosines [M x N] (the N-dict compat path of compare_faces, face_service.py:409-432) */

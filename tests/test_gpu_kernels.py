@@ -7,6 +7,8 @@ import torch
 import torch.nn.functional as F
 
 import align_model
+import match_cases as mc
+import match_model as mm
 from conftest import get_raw_and_blob
 from oracle import network as onet
 
@@ -274,25 +276,31 @@ def test_conv_rejects_unsupported_shape(engine):
         engine.conv2d(x, w, np.zeros(32, np.float32))
 
 
-@pytest.mark.parametrize("N,M", [(1000, 5), (128, 1), (4097, 37), (10000, 320), (1, 3)])
+@pytest.mark.parametrize("N,M", mc.PARITY_SHAPES)
 def test_match_parity(engine, N, M):
-    rng = np.random.default_rng(N * 7 + M)
-    G = rng.standard_normal((N, 512)).astype(np.float32)
-    G /= np.linalg.norm(G, axis=1, keepdims=True)
-    planted = rng.integers(0, N, size=M)
-    Q = G[planted] + 0.05 * rng.standard_normal((M, 512)).astype(np.float32) / np.sqrt(512) * 4
-    Q /= np.linalg.norm(Q, axis=1, keepdims=True)
+    """identity against the fp64 oracle on the original operands; rows and scores against tests/match_model.py: the stored rows within
+    normalize_bound of the exact unit rows, every score (and the winner's cosine) within score_bound + the query-rounding term of the
+    float64 product of the rows the device holds and the once-rounded unit queries"""
+    G, Q = mc.parity_inputs(N, M)
     engine.gallery_set(G)
     assert engine.gallery_size() == N
     idx, cos = engine.match(Q)
-    g16 = engine.gallery_get().astype(np.float32)
-    assert np.abs(g16 - G).max() < 1e-3
+    g16 = engine.gallery_get()
+    ok, worst = mm.normalized_within_bound(g16, G)
+    print(f"match_parity {N} x {M}: rows err / bound {worst:.3f}")
+    assert ok, worst
     oidx, ocos = onet.match_topk(G, Q, 1)
     assert np.array_equal(idx, oidx[:, 0])          # identical top-1 identity
-    assert np.abs(cos - ocos[:, 0]).max() < 1e-3    # north_star: within 1e-3 cosine
+    S_ref = mm.scores(g16, mm.to_f16(mm.normalize(Q)))
+    B = mm.public_score_bound(g16, Q)
+    ar = np.arange(M)
+    err = np.abs(cos - S_ref[ar, idx])
+    print(f"match_parity {N} x {M}: cos err / bound {(err / B[ar, idx]).max():.3f}")
+    assert np.all(err <= B[ar, idx])
     if N <= 4097:
         S = engine.match_scores(Q)
-        assert np.abs(S - Q.astype(np.float64) @ G.T.astype(np.float64)).max() < 1e-3
+        print(f"match_parity {N} x {M}: scores err / bound {(np.abs(S - S_ref) / B).max():.3f}")
+        assert np.all(np.abs(S - S_ref) <= B)
 
 
 def test_match_ties_prefer_lower_index(engine):
@@ -578,19 +586,11 @@ def test_fused_stems_agree_with_the_two_kernel_path(engine, monkeypatch):
         assert np.abs(x - y).max() < 4e-3 * scale
 
 
-@pytest.mark.parametrize("N,M,k", [(1000, 5, 7), (4097, 3, 64), (5, 2, 8), (100000, 4, 10)])
+@pytest.mark.parametrize("N,M,k", mc.TOPK_SHAPES)
 def test_match_topk_parity(engine, N, M, k):
     """device top-k (a12, find_k_nearest): same rows in the same order as the oracle's stable argsort
     computed on the fp16-rounded operands the device holds; duplicate rows exercise the tie rule."""
-    rng = np.random.default_rng(N + 31 * k)
-    G = rng.standard_normal((N, 512)).astype(np.float32)
-    G /= np.linalg.norm(G, axis=1, keepdims=True)
-    if N >= 1000:
-        G[700] = G[3]                       # exact duplicates: the lower row must come first
-        G[701] = G[3]
-    Q = G[rng.integers(0, N, size=M)] + 0.3 * rng.standard_normal((M, 512)).astype(np.float32) / np.sqrt(512)
-    if N >= 1000:
-        Q[0] = G[3]
+    G, Q = mc.topk_inputs(N, M, k)          # (N >= 1000: rows 700 and 701 duplicate row 3, query 0 is row 3)
     engine.gallery_set(G)
     idx, cos = engine.match(Q, topk=k)
     assert idx.shape == (M, k) and cos.shape == (M, k)
@@ -600,9 +600,14 @@ def test_match_topk_parity(engine, N, M, k):
     assert np.array_equal(idx[:, :kk], oidx)
     assert np.array_equal(cos[:, :kk], np.take_along_axis(S, oidx, axis=1))
     assert np.all(idx[:, kk:] == -1) and np.all(cos[:, kk:] == -2.0)
-    # and against the fp64 oracle on the original operands: same identities where the margin exceeds fp16 noise
-    o2, c2 = onet.match_topk(G, Q / np.linalg.norm(Q, axis=1, keepdims=True), kk)
-    assert np.abs(cos[:, :kk] - c2).max() < 3e-3
+    # and against the float64 reference (tests/match_model.py) on the rows the device holds and the once-rounded unit queries: each
+    # listed cosine within the derived bound of its row's score, and the j-th listed cosine within the largest bound of the query of
+    # the reference's j-th best score (elementwise errors <= b move an order statistic by <= max b)
+    S_ref = mm.scores(engine.gallery_get(), mm.to_f16(mm.normalize(Q)))
+    B = mm.public_score_bound(engine.gallery_get(), Q)
+    assert np.all(np.abs(cos[:, :kk] - np.take_along_axis(S_ref, idx[:, :kk].astype(np.int64), axis=1))
+                  <= np.take_along_axis(B, idx[:, :kk].astype(np.int64), axis=1))
+    assert np.all(np.abs(cos[:, :kk] - (-np.sort(-S_ref, axis=1))[:, :kk]) <= B.max(1, keepdims=True))
     i1, c1 = engine.match(Q)                # top-1 path agrees with column 0
     assert np.array_equal(i1, idx[:, 0])
     if N >= 1000:
@@ -610,30 +615,23 @@ def test_match_topk_parity(engine, N, M, k):
 
 
 @pytest.mark.selfcheck
-@pytest.mark.parametrize("N,M", [(1, 1), (31, 5), (1000, 33), (4097, 320), (70001, 512), (300, 513)])
+@pytest.mark.parametrize("N,M", mc.RUNNING_BEST_SHAPES)
 def test_match_running_best_kernel_equals_per_tile_kernel(engine, monkeypatch, N, M):
     """the persistent top-1 kernel (running winners in registers, M <= 512) and the per-tile kernel (FRP_MATCH_V1=1; also
     what M = 513 falls back to) return the same bits: same winner, same cosine, ties to the lower row - including
     galleries smaller than one block, ragged last blocks and duplicate rows spread over blocks, waves and workgroups"""
-    rng = np.random.default_rng(N * 1000 + M)
-    G = rng.standard_normal((N, 512)).astype(np.float32)
-    if N > 64:
-        G[N - 1] = G[7]                      # duplicates far apart: the lower row must win
-        G[N // 2] = G[7]
+    G, Q = mc.running_best_inputs(N, M)      # (N > 64: rows N // 2 and N - 1 duplicate row 7 - the lower row must win - and query 0 is row 7)
     engine.gallery_set(G)
-    Q = rng.standard_normal((M, 512)).astype(np.float32)
-    if N > 64:
-        Q[0] = G[7]
     a_idx, a_cos = engine.match(Q)
     monkeypatch.setenv("FRP_MATCH_V1", "1")
     b_idx, b_cos = engine.match(Q)
     assert np.array_equal(a_idx, b_idx) and np.array_equal(a_cos.view(np.uint32), b_cos.view(np.uint32))
     if N > 64:
         assert a_idx[0] == 7
-    g16 = engine.gallery_get().astype(np.float64)
-    qn = Q.astype(np.float64) / np.linalg.norm(Q.astype(np.float64), axis=1, keepdims=True)
-    S = qn.astype(np.float16).astype(np.float64) @ g16.T
-    assert np.abs(a_cos - S.max(1)).max() < 1e-3
+    # the winner's cosine against the float64 reference (tests/match_model.py): elementwise errors <= b move the maximum by <= max b
+    g16 = engine.gallery_get()
+    S = mm.scores(g16, mm.to_f16(mm.normalize(Q)))
+    assert np.all(np.abs(a_cos - S.max(1)) <= mm.public_score_bound(g16, Q).max(1))
 
 
 def test_match_topk_rejects_bad_k(engine):
@@ -1034,8 +1032,7 @@ def test_every_way_to_install_a_gallery_snapshot_agrees(engine):
     (fp16 rounding of unit rows: 2^-12 per value), and the exact copy holds the host rows widened bit for bit, or - rows that
     came from the device - the unit fp16 rows widened.  40 rows: every path is row-independent."""
     from frp_amd import dist as fdist, native
-    rng = np.random.default_rng(23)
-    r32 = (rng.standard_normal((40, 512)) * rng.uniform(0.2, 3.0, (40, 1))).astype(np.float32)
+    r32 = mc.snapshot_rows()
     hosts = {"f32": r32, "f64": r32.astype(np.float64), "f16": r32.astype(np.float16)}
     unit = fdist.normalize_rows_f16(r32)
     first = native.Engine(0)
@@ -1067,7 +1064,11 @@ def test_every_way_to_install_a_gallery_snapshot_agrees(engine):
                 wide = rows.astype(np.float64)
                 err = np.abs(got[name].astype(np.float64) - wide / np.linalg.norm(wide, axis=1, keepdims=True)).max()
                 print(f"exact={exact} {name}: max |snapshot - normalised rows| = {err:.3e}")
-                assert err < 1e-3
+                if name == "f16":
+                    assert err < 1e-3
+                else:                      # fp32 / fp64 rows: normalize_rows_kernel on the fp32 values, held to its derived bound
+                    ok, worst = mm.normalized_within_bound(got[name], rows)
+                    assert ok, worst
                 if exact:
                     assert np.array_equal(engine.gallery_get_exact(), wide)
             assert got["f32"].tobytes() == got["f64"].tobytes()

@@ -38,7 +38,8 @@ Switches frp::read_switches() {
 const ProcessSwitches& frp::process_switches() {
     static const ProcessSwitches s = [] {
         const char* jh = getenv("FRP_JPEG_DEVICE_HUFFMAN");
-        return ProcessSwitches{getenv("FRP_NO_GRAPH") != nullptr, getenv("FRP_C64_ALL") != nullptr, !jh ? 0 : (jh[0] == '0' ? -1 : 1)};
+        const char* js = getenv("FRP_JPEG_SELFSYNC");
+        return ProcessSwitches{getenv("FRP_NO_GRAPH") != nullptr, getenv("FRP_C64_ALL") != nullptr, !jh ? 0 : (jh[0] == '0' ? -1 : 1), js && js[0] != '0'};
     }();
     return s;
 }

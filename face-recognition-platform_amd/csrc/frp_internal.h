@@ -19,6 +19,7 @@
 #endif
 
 #include "jpeg_host.h"
+#include "jpeg_selfsync.h"
 
 namespace frp {
 
@@ -49,6 +50,8 @@ struct ProcessSwitches {
     bool c64_all;              // FRP_C64_ALL set: the 64 -> 64 kernel on every eligible shape (CONV_DBG_C64_ALL), also where it does not pay
     int jpeg_device_huffman;   // FRP_JPEG_DEVICE_HUFFMAN: entropy decode of restart-interval JPEGs on the device; unset (0): for intervals of
                                // at most 32 MCUs, "0..." (-1): never, any other value (1): always (upload_jpeg_device)
+    bool jpeg_selfsync;        // FRP_JPEG_SELFSYNC set and not "0...": new handles decode JPEG batches without restart markers on the device
+                               // (the self-synchronising decoder; frp_set_jpeg_selfsync changes it per handle)
 };
 const ProcessSwitches& process_switches();
 
@@ -248,6 +251,32 @@ struct JpegHuffParams {
     long comp_off[3];                // first coefficient of each component inside an image
 };
 hipError_t launch_jpeg_huffman(const JpegHuffParams& p, hipStream_t stream);
+
+// Entropy decoding ON THE DEVICE for streams WITHOUT restart markers: the self-synchronising decoder (jpeg_selfsync.h has the algorithm and
+// the per-thread routines, jpeg_selfsync.hip the kernels).  One thread per subsequence of S raw bytes, JSS_WG subsequences per workgroup;
+// per image n_sub = ceil(scan bytes / S) subsequences, numbered from sub0 (a multiple of JSS_WG) in the state arrays.
+struct JpegSelfsyncParams {
+    const uint8_t* scan;             // the scans of all images, each at an offset that is a multiple of 16
+    const uint32_t* img;             // [B][4]: byte offset of the scan, its bytes, n_sub, sub0
+    const JpegHuffTableDev* tables;  // [B][6]: component c's DC table at 2c, its AC table at 2c + 1
+    JssState* entry;                 // [N] entry state of every subsequence (N = all images' subsequences, each image rounded up to JSS_WG)
+    JssState* exit_;                 // [N] ... its exit state
+    JssState* wgx;                   // [2][N / JSS_WG] exit of every workgroup's last subsequence: launch k reads half k & 1, writes the other
+    uint32_t* cnt;                   // [N] blocks completed
+    uint32_t* base;                  // [N] blocks completed by the subsequences before it = its first block
+    int32_t* rounds;                 // [B] most rounds with a change among the image's workgroups in this launch (zeroed before it)
+    int32_t* stats;                  // [B][4]: subsequences, -, blocks counted (at most the total), error flag (zeroed before the first launch)
+    int16_t* coef;                   // out: [B][coef_per_image], natural order (zeroed before the launch)
+    long coef_per_image;
+    int B, S;
+    uint32_t max_sub;                // largest n_sub of the batch
+    uint32_t n_wg_all;               // N / JSS_WG
+    JssGeom g;
+};
+// launch k of the synchronisation (k = 0: speculate from the guessed states); the caller repeats it until a launch reports no round
+hipError_t launch_jpeg_selfsync_round(const JpegSelfsyncParams& p, int k, hipStream_t stream);
+// at the fix-point: block prefix sums, coefficients (DC differences), DC running sums
+hipError_t launch_jpeg_selfsync_finish(const JpegSelfsyncParams& p, hipStream_t stream);
 
 // u8 bilinear resize for the detection pyramid (frames [B,H,W,3] tightly packed)
 hipError_t launch_tensor_hash(const void* src, size_t bytes, unsigned long long* slot, hipStream_t stream);

@@ -14,6 +14,7 @@ using namespace frp;
 
 bool frp::init_ingest(frp_handle* h) {
     Ingest& in = h->in;
+    in.jpeg_selfsync = process_switches().jpeg_selfsync;
     // The copy stream gets its own PRIORITY class: the runtime multiplexes the streams of one class onto a few hardware
     // queues (4 by default), and next to torch's and RCCL's streams in the process the staged upload shared a queue with
     // the compute stream and serialised behind the step's kernels (overlapped loop 18.7-20.6 instead of 14.7 ms per
@@ -31,7 +32,7 @@ bool frp::init_ingest(frp_handle* h) {
 
 void frp::release_ingest(frp_handle* h) {       // (frp_destroy has waited for both streams)
     Ingest& in = h->in;
-    for (DevBuf* b : {&in.frames_next, &in.jpeg_coef, &in.jpeg_planes, &in.jpeg_scan, &in.jpeg_err}) release(*b);
+    for (DevBuf* b : {&in.frames_next, &in.jpeg_coef, &in.jpeg_planes, &in.jpeg_scan, &in.jpeg_err, &in.jpeg_ss}) release(*b);
     for (void* p : in.pinned) (void)hipHostFree(p);
     for (void* p : in.jpeg_pin)
         if (p) (void)hipHostFree(p);
@@ -106,6 +107,118 @@ int launch_pixels(frp_handle* h, JpegParams p, size_t q_off) {
     p.frames = (uint8_t*)h->in.frames_next.p;
     const hipError_t e = launch_jpeg_decode(p, h->in.copy_stream);
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg decode: ") + hipGetErrorString(e));
+    return FRP_OK;
+}
+
+
+// Subsequence size of the self-synchronising decoder where the caller names none (frp_upload_jpeg_async; subseq_bytes 0 of
+// frp_jpeg_selfsync_coefficients).  32 x 1080p, quality 90: batch resident after 6.84 ms at 64, 7.07 at 128, 6.86 at 256 - the repeats of
+// one setting lie within 0.08 ms, so 64 and 256 tie and 128 is behind both (profiles/r6/jpeg_selfsync.txt).
+constexpr int kJpegSelfsyncDefaultS = 64;
+
+// Entropy decode of a batch WITHOUT restart markers on the device: the self-synchronising decoder (jpeg_selfsync.h, jpeg_selfsync.hip).
+// The host parses headers and finds the end of every scan (jpeg_plan_selfsync_decode); the COMPRESSED scans go to the device, every
+// subsequence of S bytes is decoded speculatively and the synchronisation kernel is launched again while a launch reports a change -
+// launch k leaves workgroups 0 .. k of every image final, so the loop ends within the largest image's workgroups -; then blocks are
+// counted, coefficients written and the DC differences summed.  On FRP_OK in.jpeg_coef holds the batch as the host decoder would have
+// staged it (coefficients, quantisation tables at L.q_off) and the error flags have been read: none is set.  -> FRP_OK, an error (a corrupt
+// stream is reported by this call: "JPEG i: ..."), or 1 = "not this batch" (a frame with restart intervals, scans beyond the 32-bit offsets
+// or 2^24 subsequences in all).  for_frames: the batch is being staged (frp_upload_jpeg_async) - the frame and plane buffers are grown with
+// the others and the copy stream waits for the staging frame buffer.  stats: [B][4] or null (frp.h: frp_jpeg_selfsync_coefficients).
+int selfsync_decode(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, const frp_jpeg_info& I, const JpegBatchLayout& L,
+                    int turn, int S, bool for_frames, int32_t* stats) {
+    if (I.restart_interval != 0) return 1;
+    std::vector<JpegSelfsyncPlan> plans((size_t)B);
+    std::vector<JpegHuffTableDev> tabs((size_t)B * 6);
+    std::vector<size_t> scan_bytes((size_t)B);
+    for (int i = 0; i < B; ++i) {
+        std::string e;
+        if (!jpegs[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": null image");
+        const int rc = jpeg_plan_selfsync_decode(jpegs[i], sizes[i], plans[i], tabs.data() + (size_t)i * 6, &e);
+        if (rc != FRP_OK) {
+            if (plans[i].info.restart_interval != 0 && plans[i].info.width > 0) return 1;          // a frame with intervals: host path for the batch
+            return fail(h, rc, "JPEG " + std::to_string(i) + ": " + e);
+        }
+        if (!same_geometry(plans[i].info, I)) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": " + kGeometryDiffers);
+        scan_bytes[i] = plans[i].scan_bytes;
+    }
+    // staging as for the restart-interval decoder, with four words per image in the place of its interval offsets
+    const JpegDeviceStageLayout SL = jpeg_device_stage_layout(B, 3, scan_bytes.data());
+    if (SL.too_large) return 1;
+    std::vector<uint32_t> img((size_t)B * 4);
+    uint64_t n_all = 0;
+    uint32_t max_sub = 0;
+    for (int i = 0; i < B; ++i) {
+        const uint32_t n_sub = jss_subsequences((uint32_t)scan_bytes[i], (uint32_t)S);
+        img[4 * i] = (uint32_t)SL.soff[i]; img[4 * i + 1] = (uint32_t)scan_bytes[i]; img[4 * i + 2] = n_sub; img[4 * i + 3] = (uint32_t)n_all;
+        n_all += ((uint64_t)n_sub + JSS_WG - 1) / JSS_WG * JSS_WG;
+        max_sub = std::max(max_sub, n_sub);
+        if (n_all > (1u << 24)) return 1;
+    }
+    const size_t N = (size_t)n_all, n_wg_all = N / JSS_WG;
+    Ingest& in = h->in;
+    void* pin = nullptr;
+    const size_t pin_stats = SL.o_err, pin_rounds = pin_stats + (size_t)B * 16;      // read back: [B][4] stats, [B] rounds of a launch
+    FRPCHK(jpeg_staging_turn(h, turn, pin_rounds + (size_t)B * 4, &pin));
+    char* st = (char*)pin;
+    for (int i = 0; i < B; ++i) {
+        memcpy(st + SL.soff[i], plans[i].scan, plans[i].scan_bytes);
+        memcpy(st + SL.o_q + (size_t)i * 384, plans[i].qtab, 384);
+    }
+    memcpy(st + SL.o_int, img.data(), img.size() * 4);
+    memcpy(st + SL.o_tab, tabs.data(), tabs.size() * sizeof(JpegHuffTableDev));
+    // device scratch: entry | exit | wgx (8 bytes each), then cnt | base | rounds (4 bytes each)
+    const size_t o_exit = N * 8, o_wgx = o_exit + N * 8, o_cnt = o_wgx + 2 * n_wg_all * 8, o_base = o_cnt + N * 4, o_rounds = o_base + N * 4;
+    const size_t ss_total = o_rounds + (size_t)B * 4;
+    if (for_frames)
+        FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img},
+                               {&in.jpeg_scan, SL.o_err}, {&in.jpeg_err, (size_t)B * 16}, {&in.jpeg_ss, ss_total}}));
+    else
+        FRPCHK(grow_staged(h, {{&in.jpeg_coef, L.total}, {&in.jpeg_scan, SL.o_err}, {&in.jpeg_err, (size_t)B * 16}, {&in.jpeg_ss, ss_total}}));
+    if (for_frames) FRPCHK(begin_staging(h));
+    HIPCHK(h, hipMemcpyAsync(in.jpeg_scan.p, st, SL.o_err, hipMemcpyHostToDevice, in.copy_stream));
+    HIPCHK(h, hipMemsetAsync(in.jpeg_coef.p, 0, L.q_off, in.copy_stream));
+    HIPCHK(h, hipMemcpyAsync((char*)in.jpeg_coef.p + L.q_off, (char*)in.jpeg_scan.p + SL.o_q, (size_t)B * 384, hipMemcpyDeviceToDevice, in.copy_stream));
+    HIPCHK(h, hipMemsetAsync(in.jpeg_err.p, 0, (size_t)B * 16, in.copy_stream));
+    JpegSelfsyncParams sp{};
+    char* ss = (char*)in.jpeg_ss.p;
+    sp.scan = (const uint8_t*)in.jpeg_scan.p;
+    sp.img = (const uint32_t*)((const char*)in.jpeg_scan.p + SL.o_int);
+    sp.tables = (const JpegHuffTableDev*)((const char*)in.jpeg_scan.p + SL.o_tab);
+    sp.entry = (JssState*)ss; sp.exit_ = (JssState*)(ss + o_exit); sp.wgx = (JssState*)(ss + o_wgx);
+    sp.cnt = (uint32_t*)(ss + o_cnt); sp.base = (uint32_t*)(ss + o_base); sp.rounds = (int32_t*)(ss + o_rounds);
+    sp.stats = (int32_t*)in.jpeg_err.p;
+    sp.coef = (int16_t*)in.jpeg_coef.p;
+    sp.coef_per_image = (long)L.coef_elems;
+    sp.B = B; sp.S = S; sp.max_sub = max_sub; sp.n_wg_all = (uint32_t)n_wg_all;
+    sp.g.components = I.components; sp.g.mcus_x = I.mcus_x;
+    for (int c = 0; c < 3; ++c) { sp.g.hs[c] = I.h_samp[c]; sp.g.vs[c] = I.v_samp[c]; sp.g.bx[c] = L.bx[c]; sp.g.comp_off[c] = L.plane_off[c]; }
+    jss_geom_blocks(sp.g);
+    sp.g.total = (uint32_t)L.blocks_per_image;
+    if (sp.g.bpm > 6 || (long)I.mcus_x * I.mcus_y * sp.g.bpm != (long)L.blocks_per_image) return fail(h, FRP_ERR_INVALID, "JPEG 0: unsupported sampling factors");
+    const int32_t* lr = (const int32_t*)(st + pin_rounds);
+    std::vector<int32_t> rounds((size_t)B, 0);
+    const uint32_t max_wg = (max_sub + JSS_WG - 1) / JSS_WG;
+    for (uint32_t k = 0;; ++k) {
+        if (k > max_wg) return fail(h, FRP_ERR_HIP, "jpeg selfsync: no fix-point within the workgroups of the largest scan");       // (launch k leaves 0 .. k final)
+        HIPCHK(h, hipMemsetAsync(sp.rounds, 0, (size_t)B * 4, in.copy_stream));
+        const hipError_t e = launch_jpeg_selfsync_round(sp, (int)k, in.copy_stream);
+        if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg selfsync: ") + hipGetErrorString(e));
+        HIPCHK(h, hipMemcpyAsync(st + pin_rounds, sp.rounds, (size_t)B * 4, hipMemcpyDeviceToHost, in.copy_stream));
+        HIPCHK(h, hipStreamSynchronize(in.copy_stream));
+        bool changed = false;
+        for (int i = 0; i < B; ++i) { rounds[i] += lr[i]; changed = changed || lr[i] != 0; }
+        if (k == 0 ? max_wg == 1 : !changed) break;            // (one workgroup per image: launch 0 ran to the fix-point)
+    }
+    const hipError_t e = launch_jpeg_selfsync_finish(sp, in.copy_stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg selfsync: ") + hipGetErrorString(e));
+    HIPCHK(h, hipMemcpyAsync(st + pin_stats, in.jpeg_err.p, (size_t)B * 16, hipMemcpyDeviceToHost, in.copy_stream));
+    HIPCHK(h, hipStreamSynchronize(in.copy_stream));   // the flags decide this call's return value (and the staging block is free again: no jpeg_h2d_pending)
+    const int32_t* got = (const int32_t*)(st + pin_stats);
+    if (stats)
+        for (int i = 0; i < B; ++i) { stats[4 * i] = got[4 * i]; stats[4 * i + 1] = rounds[i]; stats[4 * i + 2] = got[4 * i + 2]; stats[4 * i + 3] = got[4 * i + 3]; }
+    for (int i = 0; i < B; ++i)
+        if (got[4 * i + 3]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": corrupt or truncated entropy-coded data");
     return FRP_OK;
 }
 
@@ -273,6 +386,15 @@ int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size
     for (int c = 0; c < 3; ++c) { p.bx[c] = L.bx[c]; p.by[c] = L.by[c]; p.plane_off[c] = L.plane_off[c]; }
     const int dr = upload_jpeg_device(h, jpegs, sizes, B, I, turn, p, L);     // restart-interval streams: entropy decode on the device
     if (dr != 1) return dr;
+    if (in.jpeg_selfsync) {                                                   // frames without restart markers, where the handle asks for it: on the device too
+        const int sr = selfsync_decode(h, jpegs, sizes, B, I, L, turn, in.jpeg_selfsync_bytes ? in.jpeg_selfsync_bytes : kJpegSelfsyncDefaultS, true, nullptr);
+        if (sr == FRP_OK) {
+            FRPCHK(launch_pixels(h, p, L.q_off));
+            FRPCHK(end_staging(h, B, I.height, I.width));
+            in.ctr_jpeg_selfsync_batches += 1;
+        }
+        if (sr != 1) return sr;
+    }
     void* pin = nullptr;
     FRPCHK(jpeg_staging_turn(h, turn, L.total, &pin));
     int16_t* coef = (int16_t*)pin;
@@ -312,6 +434,44 @@ int64_t frp_debug_jpeg_device_batches(frp_handle* h) {
     if (!h) return -1;
     Guard g(h, false);
     return h->in.ctr_jpeg_device_batches;
+}
+
+int frp_set_jpeg_selfsync(frp_handle* h, int32_t on) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);
+    if (on < 0 || (on > 1 && (on < 16 || on > 1024 || on % 16 != 0))) return fail(h, FRP_ERR_INVALID, "frp_set_jpeg_selfsync: 0, 1 or a subsequence size (a multiple of 16 in 16 .. 1024)");
+    h->in.jpeg_selfsync = on != 0;
+    h->in.jpeg_selfsync_bytes = on > 1 ? on : 0;
+    return FRP_OK;
+}
+
+int64_t frp_debug_jpeg_selfsync_batches(frp_handle* h) {
+    if (!h) return -1;
+    Guard g(h, false);
+    return h->in.ctr_jpeg_selfsync_batches;
+}
+
+int frp_jpeg_selfsync_coefficients(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, int32_t subseq_bytes, int16_t* coef,
+                                   int64_t coef_elems, int32_t* stats) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);      // copy stream only (as frp_upload_jpeg_async)
+    if (!jpegs || !sizes || !coef || B <= 0 || B > 1024) return fail(h, FRP_ERR_INVALID, "bad JPEG batch arguments");
+    if (subseq_bytes != 0 && (subseq_bytes < 16 || subseq_bytes > 1024 || subseq_bytes % 16 != 0))
+        return fail(h, FRP_ERR_INVALID, "subseq_bytes must be 0 or a multiple of 16 in 16 .. 1024");
+    frp_jpeg_info I{};
+    std::string err;
+    if (!jpegs[0] || jpeg_info(jpegs[0], sizes[0], &I, &err) != FRP_OK) return fail(h, FRP_ERR_INVALID, "JPEG 0: " + err);
+    const JpegBatchLayout L = jpeg_batch_layout(I, B);
+    if (coef_elems < 0 || (uint64_t)coef_elems < (uint64_t)B * L.coef_elems) return fail(h, FRP_ERR_INVALID, "coefficient buffer too small");
+    Ingest& in = h->in;
+    const int turn = in.jpeg_turn;      // a staging block of its own turn, as every JPEG batch
+    in.jpeg_turn ^= 1;
+    const int r = selfsync_decode(h, jpegs, sizes, B, I, L, turn, subseq_bytes ? subseq_bytes : kJpegSelfsyncDefaultS, false, stats);
+    if (r == 1) return fail(h, FRP_ERR_INVALID, "not a batch of the self-synchronising decoder (a frame carries restart intervals, or the scans are too large)");
+    FRPCHK(r);
+    HIPCHK(h, hipMemcpyAsync(coef, in.jpeg_coef.p, L.coef_bytes, hipMemcpyDeviceToHost, in.copy_stream));
+    HIPCHK(h, hipStreamSynchronize(in.copy_stream));
+    return FRP_OK;
 }
 
 int frp_swap_frames(frp_handle* h) {

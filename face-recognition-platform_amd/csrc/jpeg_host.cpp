@@ -516,4 +516,34 @@ int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& pl
     return FRP_OK;
 }
 
+// Plan of the self-synchronising device decode (scans without restart markers, jpeg_selfsync.h): headers and tables as above; the scan
+// ends where BitReader::fill_slow stops taking bytes.
+int jpeg_plan_selfsync_decode(const uint8_t* data, size_t size, JpegSelfsyncPlan& plan, JpegHuffTableDev* tables6, std::string* err) {
+    JpegHeaderInternal H;
+    const int rc = parse_headers(data, size, H);
+    plan.info = H.info;
+    if (rc != FRP_OK) { if (err) *err = H.err; return rc; }
+    const frp_jpeg_info& I = H.info;
+    if (I.restart_interval != 0) { if (err) *err = "scan has restart intervals"; return FRP_ERR_INVALID; }
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < 64; ++i) plan.qtab[c * 64 + i] = c < I.components ? H.qt[H.comp_tq[c]][i] : 1;
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < I.components ? c : 0;
+        flatten_table(H.dc[H.comp_td[cc]], tables6[2 * c]);
+        flatten_table(H.ac[H.comp_ta[cc]], tables6[2 * c + 1]);
+    }
+    const uint8_t* p = H.scan;
+    const uint8_t* const end = data + size;
+    while (p < end) {
+        p = (const uint8_t*)memchr(p, 0xFF, (size_t)(end - p));
+        if (!p) { p = end; break; }
+        if (p + 1 < end && p[1] == 0x00) { p += 2; continue; }     // stuffed byte
+        break;                                                     // a marker, or a 0xFF as the file's last byte
+    }
+    if ((size_t)(p - H.scan) >= ((size_t)1 << 28)) { if (err) *err = "scan too large"; return FRP_ERR_INVALID; }
+    plan.scan = H.scan;
+    plan.scan_bytes = (size_t)(p - H.scan);
+    return FRP_OK;
+}
+
 }  // namespace frp

@@ -35,6 +35,18 @@ struct JpegDevicePlan {
 };
 int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& plan, JpegHuffTableDev* tables6, std::string* err);
 
+// What the self-synchronising device decoder needs of one image WITHOUT restart intervals (frp_upload_jpeg_async's second device path,
+// jpeg_selfsync.h): headers, the six tables and the quantisation tables as above; the scan ends where the host decoder's bit reader stops
+// taking bytes - at the first 0xFF that is not followed by a stuffed 0x00, or at the end of the file -, so both decoders see the same
+// bytes.  Fails (FRP_ERR_INVALID) for files with restart intervals, for scans of 2^28 bytes or more and for what the host decoder refuses.
+struct JpegSelfsyncPlan {
+    frp_jpeg_info info;
+    uint16_t qtab[192];                 // [3][64] natural order
+    const uint8_t* scan = nullptr;      // first entropy-coded byte
+    size_t scan_bytes = 0;
+};
+int jpeg_plan_selfsync_decode(const uint8_t* data, size_t size, JpegSelfsyncPlan& plan, JpegHuffTableDev* tables6, std::string* err);
+
 #define FRP_JPEG_LOCAL __attribute__((visibility("hidden")))   // for ingest_api.cpp and the test harness: not among the library's exports
 
 // Where a batch of B images of one geometry lies (frp_upload_jpeg_async; plain arithmetic on header fields, so the sanitizer harness

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "frp_create", "frp_destroy", "frp_last_error", "frp_version", "frp_load_weights",
     "frp_gallery_set", "frp_gallery_set_device", "frp_gallery_reserve", "frp_gallery_commit", "frp_gallery_cancel", "frp_gallery_device_ptr", "frp_gallery_update_row", "frp_gallery_remove_row",
     "frp_jpeg_info_get", "frp_jpeg_coefficients", "frp_upload_jpeg_async", "frp_debug_jpeg_device_batches", "frp_debug_graph_replays",
+    "frp_set_jpeg_selfsync", "frp_debug_jpeg_selfsync_batches", "frp_jpeg_selfsync_coefficients",
     "frp_dist_unique_id", "frp_dist_init", "frp_dist_destroy", "frp_gallery_allgather",
     "frp_gallery_size", "frp_gallery_get", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact",
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
@@ -203,6 +204,10 @@ def load_library() -> C.CDLL:
     lib.frp_get_head_map.argtypes = [vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32)]
     lib.frp_debug_jpeg_device_batches.argtypes = [vp]
     lib.frp_debug_jpeg_device_batches.restype = C.c_int64
+    lib.frp_set_jpeg_selfsync.argtypes = [vp, i32]
+    lib.frp_debug_jpeg_selfsync_batches.argtypes = [vp]
+    lib.frp_debug_jpeg_selfsync_batches.restype = C.c_int64
+    lib.frp_jpeg_selfsync_coefficients.argtypes = [vp, vp, vp, i32, i32, vp, i64, vp]
     lib.frp_debug_graph_replays.argtypes = [vp]
     lib.frp_debug_graph_replays.restype = C.c_int64
     lib.frp_dist_unique_id.argtypes = [vp]
@@ -392,6 +397,37 @@ class Engine:
     def jpeg_device_batches(self) -> int:
         """diagnostic: upload_jpeg_async batches whose entropy decode ran on the device (restart-interval streams)"""
         return int(self._lib.frp_debug_jpeg_device_batches(self._h))
+
+    def set_jpeg_selfsync(self, on=True):
+        """upload_jpeg_async batches whose frames carry no restart markers: entropy decode on the device too (the self-synchronising
+        decoder, frp.h: frp_set_jpeg_selfsync) instead of on host threads.  Off by default (FRP_JPEG_SELFSYNC: on for new handles)."""
+        self._chk(self._lib.frp_set_jpeg_selfsync(self._h, int(on)))          # (an int above 1: on, with subsequences of that many bytes)
+
+    def jpeg_selfsync_batches(self) -> int:
+        """diagnostic: upload_jpeg_async batches decoded by the self-synchronising decoder"""
+        return int(self._lib.frp_debug_jpeg_selfsync_batches(self._h))
+
+    def jpeg_selfsync_coefficients(self, jpegs: Sequence[bytes], subseq_bytes: int = 0):
+        """parity: the self-synchronising decode alone -> (coef [B, n] int16: every image in the layout of jpeg_coefficients, stats [B, 4]
+        int32: subsequences, synchronisation rounds, blocks counted, error flag).  A corrupt image raises FrpError naming it; the
+        statistics of that call are then in the error's `stats`."""
+        B = len(jpegs)
+        info = jpeg_info(jpegs[0]) if B else None
+        if info is None:
+            raise FrpError(-1, "JPEG 0: not a baseline JPEG the decoder covers")
+        n = sum(info["mcus_x"] * info["h_samp"][c] * info["mcus_y"] * info["v_samp"][c] * 64 for c in range(info["components"]))
+        coef = np.zeros((B, n), np.int16)
+        stats = np.zeros((B, 4), np.int32)
+        held = [_byte_ptr(j) for j in jpegs]
+        ptrs = (C.c_void_p * B)(*[h[0] for h in held])
+        sizes = (C.c_size_t * B)(*[len(j) for j in jpegs])
+        rc = self._lib.frp_jpeg_selfsync_coefficients(self._h, ptrs, sizes, B, int(subseq_bytes), _ptr(coef), coef.size, _ptr(stats))
+        del held
+        if rc != 0:
+            e = FrpError(rc, (self._lib.frp_last_error(self._h) or b"").decode("utf-8", "replace"))
+            e.stats = stats
+            raise e
+        return coef, stats
 
     def graph_replays(self) -> int:
         """diagnostic: detector / embedder passes replayed from a captured hipGraph so far (frp.h: frp_debug_graph_replays)"""

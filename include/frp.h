@@ -229,6 +229,23 @@ int64_t frp_debug_graph_replays(frp_handle* h);
 /* diagnostic: batches of this handle whose ENTROPY decode ran on the device too (every frame carries restart intervals of at most 32
  * MCUs - one thread per interval; longer intervals: the host decoder, unless FRP_JPEG_DEVICE_HUFFMAN=1; =0: always the host) */
 int64_t frp_debug_jpeg_device_batches(frp_handle* h);
+/* Entropy decode on the device for frames WITHOUT restart markers (what PIL, cv2 and most Motion-JPEG cameras write): the
+ * self-synchronising decoder.  The scan is cut into subsequences, every one is decoded speculatively by a thread of its own, and entry
+ * states are handed from subsequence to subsequence until nothing changes - the fix-point is the serial decode, bit for bit; damaged
+ * streams are refused by the call as on the host path.  Opt-in per handle: on != 0 makes frp_upload_jpeg_async take it for every batch
+ * whose frames all have restart_interval == 0 (mixed batches and restart-interval batches route as before); default 0, or 1 for handles
+ * created while FRP_JPEG_SELFSYNC is set (to something not starting with '0'; read once per process).  on > 1 (measurements): on, with
+ * subsequences of `on` bytes - a multiple of 16 in 16 .. 1024 - instead of the product's size; anything else is FRP_ERR_INVALID. */
+int frp_set_jpeg_selfsync(frp_handle* h, int32_t on);
+/* diagnostic: batches of this handle decoded by it (frp_debug_jpeg_device_batches counts restart-interval batches only) */
+int64_t frp_debug_jpeg_selfsync_batches(frp_handle* h);
+/* parity: the same decode alone, B stills of identical geometry without restart markers -> coef = the quantised coefficients of every image
+ * in the layout of frp_jpeg_coefficients, one image after the other (coef_elems >= B times one image's).  subseq_bytes: the subsequence
+ * size, a multiple of 16 in 16 .. 1024, or 0 for the one frp_upload_jpeg_async uses.  stats (may be NULL): [B][4] = subsequences,
+ * synchronisation rounds (<= subsequences), blocks counted (at most the image's total), error flag - filled also when the call refuses the
+ * batch for a corrupt image (FRP_ERR_INVALID, "JPEG i: ...").  Needs no weights; a staged batch stays staged. */
+int frp_jpeg_selfsync_coefficients(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, int32_t subseq_bytes, int16_t* coef,
+                                   int64_t coef_elems, int32_t* stats);
 
 /* ---- multi-GPU: one process per GPU, ONE collective ----------------------------------------------------
  * Frames are sharded one stream per GPU and never exchanged.  The watch list is: every rank builds (decrypts) rows

@@ -32,7 +32,7 @@ struct Ingest {   // frame ingest (ingest_api.cpp: nothing else reads or writes 
     int64_t ctr_jpeg_device_batches = 0;   // batches whose entropy decode ran on the device (frp_debug_jpeg_device_batches)
     frp::DevBuf jpeg_scan, jpeg_err;      // device entropy decode (restart-interval streams): compressed scans + interval offsets + tables; per-image error flags
     // self-synchronising entropy decode (streams without restart markers; frp_set_jpeg_selfsync, default: FRP_JPEG_SELFSYNC): per
-    // subsequence its entry / exit state, blocks completed and first block, the workgroups' boundary states (ingest_api.cpp: selfsync_decode);
+    // subsequence its entry / exit state, blocks completed and first block, the workgroups' boundary states (ingest_api.cpp: decode_selfsync);
     // jpeg_err then holds [B][4] statistics with the error flag last
     bool jpeg_selfsync = false;
     int jpeg_selfsync_bytes = 0;            // subsequence size where the caller set one (measurements), 0: the product's

@@ -49,7 +49,7 @@ struct ProcessSwitches {
     bool no_graph;             // FRP_NO_GRAPH set: every network pass launch by launch, never replayed from a captured hipGraph (run_net)
     bool c64_all;              // FRP_C64_ALL set: the 64 -> 64 kernel on every eligible shape (CONV_DBG_C64_ALL), also where it does not pay
     int jpeg_device_huffman;   // FRP_JPEG_DEVICE_HUFFMAN: entropy decode of restart-interval JPEGs on the device; unset (0): for intervals of
-                               // at most 32 MCUs, "0..." (-1): never, any other value (1): always (upload_jpeg_device)
+                               // at most 32 MCUs, "0..." (-1): never, any other value (1): always (ingest_api.cpp: candidate_route)
     bool jpeg_selfsync;        // FRP_JPEG_SELFSYNC set and not "0...": new handles decode JPEG batches without restart markers on the device
                                // (the self-synchronising decoder; frp_set_jpeg_selfsync changes it per handle)
 };
@@ -237,7 +237,7 @@ hipError_t launch_jpeg_decode(const JpegParams& p, hipStream_t stream);
 
 // Entropy decoding ON THE DEVICE for streams with restart intervals (round 5): the DC predictors reset at every RSTn marker, so the
 // intervals of a scan are independent bit streams - one thread each (jpeg_kernels.hip: jpeg_huffman_kernel).  Canonical Huffman
-// tables: jpeg_host.h: JpegHuffTableDev.
+// tables: jpeg_entropy.h: JpegHuffTableDev.
 struct JpegHuffParams {
     const uint8_t* scan;             // the entropy-coded segments of all images, back to back
     const uint32_t* int_off;         // [B][n_int + 1]: byte offset (into `scan`) of every interval's first byte; [n_int] = one past the image's data
@@ -246,9 +246,8 @@ struct JpegHuffParams {
     int32_t* err;                    // out: [B], non-zero = the image's bit stream is corrupt / ends early
     long coef_per_image;
     int B, n_int, ri;                // intervals per image, MCUs per interval
-    int mcus_x, mcus_y, components;
-    int hs[3], vs[3], bx[3];         // sampling factors and blocks per row of each component
-    long comp_off[3];                // first coefficient of each component inside an image
+    int mcus_y;
+    JssGeom g;                       // (jpeg_selfsync.h: jss_geom; the kernel reads components, mcus_x, hs, vs, bx, comp_off)
 };
 hipError_t launch_jpeg_huffman(const JpegHuffParams& p, hipStream_t stream);
 

@@ -9,6 +9,7 @@
 
 #include "frp_handle.h"
 #include "jpeg_host.h"
+#include "jpeg_selfsync.h"
 
 using namespace frp;
 
@@ -60,7 +61,7 @@ int check_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t
 // an error return: the staged dims and next_valid stay).  Growing buffers: nothing may still be copying into / computing from them, so
 // BOTH streams are waited for first (ensure() waits for the compute stream only: a running staged copy would write into freed memory).
 struct Staged { DevBuf* buf; size_t bytes; };
-int grow_staged(frp_handle* h, std::initializer_list<Staged> bufs) {
+int grow_staged(frp_handle* h, const std::vector<Staged>& bufs) {
     if (std::none_of(bufs.begin(), bufs.end(), [](const Staged& s) { return s.bytes > s.buf->cap || !s.buf->p; })) return FRP_OK;
     HIPCHK(h, hipStreamSynchronize(h->in.copy_stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -99,106 +100,181 @@ bool same_geometry(const frp_jpeg_info& a, const frp_jpeg_info& b) {
     return a.width == b.width && a.height == b.height && a.components == b.components && a.h_samp[0] == b.h_samp[0] && a.v_samp[0] == b.v_samp[0];
 }
 
-// the pixel kernels (dequantise, inverse DCT, upsample, YCbCr -> BGR) from the device coefficients into the staging frame buffer
-int launch_pixels(frp_handle* h, JpegParams p, size_t q_off) {
-    p.coef = (const int16_t*)h->in.jpeg_coef.p;
-    p.qtab = (const uint16_t*)((const char*)h->in.jpeg_coef.p + q_off);
-    p.planes = (uint8_t*)h->in.jpeg_planes.p;
-    p.frames = (uint8_t*)h->in.frames_next.p;
-    const hipError_t e = launch_jpeg_decode(p, h->in.copy_stream);
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg decode: ") + hipGetErrorString(e));
-    return FRP_OK;
-}
+// Who entropy-decodes a JPEG batch.  The device routes move the COMPRESSED scans over PCIe (~0.5 MB per 1080p frame instead of 6.3 MB of
+// coefficients) and leave the host its threads: Intervals - frames that all carry the same restart interval, one thread per interval
+// (round 5; jpeg_kernels.hip: jpeg_huffman_kernel); Selfsync - frames without restart markers, where the handle asks for it (jpeg_selfsync.h,
+// jpeg_selfsync.hip); Host - everything else, one image per task on host threads (jpeg_host.cpp: jpeg_decode_coefficients).
+enum class JpegRoute { Host, Intervals, Selfsync };
 
+long intervals_per_image(const frp_jpeg_info& I) { return ((long)I.mcus_x * I.mcus_y + I.restart_interval - 1) / I.restart_interval; }
+
+// The device route that image 0's headers and the switches allow; plan_entropy_batch decides with the whole batch in hand.
+JpegRoute candidate_route(const Ingest& in, const frp_jpeg_info& I, int B) {
+    if (I.restart_interval <= 0) return in.jpeg_selfsync ? JpegRoute::Selfsync : JpegRoute::Host;
+    // When: one thread per interval decodes 32 x 1080p frames in 17.8 ms at one interval per MCU row (120 MCUs), 4.5 ms at 30 MCUs,
+    // 1.25 ms at 8 (profiles/r5/jpeg_device_entropy.txt) - the time goes with the LENGTH of an interval, and 16 host threads take
+    // 9-12 ms: by default the device decodes streams whose intervals are at most 32 MCUs and the host the others.
+    // FRP_JPEG_DEVICE_HUFFMAN=1 (read once): the device whatever the interval (takes the entropy decode off the host's cores; at
+    // one interval per row it is slower than the pipeline consumes frames), =0: never.
+    const int mode = process_switches().jpeg_device_huffman;
+    if (mode < 0 || (mode == 0 && I.restart_interval > 32)) return JpegRoute::Host;
+    const long n_int = intervals_per_image(I);
+    if ((long)B * n_int < 64 || n_int > 0x7fffff) return JpegRoute::Host;          // too few intervals to fill a wave
+    return JpegRoute::Intervals;
+}
 
 // Subsequence size of the self-synchronising decoder where the caller names none (frp_upload_jpeg_async; subseq_bytes 0 of
 // frp_jpeg_selfsync_coefficients).  32 x 1080p, quality 90: batch resident after 6.84 ms at 64, 7.07 at 128, 6.86 at 256 - the repeats of
 // one setting lie within 0.08 ms, so 64 and 256 tie and 128 is behind both (profiles/r6/jpeg_selfsync.txt).
 constexpr int kJpegSelfsyncDefaultS = 64;
 
-// Entropy decode of a batch WITHOUT restart markers on the device: the self-synchronising decoder (jpeg_selfsync.h, jpeg_selfsync.hip).
-// The host parses headers and finds the end of every scan (jpeg_plan_selfsync_decode); the COMPRESSED scans go to the device, every
-// subsequence of S bytes is decoded speculatively and the synchronisation kernel is launched again while a launch reports a change -
-// launch k leaves workgroups 0 .. k of every image final, so the loop ends within the largest image's workgroups -; then blocks are
-// counted, coefficients written and the DC differences summed.  On FRP_OK in.jpeg_coef holds the batch as the host decoder would have
-// staged it (coefficients, quantisation tables at L.q_off) and the error flags have been read: none is set.  -> FRP_OK, an error (a corrupt
-// stream is reported by this call: "JPEG i: ..."), or 1 = "not this batch" (a frame with restart intervals, scans beyond the 32-bit offsets
-// or 2^24 subsequences in all).  for_frames: the batch is being staged (frp_upload_jpeg_async) - the frame and plane buffers are grown with
-// the others and the copy stream waits for the staging frame buffer.  stats: [B][4] or null (frp.h: frp_jpeg_selfsync_coefficients).
-int selfsync_decode(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, const frp_jpeg_info& I, const JpegBatchLayout& L,
-                    int turn, int S, bool for_frames, int32_t* stats) {
-    if (I.restart_interval != 0) return 1;
-    std::vector<JpegSelfsyncPlan> plans((size_t)B);
-    std::vector<JpegHuffTableDev> tabs((size_t)B * 6);
+// A batch as a device route decodes it: every image's scan plan and tables, where the parts lie in the page-locked block and on the device
+struct EntropyBatch {
+    JpegRoute route = JpegRoute::Host;
+    std::vector<JpegScanPlan> plans;
+    std::vector<JpegHuffTableDev> tabs;
+    JpegDeviceStageLayout SL;
+    long off_words = 0;                 // words per image in SL's "offsets" part: the n_int + 1 interval offsets, or the four of img
+    std::vector<uint32_t> img;          // Selfsync: [B][4] scan offset, scan bytes, subsequences, first subsequence
+    int S = 0;                          // ... subsequence size; the largest image's subsequences; all images', each rounded up to JSS_WG
+    uint32_t max_sub = 0;
+    size_t n_sub_all = 0;
+};
+
+// Plans every image for the route `want` (the host does headers and one pass over the 0xFF bytes of every scan: jpeg_plan_scan) and lays
+// the staging out.  -> an error ("JPEG i: ..."), or FRP_OK with eb.route = want, or = Host where this is not a batch of that route: a
+// frame of the other kind or with another interval length, scans beyond the 32-bit offsets, more than 2^24 subsequences in all.
+int plan_entropy_batch(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, const frp_jpeg_info& I, JpegRoute want, int S,
+                       EntropyBatch& eb) {
+    eb.route = JpegRoute::Host;
+    if (want == JpegRoute::Host) return FRP_OK;
+    eb.plans.resize((size_t)B);
+    eb.tabs.resize((size_t)B * 6);
     std::vector<size_t> scan_bytes((size_t)B);
     for (int i = 0; i < B; ++i) {
         std::string e;
         if (!jpegs[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": null image");
-        const int rc = jpeg_plan_selfsync_decode(jpegs[i], sizes[i], plans[i], tabs.data() + (size_t)i * 6, &e);
-        if (rc != FRP_OK) {
-            if (plans[i].info.restart_interval != 0 && plans[i].info.width > 0) return 1;          // a frame with intervals: host path for the batch
-            return fail(h, rc, "JPEG " + std::to_string(i) + ": " + e);
+        const int rc = jpeg_plan_scan(jpegs[i], sizes[i], eb.plans[i], eb.tabs.data() + (size_t)i * 6, &e);
+        const frp_jpeg_info& Ii = eb.plans[i].info;
+        if ((Ii.restart_interval != 0) != (I.restart_interval != 0) && Ii.width > 0) return FRP_OK;       // a frame of the other kind
+        if (rc != FRP_OK) return fail(h, rc, "JPEG " + std::to_string(i) + ": " + e);
+        if (!same_geometry(Ii, I)) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": " + kGeometryDiffers);
+        if (Ii.restart_interval != I.restart_interval) return FRP_OK;
+        scan_bytes[i] = eb.plans[i].scan_bytes;
+    }
+    eb.off_words = want == JpegRoute::Intervals ? intervals_per_image(I) + 1 : 4;
+    eb.SL = jpeg_device_stage_layout(B, eb.off_words - 1, scan_bytes.data());
+    if (eb.SL.too_large) return FRP_OK;
+    if (want == JpegRoute::Selfsync) {
+        eb.S = S;
+        eb.img.resize((size_t)B * 4);
+        uint64_t n_all = 0;
+        for (int i = 0; i < B; ++i) {
+            const uint32_t n_sub = jss_subsequences((uint32_t)scan_bytes[i], (uint32_t)S);
+            eb.img[4 * i] = (uint32_t)eb.SL.soff[i]; eb.img[4 * i + 1] = (uint32_t)scan_bytes[i]; eb.img[4 * i + 2] = n_sub; eb.img[4 * i + 3] = (uint32_t)n_all;
+            n_all += ((uint64_t)n_sub + JSS_WG - 1) / JSS_WG * JSS_WG;
+            eb.max_sub = std::max(eb.max_sub, n_sub);
+            if (n_all > (1u << 24)) return FRP_OK;
         }
-        if (!same_geometry(plans[i].info, I)) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": " + kGeometryDiffers);
-        scan_bytes[i] = plans[i].scan_bytes;
+        eb.n_sub_all = (size_t)n_all;
     }
-    // staging as for the restart-interval decoder, with four words per image in the place of its interval offsets
-    const JpegDeviceStageLayout SL = jpeg_device_stage_layout(B, 3, scan_bytes.data());
-    if (SL.too_large) return 1;
-    std::vector<uint32_t> img((size_t)B * 4);
-    uint64_t n_all = 0;
-    uint32_t max_sub = 0;
-    for (int i = 0; i < B; ++i) {
-        const uint32_t n_sub = jss_subsequences((uint32_t)scan_bytes[i], (uint32_t)S);
-        img[4 * i] = (uint32_t)SL.soff[i]; img[4 * i + 1] = (uint32_t)scan_bytes[i]; img[4 * i + 2] = n_sub; img[4 * i + 3] = (uint32_t)n_all;
-        n_all += ((uint64_t)n_sub + JSS_WG - 1) / JSS_WG * JSS_WG;
-        max_sub = std::max(max_sub, n_sub);
-        if (n_all > (1u << 24)) return 1;
-    }
-    const size_t N = (size_t)n_all, n_wg_all = N / JSS_WG;
+    eb.route = want;
+    return FRP_OK;
+}
+
+// The staging sequence of a device route, up to its kernels: the page-locked block of `turn` filled (scans | offsets | Huffman tables |
+// quantisation tables; `back_bytes` behind them are the route's to read results into) -> *pin; the device buffers grown (ss_bytes: the
+// self-synchronising decoder's scratch); one copy to the device, the coefficients zeroed, the quantisation tables copied behind them
+// (L.q_off), `err_bytes` of flags zeroed.  for_frames: the batch is being staged (frp_upload_jpeg_async) - the frame and plane buffers are
+// grown with the others and the copy stream waits for the staging frame buffer.
+int stage_entropy_batch(frp_handle* h, const EntropyBatch& eb, int B, const frp_jpeg_info& I, const JpegBatchLayout& L, int turn, size_t back_bytes,
+                        size_t err_bytes, size_t ss_bytes, bool for_frames, char** pin) {
     Ingest& in = h->in;
-    void* pin = nullptr;
-    const size_t pin_stats = SL.o_err, pin_rounds = pin_stats + (size_t)B * 16;      // read back: [B][4] stats, [B] rounds of a launch
-    FRPCHK(jpeg_staging_turn(h, turn, pin_rounds + (size_t)B * 4, &pin));
-    char* st = (char*)pin;
+    const JpegDeviceStageLayout& SL = eb.SL;
+    void* block = nullptr;
+    FRPCHK(jpeg_staging_turn(h, turn, SL.o_err + back_bytes, &block));
+    char* st = (char*)block;
+    uint32_t* off = (uint32_t*)(st + SL.o_int);
     for (int i = 0; i < B; ++i) {
-        memcpy(st + SL.soff[i], plans[i].scan, plans[i].scan_bytes);
-        memcpy(st + SL.o_q + (size_t)i * 384, plans[i].qtab, 384);
+        const JpegScanPlan& P = eb.plans[i];
+        memcpy(st + SL.soff[i], P.scan, P.scan_bytes);
+        for (size_t k = 0; k < P.int_off.size(); ++k) off[(size_t)i * eb.off_words + k] = (uint32_t)(SL.soff[i] + P.int_off[k]);
+        memcpy(st + SL.o_q + (size_t)i * 384, P.qtab, 384);
     }
-    memcpy(st + SL.o_int, img.data(), img.size() * 4);
-    memcpy(st + SL.o_tab, tabs.data(), tabs.size() * sizeof(JpegHuffTableDev));
-    // device scratch: entry | exit | wgx (8 bytes each), then cnt | base | rounds (4 bytes each)
-    const size_t o_exit = N * 8, o_wgx = o_exit + N * 8, o_cnt = o_wgx + 2 * n_wg_all * 8, o_base = o_cnt + N * 4, o_rounds = o_base + N * 4;
-    const size_t ss_total = o_rounds + (size_t)B * 4;
-    if (for_frames)
-        FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img},
-                               {&in.jpeg_scan, SL.o_err}, {&in.jpeg_err, (size_t)B * 16}, {&in.jpeg_ss, ss_total}}));
-    else
-        FRPCHK(grow_staged(h, {{&in.jpeg_coef, L.total}, {&in.jpeg_scan, SL.o_err}, {&in.jpeg_err, (size_t)B * 16}, {&in.jpeg_ss, ss_total}}));
+    if (!eb.img.empty()) memcpy(off, eb.img.data(), eb.img.size() * 4);
+    memcpy(st + SL.o_tab, eb.tabs.data(), eb.tabs.size() * sizeof(JpegHuffTableDev));
+    std::vector<Staged> bufs = {{&in.jpeg_coef, L.total}, {&in.jpeg_scan, SL.o_err}, {&in.jpeg_err, err_bytes}};
+    if (for_frames) { bufs.push_back({&in.frames_next, (size_t)B * I.height * I.width * 3}); bufs.push_back({&in.jpeg_planes, (size_t)B * L.plane_img}); }
+    if (ss_bytes) bufs.push_back({&in.jpeg_ss, ss_bytes});
+    FRPCHK(grow_staged(h, bufs));
     if (for_frames) FRPCHK(begin_staging(h));
     HIPCHK(h, hipMemcpyAsync(in.jpeg_scan.p, st, SL.o_err, hipMemcpyHostToDevice, in.copy_stream));
     HIPCHK(h, hipMemsetAsync(in.jpeg_coef.p, 0, L.q_off, in.copy_stream));
     HIPCHK(h, hipMemcpyAsync((char*)in.jpeg_coef.p + L.q_off, (char*)in.jpeg_scan.p + SL.o_q, (size_t)B * 384, hipMemcpyDeviceToDevice, in.copy_stream));
-    HIPCHK(h, hipMemsetAsync(in.jpeg_err.p, 0, (size_t)B * 16, in.copy_stream));
+    HIPCHK(h, hipMemsetAsync(in.jpeg_err.p, 0, err_bytes, in.copy_stream));
+    *pin = st;
+    return FRP_OK;
+}
+
+// After the route's kernels: in.jpeg_err -> `back` (page-locked; `stride` words per image, word `flag` non-zero = a corrupt stream), and the
+// host waits for it: this call reports it, as on the host path, before the pixel kernels are queued (the staging block is free again too).
+int read_entropy_flags(frp_handle* h, int B, int32_t* back, int stride, int flag) {
+    HIPCHK(h, hipMemcpyAsync(back, h->in.jpeg_err.p, (size_t)B * stride * 4, hipMemcpyDeviceToHost, h->in.copy_stream));
+    HIPCHK(h, hipStreamSynchronize(h->in.copy_stream));
+    for (int i = 0; i < B; ++i)
+        if (back[stride * i + flag]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": corrupt or truncated entropy-coded data");
+    return FRP_OK;
+}
+
+// Route Intervals.  On FRP_OK in.jpeg_coef holds the batch as the host decoder would have staged it (coefficients, tables at L.q_off).
+int decode_intervals(frp_handle* h, const EntropyBatch& eb, int B, const frp_jpeg_info& I, const JpegBatchLayout& L, int turn) {
+    Ingest& in = h->in;
+    char* st = nullptr;
+    FRPCHK(stage_entropy_batch(h, eb, B, I, L, turn, (size_t)B * 4, (size_t)B * 4, 0, true, &st));
+    JpegHuffParams hp{};
+    hp.scan = (const uint8_t*)in.jpeg_scan.p;
+    hp.int_off = (const uint32_t*)((const char*)in.jpeg_scan.p + eb.SL.o_int);
+    hp.tables = (const JpegHuffTableDev*)((const char*)in.jpeg_scan.p + eb.SL.o_tab);
+    hp.coef = (int16_t*)in.jpeg_coef.p;
+    hp.err = (int32_t*)in.jpeg_err.p;
+    hp.coef_per_image = (long)L.coef_elems;
+    hp.B = B; hp.n_int = (int)eb.off_words - 1; hp.ri = I.restart_interval;
+    hp.mcus_y = I.mcus_y;
+    hp.g = jss_geom(I, L);
+    const hipError_t e = launch_jpeg_huffman(hp, in.copy_stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg huffman: ") + hipGetErrorString(e));
+    return read_entropy_flags(h, B, (int32_t*)(st + eb.SL.o_err), 1, 0);
+}
+
+// Route Selfsync: every subsequence of S bytes is decoded speculatively and the synchronisation kernel is launched again while a launch
+// reports a change - launch k leaves workgroups 0 .. k of every image final, so the loop ends within the largest image's workgroups -; then
+// blocks are counted, coefficients written and the DC differences summed.  On FRP_OK in.jpeg_coef holds the batch as above.
+// stats: [B][4] or null (frp.h: frp_jpeg_selfsync_coefficients).
+int decode_selfsync(frp_handle* h, const EntropyBatch& eb, int B, const frp_jpeg_info& I, const JpegBatchLayout& L, int turn, bool for_frames,
+                    int32_t* stats) {
+    Ingest& in = h->in;
+    // device scratch: entry | exit | wgx (8 bytes each), then cnt | base | rounds (4 bytes each)
+    const size_t N = eb.n_sub_all, n_wg_all = N / JSS_WG;
+    const size_t o_exit = N * 8, o_wgx = o_exit + N * 8, o_cnt = o_wgx + 2 * n_wg_all * 8, o_base = o_cnt + N * 4, o_rounds = o_base + N * 4;
+    const size_t pin_stats = eb.SL.o_err, pin_rounds = pin_stats + (size_t)B * 16;      // read back: [B][4] stats, [B] rounds of a launch
+    char* st = nullptr;
+    FRPCHK(stage_entropy_batch(h, eb, B, I, L, turn, (size_t)B * 20, (size_t)B * 16, o_rounds + (size_t)B * 4, for_frames, &st));
     JpegSelfsyncParams sp{};
     char* ss = (char*)in.jpeg_ss.p;
     sp.scan = (const uint8_t*)in.jpeg_scan.p;
-    sp.img = (const uint32_t*)((const char*)in.jpeg_scan.p + SL.o_int);
-    sp.tables = (const JpegHuffTableDev*)((const char*)in.jpeg_scan.p + SL.o_tab);
+    sp.img = (const uint32_t*)((const char*)in.jpeg_scan.p + eb.SL.o_int);
+    sp.tables = (const JpegHuffTableDev*)((const char*)in.jpeg_scan.p + eb.SL.o_tab);
     sp.entry = (JssState*)ss; sp.exit_ = (JssState*)(ss + o_exit); sp.wgx = (JssState*)(ss + o_wgx);
     sp.cnt = (uint32_t*)(ss + o_cnt); sp.base = (uint32_t*)(ss + o_base); sp.rounds = (int32_t*)(ss + o_rounds);
     sp.stats = (int32_t*)in.jpeg_err.p;
     sp.coef = (int16_t*)in.jpeg_coef.p;
     sp.coef_per_image = (long)L.coef_elems;
-    sp.B = B; sp.S = S; sp.max_sub = max_sub; sp.n_wg_all = (uint32_t)n_wg_all;
-    sp.g.components = I.components; sp.g.mcus_x = I.mcus_x;
-    for (int c = 0; c < 3; ++c) { sp.g.hs[c] = I.h_samp[c]; sp.g.vs[c] = I.v_samp[c]; sp.g.bx[c] = L.bx[c]; sp.g.comp_off[c] = L.plane_off[c]; }
-    jss_geom_blocks(sp.g);
-    sp.g.total = (uint32_t)L.blocks_per_image;
+    sp.B = B; sp.S = eb.S; sp.max_sub = eb.max_sub; sp.n_wg_all = (uint32_t)n_wg_all;
+    sp.g = jss_geom(I, L);
     if (sp.g.bpm > 6 || (long)I.mcus_x * I.mcus_y * sp.g.bpm != (long)L.blocks_per_image) return fail(h, FRP_ERR_INVALID, "JPEG 0: unsupported sampling factors");
     const int32_t* lr = (const int32_t*)(st + pin_rounds);
     std::vector<int32_t> rounds((size_t)B, 0);
-    const uint32_t max_wg = (max_sub + JSS_WG - 1) / JSS_WG;
+    const uint32_t max_wg = (eb.max_sub + JSS_WG - 1) / JSS_WG;
     for (uint32_t k = 0;; ++k) {
         if (k > max_wg) return fail(h, FRP_ERR_HIP, "jpeg selfsync: no fix-point within the workgroups of the largest scan");       // (launch k leaves 0 .. k final)
         HIPCHK(h, hipMemsetAsync(sp.rounds, 0, (size_t)B * 4, in.copy_stream));
@@ -212,13 +288,46 @@ int selfsync_decode(frp_handle* h, const uint8_t* const* jpegs, const size_t* si
     }
     const hipError_t e = launch_jpeg_selfsync_finish(sp, in.copy_stream);
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg selfsync: ") + hipGetErrorString(e));
-    HIPCHK(h, hipMemcpyAsync(st + pin_stats, in.jpeg_err.p, (size_t)B * 16, hipMemcpyDeviceToHost, in.copy_stream));
-    HIPCHK(h, hipStreamSynchronize(in.copy_stream));   // the flags decide this call's return value (and the staging block is free again: no jpeg_h2d_pending)
-    const int32_t* got = (const int32_t*)(st + pin_stats);
-    if (stats)
+    int32_t* got = (int32_t*)(st + pin_stats);
+    const int rc = read_entropy_flags(h, B, got, 4, 3);
+    if (stats && rc != FRP_ERR_HIP)                             // (the statistics of a refused batch too)
         for (int i = 0; i < B; ++i) { stats[4 * i] = got[4 * i]; stats[4 * i + 1] = rounds[i]; stats[4 * i + 2] = got[4 * i + 2]; stats[4 * i + 3] = got[4 * i + 3]; }
+    return rc;
+}
+
+// Route Host: one image per task on host threads (the images are independent; within one the bit stream is serial) into the page-locked
+// block of `turn`, which then goes to the device as it is - coefficients, quantisation tables at L.q_off.
+int decode_on_host(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int B, const frp_jpeg_info& I, const JpegBatchLayout& L, int turn) {
+    Ingest& in = h->in;
+    void* pin = nullptr;
+    FRPCHK(jpeg_staging_turn(h, turn, L.total, &pin));
+    int16_t* coef = (int16_t*)pin;
+    uint16_t* qtab = (uint16_t*)((char*)pin + L.q_off);
+    std::vector<int> rcs((size_t)B, FRP_OK);
+    std::vector<std::string> errs((size_t)B);
+    {
+        const int nth = std::max(1, std::min<int>(B, (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()))));
+        std::atomic<int> next{0};
+        auto work = [&]() {
+            for (int i = next.fetch_add(1); i < B; i = next.fetch_add(1)) {
+                frp_jpeg_info Ii{};
+                if (!jpegs[i]) { rcs[i] = FRP_ERR_INVALID; errs[i] = "null image"; continue; }
+                rcs[i] = jpeg_decode_coefficients(jpegs[i], sizes[i], coef + (size_t)i * L.coef_elems, L.coef_elems, qtab + (size_t)i * 192, &Ii, &errs[i]);
+                if (rcs[i] == FRP_OK && !same_geometry(Ii, I)) { rcs[i] = FRP_ERR_INVALID; errs[i] = kGeometryDiffers; }
+            }
+        };
+        std::vector<std::thread> th;
+        for (int t = 1; t < nth; ++t) th.emplace_back(work);
+        work();
+        for (auto& t : th) t.join();
+    }
     for (int i = 0; i < B; ++i)
-        if (got[4 * i + 3]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": corrupt or truncated entropy-coded data");
+        if (rcs[i] != FRP_OK) return fail(h, rcs[i], "JPEG " + std::to_string(i) + ": " + errs[i]);
+    FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img}}));
+    FRPCHK(begin_staging(h));
+    HIPCHK(h, hipMemcpyAsync(in.jpeg_coef.p, pin, L.total, hipMemcpyHostToDevice, in.copy_stream));
+    HIPCHK(h, hipEventRecord(in.ev_jpeg_h2d[turn], in.copy_stream));
+    in.jpeg_h2d_pending[turn] = true;
     return FRP_OK;
 }
 
@@ -291,83 +400,6 @@ int frp_jpeg_coefficients(const uint8_t* data, size_t size, int16_t* coef, size_
     return jpeg_decode_coefficients(data, size, coef, coef_elems, qtab, info, nullptr);
 }
 
-namespace {   // Inside extern "C" this unnamed namespace does not hide the name: libfrp.so exports upload_jpeg_device by accident.  Kept
-              // only because this move leaves the set of exports as it is; a change that cleans the ABI moves it out of extern "C".
-// Device entropy decode of a batch whose frames all carry restart intervals (round 5; jpeg_kernels.hip: jpeg_huffman_kernel): the host
-// parses headers and finds the RSTn markers (one memchr pass), the COMPRESSED scans go to the device (~0.5 MB per 1080p frame instead of
-// 6.3 MB of coefficients), one thread per interval decodes, and the host waits only for the per-image error flags (a corrupt stream
-// must be reported by this call, as on the host path) before the pixel kernels are queued.  -> FRP_OK, an error, or 1 = "not this
-// batch" (not switched on, no restart intervals, too few of them to fill a wave): the caller takes the host decoder.
-int upload_jpeg_device(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, const frp_jpeg_info& I, int turn,
-                       const JpegParams& p, const JpegBatchLayout& L) {
-    // When: one thread per interval decodes 32 x 1080p frames in 17.8 ms at one interval per MCU row (120 MCUs), 4.5 ms at 30 MCUs,
-    // 1.25 ms at 8 (profiles/r5/jpeg_device_entropy.txt) - the time goes with the LENGTH of an interval, and 16 host threads take
-    // 9-12 ms: by default the device decodes streams whose intervals are at most 32 MCUs and the host the others.
-    // FRP_JPEG_DEVICE_HUFFMAN=1 (read once): the device whatever the interval (takes the entropy decode off the host's cores; at
-    // one interval per row it is slower than the pipeline consumes frames), =0: never.
-    const int mode = process_switches().jpeg_device_huffman;
-    if (mode < 0 || I.restart_interval <= 0 || (mode == 0 && I.restart_interval > 32)) return 1;
-    const long n_int = ((long)I.mcus_x * I.mcus_y + I.restart_interval - 1) / I.restart_interval;
-    if ((long)B * n_int < 64 || n_int > 0x7fffff) return 1;
-    std::vector<JpegDevicePlan> plans((size_t)B);
-    std::vector<JpegHuffTableDev> tabs((size_t)B * 6);
-    std::vector<size_t> scan_bytes((size_t)B);
-    for (int i = 0; i < B; ++i) {
-        std::string e;
-        if (!jpegs[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": null image");
-        const int rc = jpeg_plan_device_decode(jpegs[i], sizes[i], plans[i], tabs.data() + (size_t)i * 6, &e);
-        if (rc != FRP_OK) {
-            if (plans[i].info.restart_interval <= 0 && plans[i].info.width > 0) return 1;          // a frame without intervals: host path for the batch
-            return fail(h, rc, "JPEG " + std::to_string(i) + ": " + e);
-        }
-        if (!same_geometry(plans[i].info, I)) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": " + kGeometryDiffers);
-        if (plans[i].info.restart_interval != I.restart_interval) return 1;
-        scan_bytes[i] = plans[i].scan_bytes;
-    }
-    const JpegDeviceStageLayout S = jpeg_device_stage_layout(B, n_int, scan_bytes.data());
-    if (S.too_large) return 1;
-    Ingest& in = h->in;
-    void* pin = nullptr;
-    FRPCHK(jpeg_staging_turn(h, turn, S.stage_total, &pin));
-    char* st = (char*)pin;
-    uint32_t* io = (uint32_t*)(st + S.o_int);
-    for (int i = 0; i < B; ++i) {
-        memcpy(st + S.soff[i], plans[i].scan, plans[i].scan_bytes);
-        for (long k = 0; k <= n_int; ++k) io[(size_t)i * (n_int + 1) + k] = (uint32_t)(S.soff[i] + plans[i].int_off[(size_t)k]);
-        memcpy(st + S.o_q + (size_t)i * 384, plans[i].qtab, 384);
-    }
-    memcpy(st + S.o_tab, tabs.data(), tabs.size() * sizeof(JpegHuffTableDev));
-    FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img},
-                           {&in.jpeg_scan, S.o_err}, {&in.jpeg_err, (size_t)B * 4}}));
-    FRPCHK(begin_staging(h));
-    HIPCHK(h, hipMemcpyAsync(in.jpeg_scan.p, st, S.o_err, hipMemcpyHostToDevice, in.copy_stream));
-    HIPCHK(h, hipMemsetAsync(in.jpeg_coef.p, 0, L.q_off, in.copy_stream));
-    HIPCHK(h, hipMemcpyAsync((char*)in.jpeg_coef.p + L.q_off, (char*)in.jpeg_scan.p + S.o_q, (size_t)B * 384, hipMemcpyDeviceToDevice, in.copy_stream));
-    HIPCHK(h, hipMemsetAsync(in.jpeg_err.p, 0, (size_t)B * 4, in.copy_stream));
-    JpegHuffParams hp{};
-    hp.scan = (const uint8_t*)in.jpeg_scan.p;
-    hp.int_off = (const uint32_t*)((const char*)in.jpeg_scan.p + S.o_int);
-    hp.tables = (const JpegHuffTableDev*)((const char*)in.jpeg_scan.p + S.o_tab);
-    hp.coef = (int16_t*)in.jpeg_coef.p;
-    hp.err = (int32_t*)in.jpeg_err.p;
-    hp.coef_per_image = (long)L.coef_elems;
-    hp.B = B; hp.n_int = (int)n_int; hp.ri = I.restart_interval;
-    hp.mcus_x = I.mcus_x; hp.mcus_y = I.mcus_y; hp.components = I.components;
-    for (int c = 0; c < 3; ++c) { hp.hs[c] = I.h_samp[c]; hp.vs[c] = I.v_samp[c]; hp.bx[c] = L.bx[c]; hp.comp_off[c] = L.plane_off[c]; }
-    const hipError_t e = launch_jpeg_huffman(hp, in.copy_stream);
-    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg huffman: ") + hipGetErrorString(e));
-    HIPCHK(h, hipMemcpyAsync(st + S.o_err, in.jpeg_err.p, (size_t)B * 4, hipMemcpyDeviceToHost, in.copy_stream));
-    HIPCHK(h, hipStreamSynchronize(in.copy_stream));   // the flags decide this call's return value (and the staging block is free again: no jpeg_h2d_pending)
-    const int32_t* flags = (const int32_t*)(st + S.o_err);
-    for (int i = 0; i < B; ++i)
-        if (flags[i]) return fail(h, FRP_ERR_INVALID, "JPEG " + std::to_string(i) + ": corrupt or truncated entropy-coded data");
-    FRPCHK(launch_pixels(h, p, L.q_off));
-    FRPCHK(end_staging(h, B, I.height, I.width));
-    in.ctr_jpeg_device_batches += 1;
-    return FRP_OK;
-}
-}  // namespace
-
 int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h, false);      // copy stream only (as frp_upload_frames_async)
@@ -379,54 +411,29 @@ int frp_upload_jpeg_async(frp_handle* h, const uint8_t* const* jpegs, const size
     Ingest& in = h->in;
     const int turn = in.jpeg_turn;      // flips once per call, whichever decoder takes the batch and whether it succeeds
     in.jpeg_turn ^= 1;
+    EntropyBatch eb;
+    FRPCHK(plan_entropy_batch(h, jpegs, sizes, B, I, candidate_route(in, I, B), in.jpeg_selfsync_bytes ? in.jpeg_selfsync_bytes : kJpegSelfsyncDefaultS, eb));
+    switch (eb.route) {                 // entropy decode: in.jpeg_coef <- coefficients and quantisation tables, on the copy stream
+        case JpegRoute::Intervals: FRPCHK(decode_intervals(h, eb, B, I, L, turn)); break;
+        case JpegRoute::Selfsync: FRPCHK(decode_selfsync(h, eb, B, I, L, turn, true, nullptr)); break;
+        case JpegRoute::Host: FRPCHK(decode_on_host(h, jpegs, sizes, B, I, L, turn)); break;
+    }
+    // the pixel kernels (dequantise, inverse DCT, upsample, YCbCr -> BGR) from the device coefficients into the staging frame buffer
     JpegParams p{};
+    p.coef = (const int16_t*)in.jpeg_coef.p;
+    p.qtab = (const uint16_t*)((const char*)in.jpeg_coef.p + L.q_off);
+    p.planes = (uint8_t*)in.jpeg_planes.p;
+    p.frames = (uint8_t*)in.frames_next.p;
     p.B = B; p.W = I.width; p.H = I.height; p.components = I.components;
     p.hs = I.h_samp[0]; p.vs = I.v_samp[0];
     p.cw = L.cw; p.ch = L.ch; p.blocks_per_image = L.blocks_per_image; p.plane_img = L.plane_img;
     for (int c = 0; c < 3; ++c) { p.bx[c] = L.bx[c]; p.by[c] = L.by[c]; p.plane_off[c] = L.plane_off[c]; }
-    const int dr = upload_jpeg_device(h, jpegs, sizes, B, I, turn, p, L);     // restart-interval streams: entropy decode on the device
-    if (dr != 1) return dr;
-    if (in.jpeg_selfsync) {                                                   // frames without restart markers, where the handle asks for it: on the device too
-        const int sr = selfsync_decode(h, jpegs, sizes, B, I, L, turn, in.jpeg_selfsync_bytes ? in.jpeg_selfsync_bytes : kJpegSelfsyncDefaultS, true, nullptr);
-        if (sr == FRP_OK) {
-            FRPCHK(launch_pixels(h, p, L.q_off));
-            FRPCHK(end_staging(h, B, I.height, I.width));
-            in.ctr_jpeg_selfsync_batches += 1;
-        }
-        if (sr != 1) return sr;
-    }
-    void* pin = nullptr;
-    FRPCHK(jpeg_staging_turn(h, turn, L.total, &pin));
-    int16_t* coef = (int16_t*)pin;
-    uint16_t* qtab = (uint16_t*)((char*)pin + L.q_off);
-    // entropy decoding: one image per task on host threads (the images are independent; within one the bit stream is serial)
-    std::vector<int> rcs((size_t)B, FRP_OK);
-    std::vector<std::string> errs((size_t)B);
-    {
-        const int nth = std::max(1, std::min<int>(B, (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()))));
-        std::atomic<int> next{0};
-        auto work = [&]() {
-            for (int i = next.fetch_add(1); i < B; i = next.fetch_add(1)) {
-                frp_jpeg_info Ii{};
-                if (!jpegs[i]) { rcs[i] = FRP_ERR_INVALID; errs[i] = "null image"; continue; }
-                rcs[i] = jpeg_decode_coefficients(jpegs[i], sizes[i], coef + (size_t)i * L.coef_elems, L.coef_elems, qtab + (size_t)i * 192, &Ii, &errs[i]);
-                if (rcs[i] == FRP_OK && !same_geometry(Ii, I)) { rcs[i] = FRP_ERR_INVALID; errs[i] = kGeometryDiffers; }
-            }
-        };
-        std::vector<std::thread> th;
-        for (int t = 1; t < nth; ++t) th.emplace_back(work);
-        work();
-        for (auto& t : th) t.join();
-    }
-    for (int i = 0; i < B; ++i)
-        if (rcs[i] != FRP_OK) return fail(h, rcs[i], "JPEG " + std::to_string(i) + ": " + errs[i]);
-    FRPCHK(grow_staged(h, {{&in.frames_next, (size_t)B * I.height * I.width * 3}, {&in.jpeg_coef, L.total}, {&in.jpeg_planes, (size_t)B * L.plane_img}}));
-    FRPCHK(begin_staging(h));
-    HIPCHK(h, hipMemcpyAsync(in.jpeg_coef.p, pin, L.total, hipMemcpyHostToDevice, in.copy_stream));
-    HIPCHK(h, hipEventRecord(in.ev_jpeg_h2d[turn], in.copy_stream));
-    in.jpeg_h2d_pending[turn] = true;
-    FRPCHK(launch_pixels(h, p, L.q_off));
-    return end_staging(h, B, I.height, I.width);
+    const hipError_t e = launch_jpeg_decode(p, in.copy_stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("jpeg decode: ") + hipGetErrorString(e));
+    FRPCHK(end_staging(h, B, I.height, I.width));
+    if (eb.route == JpegRoute::Intervals) in.ctr_jpeg_device_batches += 1;
+    if (eb.route == JpegRoute::Selfsync) in.ctr_jpeg_selfsync_batches += 1;
+    return FRP_OK;
 }
 
 // diagnostic: how many frp_upload_jpeg_async batches had their entropy decode on the device (restart-interval streams)
@@ -466,9 +473,11 @@ int frp_jpeg_selfsync_coefficients(frp_handle* h, const uint8_t* const* jpegs, c
     Ingest& in = h->in;
     const int turn = in.jpeg_turn;      // a staging block of its own turn, as every JPEG batch
     in.jpeg_turn ^= 1;
-    const int r = selfsync_decode(h, jpegs, sizes, B, I, L, turn, subseq_bytes ? subseq_bytes : kJpegSelfsyncDefaultS, false, stats);
-    if (r == 1) return fail(h, FRP_ERR_INVALID, "not a batch of the self-synchronising decoder (a frame carries restart intervals, or the scans are too large)");
-    FRPCHK(r);
+    EntropyBatch eb;
+    FRPCHK(plan_entropy_batch(h, jpegs, sizes, B, I, I.restart_interval == 0 ? JpegRoute::Selfsync : JpegRoute::Host,
+                              subseq_bytes ? subseq_bytes : kJpegSelfsyncDefaultS, eb));
+    if (eb.route != JpegRoute::Selfsync) return fail(h, FRP_ERR_INVALID, "not a batch of the self-synchronising decoder (a frame carries restart intervals, or the scans are too large)");
+    FRPCHK(decode_selfsync(h, eb, B, I, L, turn, false, stats));
     HIPCHK(h, hipMemcpyAsync(coef, in.jpeg_coef.p, L.coef_bytes, hipMemcpyDeviceToHost, in.copy_stream));
     HIPCHK(h, hipStreamSynchronize(in.copy_stream));
     return FRP_OK;

@@ -24,10 +24,6 @@ namespace frp {
 
 namespace {
 
-const uint8_t kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 constexpr int kFast = 10;                     // look-ahead bits of the two direct tables
 
 struct HuffTable {
@@ -230,7 +226,7 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeaderInternal& H) {
                 if (tq > 3 || pq > 1 || o + (pq ? 128 : 64) > sl) { H.err = "bad DQT"; return FRP_ERR_INVALID; }
                 for (int i = 0; i < 64; ++i) {
                     const int v = pq ? be16(s + o + 2 * i) : s[o + i];
-                    H.qt[tq][kZigZag[i]] = (uint16_t)v;
+                    H.qt[tq][kJpegZigZag[i]] = (uint16_t)v;
                 }
                 o += pq ? 128 : 64;
                 H.have_qt[tq] = true;
@@ -425,7 +421,7 @@ int jpeg_decode_coefficients(const uint8_t* data, size_t size, int16_t* coef, si
                                 k += (fa >> 4) & 15;
                                 if (k > 63) { if (err) *err = "corrupt AC run"; return FRP_ERR_INVALID; }
                                 br.skip(fa & 15);
-                                blk[kZigZag[k++]] = (int16_t)(fa >> 8);
+                                blk[kJpegZigZag[k++]] = (int16_t)(fa >> 8);
                                 continue;
                             }
                             const int rs = br.decode(act);
@@ -437,7 +433,7 @@ int jpeg_decode_coefficients(const uint8_t* data, size_t size, int16_t* coef, si
                             }
                             k += r;
                             if (k > 63) { if (err) *err = "corrupt AC run"; return FRP_ERR_INVALID; }
-                            blk[kZigZag[k]] = (int16_t)br.receive_extend(sz);
+                            blk[kJpegZigZag[k]] = (int16_t)br.receive_extend(sz);
                             ++k;
                         }
                     }
@@ -452,9 +448,8 @@ int jpeg_decode_coefficients(const uint8_t* data, size_t size, int16_t* coef, si
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Plan of a device-side entropy decode (restart-interval streams).  The host's part shrinks to the headers and ONE pass over
-// the scan for 0xFF bytes: every RSTn marker starts an independent interval (T.81 F.1.1.5: the DC predictors and the bit
-// alignment reset there).
+// Plan of a device-side entropy decode (jpeg_host.h: JpegScanPlan).  The host's part shrinks to the headers and ONE pass over the scan
+// for 0xFF bytes.
 static void flatten_table(const HuffTable& t, JpegHuffTableDev& d) {
     memset(&d, 0, sizeof(d));
     for (int i = 0; i < 512; ++i) {
@@ -468,13 +463,12 @@ static void flatten_table(const HuffTable& t, JpegHuffTableDev& d) {
     memcpy(d.vals, t.vals, 256);
 }
 
-int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& plan, JpegHuffTableDev* tables6, std::string* err) {
+int jpeg_plan_scan(const uint8_t* data, size_t size, JpegScanPlan& plan, JpegHuffTableDev* tables6, std::string* err) {
     JpegHeaderInternal H;
     const int rc = parse_headers(data, size, H);
     plan.info = H.info;
     if (rc != FRP_OK) { if (err) *err = H.err; return rc; }
     const frp_jpeg_info& I = H.info;
-    if (I.restart_interval <= 0) { if (err) *err = "no restart intervals"; return FRP_ERR_INVALID; }
     for (int c = 0; c < 3; ++c)
         for (int i = 0; i < 64; ++i) plan.qtab[c * 64 + i] = c < I.components ? H.qt[H.comp_tq[c]][i] : 1;
     for (int c = 0; c < 3; ++c) {
@@ -482,15 +476,27 @@ int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& pl
         flatten_table(H.dc[H.comp_td[cc]], tables6[2 * c]);
         flatten_table(H.ac[H.comp_ta[cc]], tables6[2 * c + 1]);
     }
+    plan.scan = H.scan;
+    plan.int_off.clear();
+    const uint8_t* p = H.scan;
+    const uint8_t* const end = data + size;
+    if (I.restart_interval <= 0) {                   // the scan ends where BitReader::fill_slow stops taking bytes
+        while (p < end) {
+            p = (const uint8_t*)memchr(p, 0xFF, (size_t)(end - p));
+            if (!p) { p = end; break; }
+            if (p + 1 < end && p[1] == 0x00) { p += 2; continue; }     // stuffed byte
+            break;                                                     // a marker, or a 0xFF as the file's last byte
+        }
+        if ((size_t)(p - H.scan) >= ((size_t)1 << 28)) { if (err) *err = "scan too large"; return FRP_ERR_INVALID; }
+        plan.scan_bytes = (size_t)(p - H.scan);
+        return FRP_OK;
+    }
+    // every RSTn marker starts an independent interval (T.81 F.1.1.5: the DC predictors and the bit alignment reset there)
     const long mcus = (long)I.mcus_x * I.mcus_y;
     const long n_int = (mcus + I.restart_interval - 1) / I.restart_interval;
     if (n_int > 0x7fffff) { if (err) *err = "too many restart intervals"; return FRP_ERR_INVALID; }
-    plan.scan = H.scan;
-    plan.int_off.clear();
     plan.int_off.reserve((size_t)n_int + 1);
     plan.int_off.push_back(0);
-    const uint8_t* p = H.scan;
-    const uint8_t* const end = data + size;
     int next_rst = 0;
     const uint8_t* stop = end;                       // the first marker that is not RSTn (EOI normally), or the end of the file
     while (p < end) {
@@ -513,36 +519,6 @@ int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& pl
     if ((size_t)(stop - H.scan) >= 0xfffffff0u) { if (err) *err = "scan too large"; return FRP_ERR_INVALID; }
     plan.int_off.push_back((uint32_t)(stop - H.scan));
     plan.scan_bytes = (size_t)(stop - H.scan);
-    return FRP_OK;
-}
-
-// Plan of the self-synchronising device decode (scans without restart markers, jpeg_selfsync.h): headers and tables as above; the scan
-// ends where BitReader::fill_slow stops taking bytes.
-int jpeg_plan_selfsync_decode(const uint8_t* data, size_t size, JpegSelfsyncPlan& plan, JpegHuffTableDev* tables6, std::string* err) {
-    JpegHeaderInternal H;
-    const int rc = parse_headers(data, size, H);
-    plan.info = H.info;
-    if (rc != FRP_OK) { if (err) *err = H.err; return rc; }
-    const frp_jpeg_info& I = H.info;
-    if (I.restart_interval != 0) { if (err) *err = "scan has restart intervals"; return FRP_ERR_INVALID; }
-    for (int c = 0; c < 3; ++c)
-        for (int i = 0; i < 64; ++i) plan.qtab[c * 64 + i] = c < I.components ? H.qt[H.comp_tq[c]][i] : 1;
-    for (int c = 0; c < 3; ++c) {
-        const int cc = c < I.components ? c : 0;
-        flatten_table(H.dc[H.comp_td[cc]], tables6[2 * c]);
-        flatten_table(H.ac[H.comp_ta[cc]], tables6[2 * c + 1]);
-    }
-    const uint8_t* p = H.scan;
-    const uint8_t* const end = data + size;
-    while (p < end) {
-        p = (const uint8_t*)memchr(p, 0xFF, (size_t)(end - p));
-        if (!p) { p = end; break; }
-        if (p + 1 < end && p[1] == 0x00) { p += 2; continue; }     // stuffed byte
-        break;                                                     // a marker, or a 0xFF as the file's last byte
-    }
-    if ((size_t)(p - H.scan) >= ((size_t)1 << 28)) { if (err) *err = "scan too large"; return FRP_ERR_INVALID; }
-    plan.scan = H.scan;
-    plan.scan_bytes = (size_t)(p - H.scan);
     return FRP_OK;
 }
 

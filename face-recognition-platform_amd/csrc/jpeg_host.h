@@ -1,4 +1,5 @@
-// Host half of the JPEG ingest (jpeg_host.cpp): header parsing + Huffman decoding of baseline JPEG stills, the buffer layouts of a batch.
+// Host half of the JPEG ingest (jpeg_host.cpp): header parsing + Huffman decoding of baseline JPEG stills, the scan plan of the device
+// entropy decoders, the buffer layouts of a batch.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -7,6 +8,7 @@
 #include <vector>
 
 #include "frp.h"
+#include "jpeg_entropy.h"
 
 namespace frp {
 
@@ -16,36 +18,24 @@ int jpeg_info(const uint8_t* data, size_t size, frp_jpeg_info* out, std::string*
 int jpeg_decode_coefficients(const uint8_t* data, size_t size, int16_t* coef, size_t coef_elems, uint16_t* qtab, frp_jpeg_info* info,
                              std::string* err);
 
-// What the device entropy decoder needs of one image (frp_upload_jpeg_async's device path): headers parsed as above, the scan
-// located, the restart markers found and checked (count and RST0..7 sequence).  Fails (FRP_ERR_INVALID) for files without
-// restart intervals and for anything the host decoder refuses.
-// Canonical Huffman table in the form both decoders walk (T.81 F.2.2.3) + a 9-bit look-ahead: (code length << 8) | value, 0 = a
-// longer code.  (Plain data: shared with the device code through frp_internal.h.)
-struct JpegHuffTableDev {
-    uint16_t fast[512];
-    int32_t mincode[17], maxcode[18], valptr[17];
-    uint8_t vals[256];
-};
-struct JpegDevicePlan {
+// What the device entropy decoders need of one image (ingest_api.cpp: plan_entropy_batch): headers parsed as above, the quantisation tables,
+// the six Huffman tables flattened (tables6: component c's DC table at 2c, its AC table at 2c + 1) and the scan located by ONE pass over its
+// 0xFF bytes.  Which pass, info.restart_interval decides - a caller that takes one kind of scan checks it:
+//   with restart intervals   every RSTn marker starts an interval: int_off[n_int + 1], count and RST0..7 sequence checked, FF FF fill
+//                            bytes skipped; the scan ends at the first other marker or at the end of the file.  Refused from 0xfffffff0
+//                            bytes or 0x7fffff intervals on.
+//   without                  int_off stays empty; the scan ends where the host decoder's bit reader stops taking bytes - at the first
+//                            0xFF that is not followed by a stuffed 0x00, or at the end of the file -, so both decoders see the same
+//                            bytes.  Refused from 2^28 bytes on.
+// Fails (FRP_ERR_INVALID) for these and for anything the host decoder's header parser refuses.
+struct JpegScanPlan {
     frp_jpeg_info info;
     uint16_t qtab[192];                 // [3][64] natural order
     const uint8_t* scan = nullptr;      // first entropy-coded byte
-    size_t scan_bytes = 0;              // up to the end of the last interval (the marker behind it, or the end of the file)
-    std::vector<uint32_t> int_off;      // [n_int + 1] offsets from `scan`
+    size_t scan_bytes = 0;              // up to the marker that ends the scan, or the end of the file
+    std::vector<uint32_t> int_off;      // [n_int + 1] offsets from `scan`; empty for a scan without restart intervals
 };
-int jpeg_plan_device_decode(const uint8_t* data, size_t size, JpegDevicePlan& plan, JpegHuffTableDev* tables6, std::string* err);
-
-// What the self-synchronising device decoder needs of one image WITHOUT restart intervals (frp_upload_jpeg_async's second device path,
-// jpeg_selfsync.h): headers, the six tables and the quantisation tables as above; the scan ends where the host decoder's bit reader stops
-// taking bytes - at the first 0xFF that is not followed by a stuffed 0x00, or at the end of the file -, so both decoders see the same
-// bytes.  Fails (FRP_ERR_INVALID) for files with restart intervals, for scans of 2^28 bytes or more and for what the host decoder refuses.
-struct JpegSelfsyncPlan {
-    frp_jpeg_info info;
-    uint16_t qtab[192];                 // [3][64] natural order
-    const uint8_t* scan = nullptr;      // first entropy-coded byte
-    size_t scan_bytes = 0;
-};
-int jpeg_plan_selfsync_decode(const uint8_t* data, size_t size, JpegSelfsyncPlan& plan, JpegHuffTableDev* tables6, std::string* err);
+int jpeg_plan_scan(const uint8_t* data, size_t size, JpegScanPlan& plan, JpegHuffTableDev* tables6, std::string* err);
 
 #define FRP_JPEG_LOCAL __attribute__((visibility("hidden")))   // for ingest_api.cpp and the test harness: not among the library's exports
 
@@ -61,7 +51,7 @@ struct JpegBatchLayout {
 };
 FRP_JPEG_LOCAL JpegBatchLayout jpeg_batch_layout(const frp_jpeg_info& info, int B);
 
-// Page-locked staging of the device entropy decode: scans (16-byte aligned each, soff[B + 1]) | interval offsets [B][n_int + 1] u32 |
+// Page-locked staging of the device entropy decode: scans (16-byte aligned each, soff[B + 1]) | offsets [B][n_int + 1] u32 |
 // Huffman tables [B][6] | quantisation tables, 384 bytes per image | error flags [B] i32 (read back) - every part 256-byte aligned.
 // The first o_err bytes go to the device.  too_large: the scans do not fit 32-bit offsets (the batch takes the host decoder).
 struct JpegDeviceStageLayout {

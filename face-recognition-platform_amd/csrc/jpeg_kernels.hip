@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "frp_internal.h"
+#include "jpeg_entropy_dev.h"
 
 namespace frp {
 
@@ -198,17 +199,15 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(JpegParams p) {
 // Entropy decoding on the device (round 5): one THREAD per restart interval.  The DC predictors and the byte alignment reset at
 // every RSTn marker (T.81 F.1.1.5), so a scan with restart intervals is a set of independent bit streams: a 1080p 4:2:0 frame
 // with one interval per MCU row is 68 of them, a batch of 32 frames 2,176 threads.  Each walks its bytes (un-stuffing 0xFF00),
-// decodes with the image's own tables (copied to LDS: one workgroup = 64 intervals of ONE image) and scatters the non-zero
+// decodes with the image's own tables (copied to LDS, jpeg_entropy_dev.h: one workgroup = 64 intervals of ONE image) and scatters the non-zero
 // coefficients into the buffer the inverse-DCT kernel reads (zeroed before the launch).  The same canonical decoding as
 // jpeg_host.cpp - bit-identical coefficients (tests/test_gpu_pipeline.py: both paths against PIL).  What moves over PCIe is the
 // compressed stream (~0.5 MB per 1080p frame) instead of 6.3 MB of coefficients, and the host keeps its threads.
-struct DevBits {
+struct DevBits : JpegBitWindow<DevBits> {     // (acc, nbits, peek / skip / extend / decode: jpeg_entropy.h)
     const unsigned* wp;           // next aligned dword of the interval's bytes
     unsigned long long raw;       // bytes fetched but not yet fed (next byte = bits 0..7)
     int rawn;                     // ... how many
     int left;                     // bytes of the interval not yet fed into the window (incl. those in `raw`)
-    unsigned long long acc;       // next bit of the stream = bit 63
-    int nbits;
     int pad;                      // zero bits fed behind the end of the interval
     // (bytes come in 8 at a time - two aligned dword loads -: fetched one by one, every lane of a wave waited a memory round trip
     // per byte of its own stream and a batch of 32 x 1080p took 18 ms)
@@ -253,43 +252,13 @@ struct DevBits {
             nbits += 8;
         }
     }
-    __device__ __forceinline__ unsigned peek(int n) const { return (unsigned)(acc >> (64 - n)); }
-    __device__ __forceinline__ void skip(int n) { acc <<= n; nbits -= n; }
-    __device__ __forceinline__ int extend(int s) {
-        if (s == 0) return 0;
-        const int v = (int)peek(s);
-        skip(s);
-        return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-    }
-    __device__ __forceinline__ int decode(const JpegHuffTableDev& t) {
-        const unsigned f = t.fast[peek(9)];
-        if (f) { skip((int)(f >> 8)); return (int)(f & 0xff); }
-        for (int len = 10; len <= 16; ++len) {
-            const int code = (int)peek(len);
-            if (t.maxcode[len] >= 0 && code <= t.maxcode[len] && code >= t.mincode[len]) {
-                skip(len);
-                return t.vals[t.valptr[len] + code - t.mincode[len]];
-            }
-        }
-        return -1;
-    }
 };
-
-__constant__ uint8_t kZigZagDev[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 __global__ __launch_bounds__(64) void jpeg_huffman_kernel(JpegHuffParams p) {
     __shared__ JpegHuffTableDev tab[6];
-
-    __shared__ uint8_t zz[64];                 // (in LDS: indexed per lane - from constant memory every symbol waited a vector-memory round trip)
-    zz[threadIdx.x] = kZigZagDev[threadIdx.x];
+    __shared__ uint8_t zz[64];
     const int b = blockIdx.y;
-    {   // this image's tables -> LDS (dwords: the struct is a multiple of 4 bytes)
-        const unsigned* src = reinterpret_cast<const unsigned*>(p.tables + (long)b * 6);
-        unsigned* dst = reinterpret_cast<unsigned*>(tab);
-        for (int i = threadIdx.x; i < (int)(6 * sizeof(JpegHuffTableDev) / 4); i += 64) dst[i] = src[i];
-    }
+    load_entropy_tables<64>(p.tables, b, tab, zz);
     __syncthreads();
     const int it = blockIdx.x * 64 + threadIdx.x;
     if (it >= p.n_int) return;
@@ -298,19 +267,19 @@ __global__ __launch_bounds__(64) void jpeg_huffman_kernel(JpegHuffParams p) {
     // an interval ends where the next one's marker starts (2 bytes in front of the next interval's first byte); the last one at the end of the data
     br.init(p.scan + io[it], p.scan + (it + 1 < p.n_int ? io[it + 1] - 2 : io[p.n_int]));
     int16_t* coef = p.coef + (long)b * p.coef_per_image;
-    const long total = (long)p.mcus_x * p.mcus_y;
+    const long total = (long)p.g.mcus_x * p.mcus_y;
     long m0 = (long)it * p.ri, m1 = m0 + p.ri;
     m1 = m1 < total ? m1 : total;
     int pred0 = 0, pred1 = 0, pred2 = 0;
     bool bad = false;
     for (long m = m0; m < m1 && !bad; ++m) {
-        const int my = (int)(m / p.mcus_x), mx = (int)(m - (long)my * p.mcus_x);
-        for (int c = 0; c < p.components && !bad; ++c) {
+        const int my = (int)(m / p.g.mcus_x), mx = (int)(m - (long)my * p.g.mcus_x);
+        for (int c = 0; c < p.g.components && !bad; ++c) {
             const JpegHuffTableDev& dct = tab[2 * c];
             const JpegHuffTableDev& act = tab[2 * c + 1];
-            for (int v = 0; v < p.vs[c] && !bad; ++v)
-                for (int hh = 0; hh < p.hs[c] && !bad; ++hh) {
-                    int16_t* blk = coef + p.comp_off[c] + ((long)(my * p.vs[c] + v) * p.bx[c] + (mx * p.hs[c] + hh)) * 64;
+            for (int v = 0; v < p.g.vs[c] && !bad; ++v)
+                for (int hh = 0; hh < p.g.hs[c] && !bad; ++hh) {
+                    int16_t* blk = coef + p.g.comp_off[c] + ((long)(my * p.g.vs[c] + v) * p.g.bx[c] + (mx * p.g.hs[c] + hh)) * 64;
                     br.fill();
                     const int s = br.decode(dct);
                     if (s < 0 || s > 11) { bad = true; break; }
@@ -358,7 +327,7 @@ hipError_t launch_jpeg_decode(const JpegParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_jpeg_huffman(const JpegHuffParams& p, hipStream_t stream) {
-    if (p.B <= 0 || p.n_int <= 0 || p.ri <= 0 || p.components <= 0 || p.components > 3 || !p.scan || !p.int_off || !p.tables || !p.coef || !p.err)
+    if (p.B <= 0 || p.n_int <= 0 || p.ri <= 0 || p.g.components <= 0 || p.g.components > 3 || !p.scan || !p.int_off || !p.tables || !p.coef || !p.err)
         return hipErrorInvalidValue;
     if (p.B > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)((p.n_int + 63) / 64), (unsigned)p.B), dim3(64), 0, stream, p);

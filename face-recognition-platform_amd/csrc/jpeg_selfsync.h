@@ -12,23 +12,20 @@
 //
 // Reads: the bytes [0, n_bytes) of the scan in aligned 8-byte words, so never beyond round_up(n_bytes, 8) - inside the 16-byte slot
 // the staging layout gives every scan (jpeg_device_stage_layout).  Bytes at and behind n_bytes count as zeros ("padding").
+// The bit window, the symbol decode and the zig-zag order are the ones every entropy decoder here uses: jpeg_entropy.h.
 #pragma once
 #include <stdint.h>
 
+#include "jpeg_entropy.h"
 #include "jpeg_host.h"
-
-#if defined(__HIPCC__)
-#define JSS_HD __host__ __device__ __forceinline__
-#else
-#define JSS_HD inline
-#endif
 
 namespace frp {
 
 #define JSS_WG 256                       // subsequences (threads) per workgroup
 #define JSS_MAX_SCAN (1u << 28)          // scans of this many bytes or more are refused (bit positions stay below 2^31)
 
-// geometry of the images of a batch (they share it): where block j of the scan lies in the coefficient buffer of JpegBatchLayout
+// geometry of the images of a batch (they share it): where block j of the scan lies in the coefficient buffer of JpegBatchLayout (both
+// device decoders: JpegHuffParams and JpegSelfsyncParams carry one)
 struct JssGeom {
     int components, bpm;                 // blocks per MCU (1 .. 6)
     int mcus_x;
@@ -38,7 +35,7 @@ struct JssGeom {
     uint8_t comp[8], bv[8], bh[8];       // block n of an MCU: its component, its row and column inside the component's part of the MCU
 };
 
-JSS_HD void jss_geom_blocks(JssGeom& g) {     // comp / bv / bh / bpm from components, hs, vs
+JPEG_HD void jss_geom_blocks(JssGeom& g) {     // comp / bv / bh / bpm from components, hs, vs
     int n = 0;
     for (int c = 0; c < g.components; ++c)
         for (int v = 0; v < g.vs[c]; ++v)
@@ -49,15 +46,25 @@ JSS_HD void jss_geom_blocks(JssGeom& g) {     // comp / bv / bh / bpm from compo
     g.bpm = n;
 }
 
+inline JssGeom jss_geom(const frp_jpeg_info& I, const JpegBatchLayout& L) {
+    JssGeom g{};
+    g.components = I.components;
+    g.mcus_x = I.mcus_x;
+    for (int c = 0; c < 3; ++c) { g.hs[c] = I.h_samp[c]; g.vs[c] = I.v_samp[c]; g.bx[c] = L.bx[c]; g.comp_off[c] = L.plane_off[c]; }
+    jss_geom_blocks(g);
+    g.total = (uint32_t)L.blocks_per_image;
+    return g;
+}
+
 // block j of the scan (MCU j / bpm, block j % bpm of it) -> its first coefficient
-JSS_HD long jss_block_addr(const JssGeom& g, uint32_t j) {
+JPEG_HD long jss_block_addr(const JssGeom& g, uint32_t j) {
     const uint32_t m = j / (uint32_t)g.bpm;
     const int n = (int)(j - m * (uint32_t)g.bpm), c = g.comp[n];
     const int my = (int)(m / (uint32_t)g.mcus_x), mx = (int)(m - (uint32_t)my * (uint32_t)g.mcus_x);
     return g.comp_off[c] + ((long)(my * g.vs[c] + g.bv[n]) * g.bx[c] + (mx * g.hs[c] + g.bh[n])) * 64;
 }
 // the k-th block of component c in SCAN order (4:2:0 luma: MCU by MCU, not row by row): the order the DC differences are summed in
-JSS_HD long jss_dc_addr(const JssGeom& g, int c, uint32_t k) {
+JPEG_HD long jss_dc_addr(const JssGeom& g, int c, uint32_t k) {
     const uint32_t per = (uint32_t)(g.hs[c] * g.vs[c]);
     const uint32_t m = k / per;
     const int r = (int)(k - m * per), v = r / g.hs[c], h = r - v * g.hs[c];
@@ -67,33 +74,32 @@ JSS_HD long jss_dc_addr(const JssGeom& g, int c, uint32_t k) {
 
 // state (p, n, z) in one word: equal words = equal continuations
 typedef unsigned long long JssState;
-JSS_HD JssState jss_pack(uint32_t p, int n, int z) { return (JssState)p | ((JssState)(unsigned)n << 32) | ((JssState)(unsigned)z << 40); }
-JSS_HD uint32_t jss_p(JssState s) { return (uint32_t)s; }
-JSS_HD int jss_n(JssState s) { return (int)((s >> 32) & 0xff); }
-JSS_HD int jss_z(JssState s) { return (int)((s >> 40) & 0xff); }
+JPEG_HD JssState jss_pack(uint32_t p, int n, int z) { return (JssState)p | ((JssState)(unsigned)n << 32) | ((JssState)(unsigned)z << 40); }
+JPEG_HD uint32_t jss_p(JssState s) { return (uint32_t)s; }
+JPEG_HD int jss_n(JssState s) { return (int)((s >> 32) & 0xff); }
+JPEG_HD int jss_z(JssState s) { return (int)((s >> 40) & 0xff); }
 
 // first byte of subsequence i: i * S, or the byte behind it when that one is the stuffed 0x00 of a 0xFF (inside entropy-coded data
 // a 0x00 behind a 0xFF is nothing else).  i == n_sub gives the end of the scan.
-JSS_HD uint32_t jss_start(const uint8_t* scan, uint32_t n_bytes, uint32_t i, uint32_t n_sub, uint32_t S) {
+JPEG_HD uint32_t jss_start(const uint8_t* scan, uint32_t n_bytes, uint32_t i, uint32_t n_sub, uint32_t S) {
     if (i >= n_sub) return n_bytes;
     const uint32_t o = i * S;
     return (o > 0 && scan[o] == 0x00 && scan[o - 1] == 0xFF) ? o + 1 : o;
 }
-JSS_HD uint32_t jss_subsequences(uint32_t n_bytes, uint32_t S) { return n_bytes == 0 ? 1u : (n_bytes + S - 1) / S; }
+JPEG_HD uint32_t jss_subsequences(uint32_t n_bytes, uint32_t S) { return n_bytes == 0 ? 1u : (n_bytes + S - 1) / S; }
 
-// Bit reader over the raw scan from an arbitrary bit position.  A 64-bit window, the next bit of the stream at bit 63 (as DevBits of
-// jpeg_kernels.hip); `ffm` moves with it and marks the last bit of every 0xFF data byte, so that the RAW position of the next bit
+// Bit reader over the raw scan from an arbitrary bit position.  The 64-bit window and the symbol decode of jpeg_entropy.h (as DevBits of
+// jpeg_kernels.hip); `ffm` moves with the window and marks the last bit of every 0xFF data byte, so that the RAW position of the next bit
 // can be told at any time: every byte with bits in the window stands for one raw byte, two if it is a 0xFF (its stuffed zero).
-struct JssBits {
+struct JssBits : JpegBitWindow<JssBits> {
     const unsigned long long* words;      // the scan, 8-byte aligned
     uint32_t n_bytes;
     uint32_t next;                        // raw offset of the next byte to feed (behind n_bytes: zeros)
     unsigned long long raw;               // bytes fetched but not yet fed (next byte = bits 0..7)
     int rawn;
-    unsigned long long acc, ffm;
-    int nbits;
+    unsigned long long ffm;
 
-    JSS_HD unsigned next_byte() {
+    JPEG_HD unsigned next_byte() {
         unsigned b = 0;
         if (next < n_bytes) {
             if (rawn == 0) { raw = words[next >> 3]; rawn = 8; }       // (next is a multiple of 8 here: word next / 8 starts inside the scan)
@@ -104,7 +110,7 @@ struct JssBits {
         ++next;
         return b;
     }
-    JSS_HD void fill() {
+    JPEG_HD void fill() {
         while (nbits <= 56) {
             const unsigned b = next_byte();
             if (b == 0xFF) { (void)next_byte(); ffm |= 1ull << (56 - nbits); }     // its stuffed zero goes with it
@@ -112,7 +118,7 @@ struct JssBits {
             nbits += 8;
         }
     }
-    JSS_HD void init(const uint8_t* scan, uint32_t n, uint32_t p) {
+    JPEG_HD void init(const uint8_t* scan, uint32_t n, uint32_t p) {
         words = (const unsigned long long*)__builtin_assume_aligned(scan, 8);
         n_bytes = n;
         next = p >> 3;
@@ -124,29 +130,10 @@ struct JssBits {
         fill();
         skip((int)(p & 7u));
     }
-    JSS_HD unsigned peek(int n) const { return (unsigned)(acc >> (64 - n)); }       // 1 <= n <= 32
-    JSS_HD void skip(int n) { acc <<= n; ffm <<= n; nbits -= n; }
-    JSS_HD uint32_t pos() const {
+    JPEG_HD void skip(int n) { acc <<= n; ffm <<= n; nbits -= n; }                    // (replaces the window's: ffm moves with acc)
+    JPEG_HD uint32_t pos() const {
         const uint32_t bytes = (uint32_t)((nbits + 7) >> 3) + (uint32_t)__builtin_popcountll(ffm);
         return (next - bytes) * 8u + (uint32_t)((8 - (nbits & 7)) & 7);
-    }
-    JSS_HD int extend(int s) {                                                       // T.81 F.2.2.1, s <= 15
-        if (s == 0) return 0;
-        const int v = (int)peek(s);
-        skip(s);
-        return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-    }
-    JSS_HD int decode(const JpegHuffTableDev& t) {                                   // (DevBits::decode as it is)
-        const unsigned f = t.fast[peek(9)];
-        if (f) { skip((int)(f >> 8)); return (int)(f & 0xff); }
-        for (int len = 10; len <= 16; ++len) {
-            const int code = (int)peek(len);
-            if (t.maxcode[len] >= 0 && code <= t.maxcode[len] && code >= t.mincode[len]) {
-                skip(len);
-                return t.vals[t.valptr[len] + code - t.mincode[len]];
-            }
-        }
-        return -1;
     }
 };
 
@@ -157,8 +144,8 @@ struct JssBits {
 // the image: an invalid code, a DC size above 11, an index above 63, or bits consumed behind the end of the scan.
 // Every iteration consumes at least one bit, so the loop ends within its budget of end_bit - p(entry) iterations.
 template <bool WRITE>
-JSS_HD int jss_decode(const uint8_t* scan, uint32_t n_bytes, const JpegHuffTableDev* tab, const uint8_t* zz, const JssGeom& g, JssState entry,
-                      uint32_t end_bit, int16_t* coef, uint32_t blk0, JssState* exit_state, uint32_t* completed) {
+JPEG_HD int jss_decode(const uint8_t* scan, uint32_t n_bytes, const JpegHuffTableDev* tab, const uint8_t* zz, const JssGeom& g, JssState entry,
+                       uint32_t end_bit, int16_t* coef, uint32_t blk0, JssState* exit_state, uint32_t* completed) {
     uint32_t p = jss_p(entry), blk = blk0, done = 0;
     int n = jss_n(entry), z = jss_z(entry), bad = 0;
     if (p < end_bit && !(WRITE && blk >= g.total)) {

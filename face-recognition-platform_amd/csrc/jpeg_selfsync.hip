@@ -1,6 +1,6 @@
 // Entropy decoding on the device for JPEG scans WITHOUT restart markers: the self-synchronising decoder (the algorithm and what every
-// thread runs: jpeg_selfsync.h; the host's part: ingest_api.cpp: selfsync_decode).  A scan is ONE serial bit stream; it is cut into
-// subsequences of S raw bytes, one thread each, JSS_WG of them per workgroup:
+// thread runs: jpeg_selfsync.h; the host's part: ingest_api.cpp: decode_selfsync; table load and prefix sum: jpeg_entropy_dev.h).  A scan
+// is ONE serial bit stream; it is cut into subsequences of S raw bytes, one thread each, JSS_WG of them per workgroup:
 //   jss_sync_kernel, launch 0   every thread decodes its subsequence from the guessed state (byte boundary, block 0 of an MCU, DC next),
 //                               then the workgroup iterates entry(t) = exit(t - 1) over the exit states it holds in LDS - a thread whose
 //                               entry changed decodes again - until a round changes nothing (at most JSS_WG rounds: round r leaves
@@ -18,22 +18,11 @@
 #include <stdint.h>
 
 #include "frp_internal.h"
+#include "jpeg_entropy_dev.h"
 
 namespace frp {
 
 namespace {
-
-__constant__ uint8_t kZigZagSs[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// this image's tables and the zig-zag order -> LDS (indexed per lane: from constant memory every symbol waited a vector-memory round trip)
-__device__ __forceinline__ void load_tables(const JpegSelfsyncParams& p, int b, JpegHuffTableDev* tab, uint8_t* zz) {
-    const unsigned* src = reinterpret_cast<const unsigned*>(p.tables + (long)b * 6);
-    unsigned* dst = reinterpret_cast<unsigned*>(tab);
-    for (int i = threadIdx.x; i < (int)(6 * sizeof(JpegHuffTableDev) / 4); i += JSS_WG) dst[i] = src[i];
-    if (threadIdx.x < 64) zz[threadIdx.x] = kZigZagSs[threadIdx.x];
-}
 
 __global__ __launch_bounds__(JSS_WG) void jss_sync_kernel(JpegSelfsyncParams p, int k) {
     __shared__ JpegHuffTableDev tab[6];
@@ -52,7 +41,7 @@ __global__ __launch_bounds__(JSS_WG) void jss_sync_kernel(JpegSelfsyncParams p, 
         if (t == 0) wg_out[wg] = p.exit_[sub0 + m - 1];
         return;
     }
-    load_tables(p, b, tab, zz);
+    load_entropy_tables<JSS_WG>(p.tables, b, tab, zz);
     const uint8_t* scan = p.scan + im[0];
     const uint32_t i = first + t, gi = sub0 + i;
     const bool live = (uint32_t)t < m;
@@ -100,17 +89,10 @@ __global__ __launch_bounds__(JSS_WG) void jss_count_kernel(JpegSelfsyncParams p)
     for (uint32_t c0 = 0; c0 < n_sub; c0 += JSS_WG) {
         const uint32_t i = c0 + t;
         const uint32_t v = i < n_sub ? p.cnt[sub0 + i] : 0u;
-        sc[t] = v;
-        __syncthreads();
-        for (int d = 1; d < JSS_WG; d <<= 1) {
-            const uint32_t add = t >= d ? sc[t - d] : 0u;
-            __syncthreads();
-            sc[t] += add;
-            __syncthreads();
-        }
-        if (i < n_sub) p.base[sub0 + i] = running + sc[t] - v;
-        running += sc[JSS_WG - 1];
-        __syncthreads();
+        uint32_t sum;
+        const uint32_t incl = wg_inclusive_scan<JSS_WG>(sc, v, sum);
+        if (i < n_sub) p.base[sub0 + i] = running + incl - v;
+        running += sum;
     }
     if (t == 0) {
         int32_t* st = p.stats + 4 * b;
@@ -127,7 +109,7 @@ __global__ __launch_bounds__(JSS_WG) void jss_write_kernel(JpegSelfsyncParams p)
     const uint32_t* im = p.img + 4 * b;
     const uint32_t n_bytes = im[1], n_sub = im[2], sub0 = im[3];
     if (blockIdx.x * JSS_WG >= n_sub) return;
-    load_tables(p, b, tab, zz);
+    load_entropy_tables<JSS_WG>(p.tables, b, tab, zz);
     __syncthreads();
     const uint32_t i = blockIdx.x * JSS_WG + t;
     if (i >= n_sub) return;
@@ -151,17 +133,10 @@ __global__ __launch_bounds__(JSS_WG) void jss_dc_kernel(JpegSelfsyncParams p) {
     for (uint32_t c0 = 0; c0 < nb; c0 += JSS_WG) {
         const uint32_t kk = c0 + t;
         int16_t* d = kk < nb ? coef + jss_dc_addr(p.g, c, kk) : nullptr;
-        sc[t] = d ? (uint32_t)(int32_t)*d : 0u;
-        __syncthreads();
-        for (int s = 1; s < JSS_WG; s <<= 1) {
-            const uint32_t add = t >= s ? sc[t - s] : 0u;
-            __syncthreads();
-            sc[t] += add;
-            __syncthreads();
-        }
-        if (d) *d = (int16_t)(int32_t)(running + sc[t]);
-        running += sc[JSS_WG - 1];
-        __syncthreads();
+        uint32_t sum;
+        const uint32_t incl = wg_inclusive_scan<JSS_WG>(sc, d ? (uint32_t)(int32_t)*d : 0u, sum);
+        if (d) *d = (int16_t)(int32_t)(running + incl);
+        running += sum;
     }
 }
 

@@ -20,7 +20,7 @@
         if (!(cond)) { fprintf(stderr, "%s: B %d: layout check failed: %s\n", path, B, #cond); exit(3); } \
     } while (0)
 
-static void check_layouts(const char* path, const frp_jpeg_info& info, const frp::JpegDevicePlan* plan, size_t file_bytes) {
+static void check_layouts(const char* path, const frp_jpeg_info& info, const frp::JpegScanPlan* plan, size_t file_bytes) {
     for (int B : {1, 3, 32}) {
         const frp::JpegBatchLayout L = frp::jpeg_batch_layout(info, B);
         const unsigned __int128 b = (unsigned)B;
@@ -89,17 +89,17 @@ int main(int argc, char** argv) {
                 free(coef);
             }
         }
-        {   // the plan of the device entropy decode (headers + restart-marker scan) over the same bytes
-            frp::JpegDevicePlan plan;
+        {   // the plan of the device entropy decode (headers + the pass over the scan's 0xFF bytes) over the same bytes
+            frp::JpegScanPlan plan;
             frp::JpegHuffTableDev tabs[6];
             std::string e2;
-            const int rc2 = frp::jpeg_plan_device_decode(buf, (size_t)n, plan, tabs, &e2);
+            const int rc2 = frp::jpeg_plan_scan(buf, (size_t)n, plan, tabs, &e2);
             if (rc2 == FRP_OK) {
                 volatile unsigned sum = 0;
                 for (size_t k = 0; k + 1 < plan.int_off.size(); ++k) sum += plan.scan[plan.int_off[k] < plan.scan_bytes ? plan.int_off[k] : 0];
                 if (plan.scan_bytes) sum += plan.scan[plan.scan_bytes - 1];
             }
-            if (rc == FRP_OK) check_layouts(argv[i], info, rc2 == FRP_OK ? &plan : nullptr, (size_t)n);
+            if (rc == FRP_OK) check_layouts(argv[i], info, rc2 == FRP_OK && plan.info.restart_interval > 0 ? &plan : nullptr, (size_t)n);
         }
         if (rc == FRP_OK) ++decoded; else ++refused;
         free(buf);

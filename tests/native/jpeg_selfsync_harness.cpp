@@ -1,4 +1,4 @@
-// CPU harness of the self-synchronising JPEG entropy decoder (csrc/jpeg_selfsync.h: the per-thread routines the kernels of
+// CPU harness of the self-synchronising JPEG entropy decoder (csrc/jpeg_selfsync.h over csrc/jpeg_entropy.h: the per-thread routines the kernels of
 // csrc/jpeg_selfsync.hip run), built by tests/test_jpeg_selfsync_host.py with g++ -fsanitize=address,undefined.  The grid is emulated
 // serially, launch by launch and workgroup by workgroup as the kernels run it: speculate, rounds to the fix-point (inside a workgroup, then
 // across workgroups with the boundary states double-buffered between launches), count, write, DC sums.  Every input is copied into a heap
@@ -22,10 +22,6 @@
 
 using namespace frp;
 
-static const uint8_t kZigZag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
 #define REQUIRE(cond, ...)                                                     \
     do {                                                                       \
         if (!(cond)) { fprintf(stderr, "%s: ", path); fprintf(stderr, __VA_ARGS__); fprintf(stderr, " [%s]\n", #cond); exit(3); } \
@@ -43,7 +39,7 @@ struct Emu {
     uint32_t rounds = 0;                  // over the launches: the most rounds a workgroup of that launch ran with a change
 
     uint32_t start_bit(uint32_t i) const { return jss_start(scan, n_bytes, i, n_sub, S) * 8u; }
-    void decode(uint32_t i) { jss_decode<false>(scan, n_bytes, tab, kZigZag, g, entry[i], start_bit(i + 1), nullptr, 0, &exit_[i], &cnt[i]); }
+    void decode(uint32_t i) { jss_decode<false>(scan, n_bytes, tab, kJpegZigZag, g, entry[i], start_bit(i + 1), nullptr, 0, &exit_[i], &cnt[i]); }
 
     // one launch of the synchronisation kernel; -> the rounds of the launch (0: nothing changed)
     uint32_t launch(int k) {
@@ -101,7 +97,7 @@ struct Emu {
         int err = running < g.total;
         // write
         for (uint32_t i = 0; i < n_sub; ++i)
-            err |= jss_decode<true>(scan, n_bytes, tab, kZigZag, g, entry[i], start_bit(i + 1), coef, base[i], nullptr, nullptr);
+            err |= jss_decode<true>(scan, n_bytes, tab, kJpegZigZag, g, entry[i], start_bit(i + 1), coef, base[i], nullptr, nullptr);
         // DC: running sums per component in scan order
         for (int c = 0; c < g.components; ++c) {
             const uint32_t nb = g.total / (uint32_t)g.bpm * (uint32_t)(g.hs[c] * g.vs[c]);
@@ -141,13 +137,15 @@ int main(int argc, char** argv) {
             ref.assign(ce, 0);
             rc = jpeg_decode_coefficients(buf, (size_t)n, ref.data(), ce, q, &info, &err);
         }
-        JpegSelfsyncPlan plan;
+        JpegScanPlan plan;
         JpegHuffTableDev tabs[6];
         std::string e2;
-        const int rc2 = jpeg_plan_selfsync_decode(buf, (size_t)n, plan, tabs, &e2);
+        const int rc2 = jpeg_plan_scan(buf, (size_t)n, plan, tabs, &e2);
+        if (plan.info.restart_interval != 0 && plan.info.width > 0) { ++skipped; printf("%s skipped\n", path); free(buf); continue; }
         if (rc2 != FRP_OK) {
-            if (plan.info.restart_interval != 0 && plan.info.width > 0) { ++skipped; printf("%s skipped\n", path); }
-            else { REQUIRE(rc != FRP_OK, "the plan refuses (%s) what the host decoder accepts", e2.c_str()); ++refused; printf("%s host=0\n", path); }
+            REQUIRE(rc != FRP_OK, "the plan refuses (%s) what the host decoder accepts", e2.c_str());
+            ++refused;
+            printf("%s host=0\n", path);
             free(buf);
             continue;
         }
@@ -166,13 +164,8 @@ int main(int argc, char** argv) {
         E.scan = scan;
         E.n_bytes = (uint32_t)plan.scan_bytes;
         E.tab = tabs;
-        JssGeom& g = E.g;
-        memset(&g, 0, sizeof(g));
-        g.components = plan.info.components;
-        g.mcus_x = plan.info.mcus_x;
-        for (int c = 0; c < 3; ++c) { g.hs[c] = plan.info.h_samp[c]; g.vs[c] = plan.info.v_samp[c]; g.bx[c] = L.bx[c]; g.comp_off[c] = L.plane_off[c]; }
-        jss_geom_blocks(g);
-        g.total = (uint32_t)L.blocks_per_image;
+        E.g = jss_geom(plan.info, L);
+        const JssGeom& g = E.g;
         REQUIRE(g.bpm >= 1 && g.bpm <= 6 && (size_t)g.total * 64 == L.coef_elems && (uint32_t)(plan.info.mcus_x * plan.info.mcus_y * g.bpm) == g.total, "geometry");
         printf("%s host=%d", path, rc == FRP_OK ? 1 : 0);
         for (uint32_t S : {16u, 32u, 128u, 1024u}) {

@@ -40,6 +40,15 @@ struct Ingest {   // frame ingest (ingest_api.cpp: nothing else reads or writes 
     frp::DevBuf jpeg_ss;
     hipEvent_t ev_jpeg_h2d[2] = {nullptr, nullptr};     // the copy out of jpeg_pin[i] has finished
     bool jpeg_h2d_pending[2] = {false, false};
+    // YUV 4:2:0 ingest (frp_upload_yuv / frp_upload_yuv_async): host planes are copied into yuv_stage (packed, W * H * 3 / 2 bytes per
+    // frame); the kernel finds every frame's planes - there or in the caller's device surfaces - through a table of addresses.  The table
+    // has two turns: yuv_pin (page-locked, both turns) is the source of an asynchronous copy into the turn's half of yuv_tab, and
+    // ev_yuv[turn], recorded behind the turn's kernel, says that the copy has read the one and the kernel the other (and yuv_stage).
+    frp::DevBuf yuv_stage, yuv_tab;
+    void* yuv_pin = nullptr;
+    int yuv_turn = 0;
+    hipEvent_t ev_yuv[2] = {nullptr, nullptr};
+    bool yuv_pending[2] = {false, false};
 };
 
 struct frp_handle {

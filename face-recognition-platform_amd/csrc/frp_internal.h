@@ -235,6 +235,19 @@ struct JpegParams {
 };
 hipError_t launch_jpeg_decode(const JpegParams& p, hipStream_t stream);
 
+// YUV 4:2:0 ingest (yuv_kernels.hip; frp.h: frp_upload_yuv): decoder surfaces -> BGR frames.  The constants of one matrix, see the kernel file:
+// y = max(0, Y - yoff) * cy, R = clamp((y + cvr * v + rnd) >> sh), G = clamp((y - cvg * v - cug * u + rnd) >> sh), B = clamp((y + cub * u + rnd) >> sh)
+struct YuvCoef { int yoff, cy, cvr, cvg, cug, cub, rnd, sh; };
+struct YuvParams {
+    const uint8_t* const* tab;   // [B][3] device addresses per frame: Y, U (semi-planar: the interleaved plane), V (semi-planar: unused)
+    uint8_t* frames;             // out: [B, H, W, 3] u8 BGR
+    int B, W, H;                 // W, H even
+    int64_t y_pitch, c_pitch;    // bytes per row of the Y plane / of each chroma plane
+    int ush;                     // semi-planar: 0 - U is the first byte of a pair (NV12), 8 - V is (NV21)
+    YuvCoef k;
+};
+hipError_t launch_yuv_to_bgr(const YuvParams& p, bool semi_planar, bool fast, hipStream_t stream);
+
 // Entropy decoding ON THE DEVICE for streams with restart intervals (round 5): the DC predictors reset at every RSTn marker, so the
 // intervals of a scan are independent bit streams - one thread each (jpeg_kernels.hip: jpeg_huffman_kernel).  Canonical Huffman
 // tables: jpeg_entropy.h: JpegHuffTableDev.

@@ -1,5 +1,6 @@
 // Frame ingest of libfrp.so: the blocking upload into the resident buffer, the staged upload of the NEXT batch on the copy stream (raw
-// frames out of pageable or page-locked memory; JPEG stills with the entropy decode on host threads or on the device), the swap that
+// frames out of pageable or page-locked memory; JPEG stills with the entropy decode on host threads or on the device; YUV 4:2:0 surfaces
+// of a decoder out of host or device memory), the swap that
 // makes the staged batch resident.  Everything here works on h->in (frp_handle.h: struct Ingest); the pass that reads the resident
 // frames: frp_api.cpp.  Sizes and offsets of the JPEG buffers: jpeg_host.cpp (jpeg_batch_layout, jpeg_device_stage_layout).
 #include <atomic>
@@ -33,11 +34,12 @@ bool frp::init_ingest(frp_handle* h) {
 
 void frp::release_ingest(frp_handle* h) {       // (frp_destroy has waited for both streams)
     Ingest& in = h->in;
-    for (DevBuf* b : {&in.frames_next, &in.jpeg_coef, &in.jpeg_planes, &in.jpeg_scan, &in.jpeg_err, &in.jpeg_ss}) release(*b);
+    for (DevBuf* b : {&in.frames_next, &in.jpeg_coef, &in.jpeg_planes, &in.jpeg_scan, &in.jpeg_err, &in.jpeg_ss, &in.yuv_stage, &in.yuv_tab}) release(*b);
+    if (in.yuv_pin) (void)hipHostFree(in.yuv_pin);
     for (void* p : in.pinned) (void)hipHostFree(p);
     for (void* p : in.jpeg_pin)
         if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {in.ev_jpeg_h2d[0], in.ev_jpeg_h2d[1], in.ev_next_ready, in.ev_next_free})
+    for (hipEvent_t e : {in.ev_jpeg_h2d[0], in.ev_jpeg_h2d[1], in.ev_yuv[0], in.ev_yuv[1], in.ev_next_ready, in.ev_next_free})
         if (e) (void)hipEventDestroy(e);
     if (in.copy_stream) (void)hipStreamDestroy(in.copy_stream);
 }
@@ -331,6 +333,128 @@ int decode_on_host(frp_handle* h, const uint8_t* const* jpegs, const size_t* siz
     return FRP_OK;
 }
 
+// ---- YUV 4:2:0 surfaces (frp.h: frp_upload_yuv; the kernels and the arithmetic: yuv_kernels.hip) ----
+constexpr int kYuvMaxBatch = 1024;
+constexpr size_t kYuvTabBytes = (size_t)kYuvMaxBatch * 3 * sizeof(void*);       // one turn of the plane table
+// yoff, cy, cvr, cvg, cug, cub, rnd, sh per FRP_YUV_BT601 / _BT709 / _JFIF (frp.h has the formulas)
+const YuvCoef kYuvCoef[3] = {{16, 1220542, 1673527, 852492, 409993, 2116026, 1 << 19, 20},
+                             {16, 1220542, 1880097, 558891, 223347, 2214593, 1 << 19, 20},
+                             {0, 65536, 91881, 46802, 22554, 116130, 32768, 16}};
+bool yuv_semi_planar(int layout) { return layout == FRP_YUV_NV12 || layout == FRP_YUV_NV21; }
+
+int check_yuv(frp_handle* h, const frp_yuv_desc* d, const uint8_t* const* planes, int B) {
+    if (!d) return fail(h, FRP_ERR_INVALID, "yuv: desc is null");
+    if (!planes) return fail(h, FRP_ERR_INVALID, "yuv: planes is null");
+    if (d->struct_size != (int32_t)sizeof(frp_yuv_desc)) return fail(h, FRP_ERR_INVALID, "yuv: struct_size is not sizeof(frp_yuv_desc)");
+    if (d->layout < FRP_YUV_NV12 || d->layout > FRP_YUV_YV12) return fail(h, FRP_ERR_INVALID, "yuv: unknown layout");
+    if (d->matrix < FRP_YUV_BT601 || d->matrix > FRP_YUV_JFIF) return fail(h, FRP_ERR_INVALID, "yuv: unknown matrix");
+    if (d->flags & ~FRP_YUV_DEVICE) return fail(h, FRP_ERR_INVALID, "yuv: unknown bits in flags");
+    if (d->width <= 0 || d->width % 2) return fail(h, FRP_ERR_INVALID, "yuv: width must be positive and even");
+    if (d->height <= 0 || d->height % 2) return fail(h, FRP_ERR_INVALID, "yuv: height must be positive and even");
+    if ((int64_t)d->width * d->height > (1ll << 30)) return fail(h, FRP_ERR_INVALID, "yuv: width * height beyond 2^30 pixels");
+    if (d->y_pitch < d->width) return fail(h, FRP_ERR_INVALID, "yuv: y_pitch is smaller than width");
+    const bool semi = yuv_semi_planar(d->layout);
+    if (d->c_pitch < (semi ? d->width : d->width / 2)) return fail(h, FRP_ERR_INVALID, semi ? "yuv: c_pitch is smaller than width" : "yuv: c_pitch is smaller than width / 2");
+    if (B < 1 || B > kYuvMaxBatch) return fail(h, FRP_ERR_INVALID, "yuv: B must be 1 .. 1024");
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < (semi ? 2 : 3); ++k)
+            if (!planes[3 * b + k]) return fail(h, FRP_ERR_INVALID, "yuv: planes[" + std::to_string(b) + "][" + std::to_string(k) + "] is null");
+    return FRP_OK;
+}
+
+// the buffers a YUV batch needs besides its frame buffer (`more`: that one, when it is the staging buffer), and the page-locked table
+int prepare_yuv(frp_handle* h, const frp_yuv_desc& d, int B, std::vector<Staged> more) {
+    Ingest& in = h->in;
+    if (!(d.flags & FRP_YUV_DEVICE)) more.push_back({&in.yuv_stage, (size_t)B * d.width * d.height * 3 / 2});
+    more.push_back({&in.yuv_tab, 2 * kYuvTabBytes});
+    FRPCHK(grow_staged(h, more));
+    if (!in.yuv_pin && hipHostMalloc(&in.yuv_pin, 2 * kYuvTabBytes, hipHostMallocDefault) != hipSuccess) {
+        in.yuv_pin = nullptr;
+        return fail(h, FRP_ERR_OOM, "hipHostMalloc (YUV plane table) failed");
+    }
+    return FRP_OK;
+}
+
+// Queues the work of one batch on `s` (yuv_to_frames below owns the turn and its event): host planes into in.yuv_stage (neighbouring copies
+// that continue each other in the source and in the packed destination go as one - a pool of pitched NV12 surfaces is a single 2-D copy,
+// packed frames back to back a single linear one), the plane table of `turn`, the kernel into `dst` [B, H, W, 3].
+int queue_yuv_turn(frp_handle* h, const frp_yuv_desc& d, const uint8_t* const* planes, int B, void* dst, hipStream_t s, int turn) {
+    Ingest& in = h->in;
+    const bool semi = yuv_semi_planar(d.layout), device = (d.flags & FRP_YUV_DEVICE) != 0;
+    const size_t W = (size_t)d.width, H = (size_t)d.height, y_bytes = W * H, c_bytes = semi ? y_bytes / 2 : y_bytes / 4;
+    const uint8_t** tab = (const uint8_t**)((char*)in.yuv_pin + (size_t)turn * kYuvTabBytes);
+    int64_t y_pitch = d.y_pitch, c_pitch = d.c_pitch;
+    if (device) {
+        for (int i = 0; i < 3 * B; ++i) tab[i] = i % 3 == 2 && semi ? nullptr : planes[i];
+    } else {
+        if (in.yuv_pending[turn ^ 1]) HIPCHK(h, hipStreamWaitEvent(s, in.ev_yuv[turn ^ 1], 0));       // the previous batch's kernel may still read the stage
+        struct Copy { size_t dst; const uint8_t* src; size_t width, rows, pitch; };
+        std::vector<Copy> jobs;
+        auto add = [&jobs](size_t at, const uint8_t* src, size_t width, size_t rows, size_t pitch) {
+            if (pitch == width || rows == 1) { width *= rows; rows = 1; pitch = width; }           // dense: one run of bytes
+            if (!jobs.empty()) {
+                Copy& j = jobs.back();
+                const bool follows = j.dst + j.width * j.rows == at;
+                if (follows && j.rows == 1 && rows == 1 && j.src + j.width == src) { j.width += width; j.pitch = j.width; return; }
+                if (follows && j.rows > 1 && rows > 1 && j.width == width && j.pitch == pitch && j.src + j.rows * j.pitch == src) { j.rows += rows; return; }
+            }
+            jobs.push_back({at, src, width, rows, pitch});
+        };
+        uint8_t* stage = (uint8_t*)in.yuv_stage.p;
+        const size_t frame_bytes = y_bytes * 3 / 2, c_w = semi ? W : W / 2;
+        for (int b = 0; b < B; ++b) {
+            const size_t at = (size_t)b * frame_bytes;
+            add(at, planes[3 * b], W, H, (size_t)d.y_pitch);
+            add(at + y_bytes, planes[3 * b + 1], c_w, H / 2, (size_t)d.c_pitch);
+            if (!semi) add(at + y_bytes + c_bytes, planes[3 * b + 2], c_w, H / 2, (size_t)d.c_pitch);
+            tab[3 * b] = stage + at;
+            tab[3 * b + 1] = stage + at + y_bytes;
+            tab[3 * b + 2] = semi ? nullptr : stage + at + y_bytes + c_bytes;
+        }
+        for (const Copy& j : jobs) {
+            if (j.rows == 1) HIPCHK(h, hipMemcpyAsync(stage + j.dst, j.src, j.width, hipMemcpyHostToDevice, s));
+            else HIPCHK(h, hipMemcpy2DAsync(stage + j.dst, j.width, j.src, j.pitch, j.width, j.rows, hipMemcpyHostToDevice, s));
+        }
+        y_pitch = (int64_t)W;
+        c_pitch = (int64_t)c_w;
+    }
+    if (d.layout == FRP_YUV_YV12)
+        for (int b = 0; b < B; ++b) std::swap(tab[3 * b + 1], tab[3 * b + 2]);          // the kernel's order is Y, U, V
+    // the fast path's conditions (yuv_kernels.hip); one frame that misses them sends the whole batch down the general path
+    const uintptr_t c_align = semi ? 15 : 7;
+    bool fast = W % 16 == 0 && y_pitch % 16 == 0 && (c_pitch & (int64_t)c_align) == 0;
+    for (int b = 0; b < B && fast; ++b)
+        fast = ((uintptr_t)tab[3 * b] & 15) == 0 && ((uintptr_t)tab[3 * b + 1] & c_align) == 0 && ((uintptr_t)tab[3 * b + 2] & c_align) == 0;
+    char* dev_tab = (char*)in.yuv_tab.p + (size_t)turn * kYuvTabBytes;
+    HIPCHK(h, hipMemcpyAsync(dev_tab, tab, (size_t)B * 3 * sizeof(void*), hipMemcpyHostToDevice, s));
+    YuvParams p{};
+    p.tab = (const uint8_t* const*)dev_tab;
+    p.frames = (uint8_t*)dst;
+    p.B = B; p.W = d.width; p.H = d.height;
+    p.y_pitch = y_pitch; p.c_pitch = c_pitch;
+    p.ush = d.layout == FRP_YUV_NV21 ? 8 : 0;
+    p.k = kYuvCoef[d.matrix];
+    const hipError_t e = launch_yuv_to_bgr(p, semi, fast, s);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("yuv to bgr: ") + hipGetErrorString(e));
+    return FRP_OK;
+}
+
+// One batch on `s` through the next turn of the plane table.  The turn's event is recorded behind whatever queue_yuv_turn queued, also when
+// it returns an error half way (copies out of the page-locked table may be in flight then): the next use of the turn waits for them.
+int yuv_to_frames(frp_handle* h, const frp_yuv_desc& d, const uint8_t* const* planes, int B, void* dst, hipStream_t s) {
+    Ingest& in = h->in;
+    const int turn = in.yuv_turn;
+    if (in.yuv_pending[turn]) HIPCHK(h, hipEventSynchronize(in.ev_yuv[turn]));         // the table of two batches ago: copied and read
+    in.yuv_pending[turn] = false;
+    if (!in.ev_yuv[turn]) HIPCHK(h, hipEventCreateWithFlags(&in.ev_yuv[turn], hipEventDisableTiming));
+    in.yuv_turn ^= 1;
+    const int rc = queue_yuv_turn(h, d, planes, B, dst, s, turn);
+    const hipError_t e = hipEventRecord(in.ev_yuv[turn], s);
+    in.yuv_pending[turn] = e == hipSuccess;
+    if (rc == FRP_OK && e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("hipEventRecord (YUV turn): ") + hipGetErrorString(e));
+    return rc;
+}
+
 }  // namespace
 
 int frp::upload_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride) {
@@ -480,6 +604,42 @@ int frp_jpeg_selfsync_coefficients(frp_handle* h, const uint8_t* const* jpegs, c
     FRPCHK(decode_selfsync(h, eb, B, I, L, turn, false, stats));
     HIPCHK(h, hipMemcpyAsync(coef, in.jpeg_coef.p, L.coef_bytes, hipMemcpyDeviceToHost, in.copy_stream));
     HIPCHK(h, hipStreamSynchronize(in.copy_stream));
+    return FRP_OK;
+}
+
+int frp_upload_yuv(frp_handle* h, const frp_yuv_desc* desc, const uint8_t* const* planes, int32_t B) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    FRPCHK(check_yuv(h, desc, planes, B));
+    FRPCHK(prepare_yuv(h, *desc, B, {}));
+    FRPCHK(ensure(h, h->frames, (size_t)B * desc->height * desc->width * 3));
+    rec(h, EV_START);
+    FRPCHK(yuv_to_frames(h, *desc, planes, B, h->frames.p, h->stream));
+    rec(h, EV_H2D);
+    set_resident(h, B, desc->height, desc->width);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return FRP_OK;
+}
+
+int frp_upload_yuv_async(frp_handle* h, const frp_yuv_desc* desc, const uint8_t* const* planes, int32_t B) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);      // copy stream only (as frp_upload_frames_async)
+    FRPCHK(check_yuv(h, desc, planes, B));
+    FRPCHK(prepare_yuv(h, *desc, B, {{&h->in.frames_next, (size_t)B * desc->height * desc->width * 3}}));
+    FRPCHK(begin_staging(h));
+    FRPCHK(yuv_to_frames(h, *desc, planes, B, h->in.frames_next.p, h->in.copy_stream));
+    return end_staging(h, B, desc->height, desc->width);
+}
+
+int frp_get_frames(frp_handle* h, uint8_t* out, int64_t out_bytes, int32_t first, int32_t n) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (h->rB <= 0 || !h->frames.p) return fail(h, FRP_ERR_INVALID, "no resident frames");
+    if (first < 0 || n <= 0 || (int64_t)first + n > h->rB) return fail(h, FRP_ERR_INVALID, "get_frames: first / n outside the resident batch");
+    const int64_t frame_bytes = (int64_t)h->rH * h->rW * 3;
+    if (!out || out_bytes < n * frame_bytes) return fail(h, FRP_ERR_INVALID, "get_frames: out_bytes too small");
+    HIPCHK(h, hipMemcpyAsync(out, (const char*)h->frames.p + first * frame_bytes, (size_t)(n * frame_bytes), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return FRP_OK;
 }
 

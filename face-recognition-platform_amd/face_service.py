@@ -37,6 +37,9 @@ import numpy as np
 from . import lanes, native
 from .gallery import Gallery
 from .mjpeg import JpegBatch
+from .yuv import YuvBatch
+
+_SOURCE_BATCHES = (JpegBatch, YuvBatch)      # batches that are not pixel arrays yet: they carry `hw` and `decode()`
 
 logger = logging.getLogger(__name__)
 
@@ -231,13 +234,13 @@ class FaceService:
 
     def _quality_of(self, eng, frames, faces: List[Tuple[int, Tuple[int, int, int, int]]], rgb: bool) -> List[Dict[str, Any]]:
         """assess_face_quality for `faces` = [(frame index, (top, right, bottom, left))] of the batch `frames` ([B,H,W,3] in RGB or
-        BGR order, or a JpegBatch) that is RESIDENT on `eng`: one Engine.face_quality call for all rectangles the device takes;
+        BGR order, or a JpegBatch / YuvBatch) that is RESIDENT on `eng`: one Engine.face_quality call for all rectangles the device takes;
         the host method on the caller's pixels for the others (a location that clipping left empty) and for an engine without
         face_quality (the tests' FakeEngine).  In the order of `faces`."""
         if not faces:
             return []
-        H, W = frames.hw if isinstance(frames, JpegBatch) else frames.shape[1:3]
-        pixels = [None if isinstance(frames, JpegBatch) else frames]
+        H, W = frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[1:3]
+        pixels = [None if isinstance(frames, _SOURCE_BATCHES) else frames]
 
         def on_host(b, loc):
             if pixels[0] is None:
@@ -744,6 +747,8 @@ class FaceService:
         tol = self.tolerance if threshold is None else min(self.tolerance, threshold)   # camera.py:250
         G = self.ENCODINGS
         overlapped = take_next is not None and staged is not None
+        if isinstance(frames_bgr, YuvBatch):
+            frames_bgr.validate()                                      # (an odd size, mixed geometry: before anything reaches the engine)
         # The device returns gallery ROW indices; store/delete move rows (swap-remove).  The guard (exclusive for
         # process_frames, shared between the lanes of process_stream) is held over the device call and the
         # row -> name snapshot, so a concurrent delete can neither mis-attribute a face to the identity that was
@@ -773,7 +778,8 @@ class FaceService:
                     idle()                                             # the PREVIOUS batch's result dicts, under this batch's kernels
                 out = eng.fetch_results()                              # waits for the pass
                 qual = self._stream_quality(eng, frames_bgr, out) if quality else None      # (before the lane's next swap_frames)
-            elif isinstance(frames_bgr, JpegBatch) and hasattr(eng, "upload_jpeg_async"):
+            elif (isinstance(frames_bgr, JpegBatch) and hasattr(eng, "upload_jpeg_async")) or \
+                    (isinstance(frames_bgr, YuvBatch) and hasattr(eng, "upload_yuv_async") and hasattr(eng, "swap_frames")):
                 with eng.sequence():
                     self._stage_on(eng, frames_bgr)
                     eng.swap_frames()
@@ -781,8 +787,8 @@ class FaceService:
                     out = eng.fetch_results()
                     qual = self._stream_quality(eng, frames_bgr, out) if quality else None
             else:
-                if isinstance(frames_bgr, JpegBatch):
-                    frames_bgr = frames_bgr.decode()                   # an engine without the device decoder (tests' FakeEngine)
+                if isinstance(frames_bgr, _SOURCE_BATCHES):
+                    frames_bgr = frames_bgr.decode()                   # an engine without the device decoder / converter (tests' FakeEngine)
                 with (self._sequence_of(eng) if quality else contextlib.nullcontext()):
                     out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
                     qual = self._stream_quality(eng, frames_bgr, out) if quality else None
@@ -853,8 +859,8 @@ class FaceService:
 
     def _stream_quality(self, eng, frames_bgr, out) -> List[Dict[str, Any]]:
         """quality dicts of a fetched batch's faces, frame by frame (the order of the face dicts), from the frames still resident on `eng`"""
-        frames = frames_bgr if isinstance(frames_bgr, JpegBatch) or frames_bgr.ndim == 4 else frames_bgr[None]
-        H, W = frames.hw if isinstance(frames, JpegBatch) else frames.shape[1:3]
+        frames = frames_bgr if isinstance(frames_bgr, _SOURCE_BATCHES) or frames_bgr.ndim == 4 else frames_bgr[None]
+        H, W = frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[1:3]
         K = out["boxes"].shape[1]
         faces = [(b, box_to_location(out["boxes"][b, k], H, W)) for b, c in enumerate(out["counts"]) for k in range(min(int(c), K))]
         return self._quality_of(eng, frames, faces, rgb=False)
@@ -863,7 +869,13 @@ class FaceService:
     def _stage_on(eng, batch) -> None:
         """start moving a batch into the lane's staging frame buffer: pixel arrays by DMA, encoded batches (mjpeg.JpegBatch)
         through the engine's JPEG path - bit streams decoded here on host threads, pixels produced on the copy stream -
-        unless the device decoder does not cover the batch (progressive frames, mixed sampling): then PIL decodes it"""
+        unless the device decoder does not cover the batch (progressive frames, mixed sampling): then PIL decodes it; decoded
+        YUV 4:2:0 surfaces (yuv.YuvBatch) through the engine's converter where it has one, else converted here"""
+        if isinstance(batch, YuvBatch):
+            if hasattr(eng, "upload_yuv_async"):
+                eng.upload_yuv_async(batch)
+                return
+            batch = batch.decode()
         if isinstance(batch, JpegBatch):
             from . import ingest
             jp = ingest.device_jpeg_batch(batch, len(batch), batch.hw)

@@ -13,7 +13,9 @@ same memory is the source of the asynchronous H2D copy on the engine's copy stre
 host copy (decoder buffer -> pinned; PIL cannot decode into caller memory), no runtime bounce, and - two staging
 buffers - the decode + upload of batch t+1 runs while the GPU processes batch t.
 
-Video (RTSP / H.264) ingest is NOT covered: the image has no codec library or hardware-decode API.
+Video DECODE (RTSP / H.264) is NOT covered: no codec library or hardware-decode API ships with the package.  What a decoder
+emits is: 8-bit YUV 4:2:0 surfaces (NV12 / I420, with pitches, in host or device memory) go in through yuv.YuvBatch and
+Engine.upload_yuv_async, converted to BGR on the device - "bring your own decoder" needs nothing further.
 """
 from __future__ import annotations
 

@@ -27,6 +27,9 @@ MAX_TOPK = 64
 FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN = 1, 2, 4, 8
 F32, F16, F64 = 0, 1, 2
 JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}      # include/frp.h: FRP_JPEG_420, FRP_JPEG_444
+YUV_LAYOUTS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3}      # include/frp.h: FRP_YUV_NV12 ... (plane order: frp_upload_yuv)
+YUV_MATRICES = {"BT601": 0, "BT709": 1, "JFIF": 2}             # FRP_YUV_BT601, FRP_YUV_BT709, FRP_YUV_JFIF
+YUV_DEVICE = 1                                                  # frp_yuv_desc.flags: FRP_YUV_DEVICE
 QUALITY_TILE_H, QUALITY_TILE_W = 32, 64      # csrc/frp_internal.h: one workgroup of the face-quality kernel covers this much of a crop
 
 ABI_SYMBOLS = [
@@ -38,6 +41,7 @@ ABI_SYMBOLS = [
     "frp_gallery_size", "frp_gallery_get", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact",
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
+    "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
     "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
@@ -69,6 +73,12 @@ class JpegInfo(C.Structure):
     def as_dict(self) -> dict:
         return {"width": self.width, "height": self.height, "components": self.components, "h_samp": list(self.h_samp),
                 "v_samp": list(self.v_samp), "mcus_x": self.mcus_x, "mcus_y": self.mcus_y, "restart_interval": self.restart_interval}
+
+
+class FrpYuvDesc(C.Structure):
+    """include/frp.h: frp_yuv_desc"""
+    _fields_ = [("struct_size", C.c_int32), ("layout", C.c_int32), ("matrix", C.c_int32), ("flags", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("y_pitch", C.c_int64), ("c_pitch", C.c_int64)]
 
 
 def _byte_ptr(data):
@@ -197,6 +207,10 @@ def load_library() -> C.CDLL:
     lib.frp_host_free.restype = None
     lib.frp_upload_frames_async.argtypes = [vp, vp, i32, i32, i32, i64]
     lib.frp_swap_frames.argtypes = [vp]
+    if hasattr(lib, "frp_upload_yuv"):       # (as frp_match_within below: an older A/B partner build has none)
+        lib.frp_upload_yuv.argtypes = [vp, C.POINTER(FrpYuvDesc), vp, i32]
+        lib.frp_upload_yuv_async.argtypes = [vp, C.POINTER(FrpYuvDesc), vp, i32]
+        lib.frp_get_frames.argtypes = [vp, vp, i64, i32, i32]
     lib.frp_detect.argtypes = [vp, vp, i32, i32, i32, i64, i32, f32, f32, u32, vp, vp, vp, vp, vp]
     lib.frp_detect_resident.argtypes = [vp, i32, i32, i32, i32, f32, f32, u32, vp, vp, vp, vp, vp]
     lib.frp_get_det_source.argtypes = [vp, vp, i64, C.POINTER(i32), C.POINTER(i32)]
@@ -528,6 +542,40 @@ class Engine:
     def swap_frames(self):
         self._chk(self._lib.frp_swap_frames(self._h))
         self._resident = self._staged
+
+    def _yuv(self, fn, batch):
+        """one frp_upload_yuv* call for a yuv.YuvBatch (anything with its layout / matrix / hw / plane_table())
+        -> ((B, H, W), what keeps the host planes alive)"""
+        device, y_pitch, c_pitch, table, keep = batch.plane_table()
+        B = len(table)
+        d = FrpYuvDesc(C.sizeof(FrpYuvDesc), YUV_LAYOUTS.get(batch.layout, -1), YUV_MATRICES.get(batch.matrix, -1), YUV_DEVICE if device else 0,
+                       int(batch.hw[1]), int(batch.hw[0]), int(y_pitch), int(c_pitch))
+        ptrs = (C.c_void_p * (3 * B))(*[a or None for frame in table for a in frame])
+        self._chk(fn(self._h, C.byref(d), ptrs, B))
+        return (B, int(batch.hw[0]), int(batch.hw[1])), keep
+
+    def upload_yuv(self, batch):
+        """a yuv.YuvBatch of decoder surfaces (NV12 / NV21 / I420 / YV12, host arrays or device addresses) -> resident BGR frames,
+        converted on the device (frp.h: frp_upload_yuv); blocking, as upload_frames(): the surfaces have been read on return"""
+        self._resident, _ = self._yuv(self._lib.frp_upload_yuv, batch)
+
+    def upload_yuv_async(self, batch):
+        """the same into the staging frame buffer, on the copy stream: follow with swap_frames() as after upload_frames_async().
+        The call only QUEUES the copies and the kernel: the surfaces, host arrays and device memory alike, must stay untouched
+        until swap_frames() AND a call that waits for the pass (fetch_results, synchronize) have returned (frp.h).  The engine
+        holds a reference to the host arrays of the last two staged batches - the library has finished with a batch when the
+        second call after it returns - so that dropping a batch does not free memory under a running copy; it cannot keep a
+        caller from REWRITING them."""
+        self._staged, keep = self._yuv(self._lib.frp_upload_yuv_async, batch)
+        self._yuv_keep = (getattr(self, "_yuv_keep", ()) + (keep,))[-2:]
+
+    def get_frames(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """the resident BGR frames as they lie -> u8 [n, H, W, 3] (frp.h: frp_get_frames; parity tests, snapshots)"""
+        B, H, W = getattr(self, "_resident", (0, 0, 0))
+        n = B - first if n is None else n
+        out = np.empty((max(n, 0), H, W, 3), np.uint8)
+        self._chk(self._lib.frp_get_frames(self._h, _ptr(out), out.nbytes, first, n))
+        return out
 
     def process_resident(self, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4, flags: int = 0):
         self._chk(self._lib.frp_process_resident(self._h, max_faces, det_thresh, nms_iou, flags))

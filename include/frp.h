@@ -247,6 +247,56 @@ int64_t frp_debug_jpeg_selfsync_batches(frp_handle* h);
 int frp_jpeg_selfsync_coefficients(frp_handle* h, const uint8_t* const* jpegs, const size_t* sizes, int32_t B, int32_t subseq_bytes, int16_t* coef,
                                    int64_t coef_elems, int32_t* stats);
 
+/* ---- decoded video surfaces ----------------------------------------------
+ * replaces: the frames cv2.VideoCapture hands out for "device ID, RTSP URL, or HTTP stream" sources (routes/camera.py:52), for callers
+ * that bring their own decoder.  The library ships no codec; every decoder (a hardware video block, VA-API, ffmpeg in software) emits
+ * 8-bit YUV 4:2:0 surfaces with row pitches, and these calls take them - from host memory at 1.5 bytes per pixel over PCIe instead of
+ * the 3 of BGR, or where they already lie in device memory - and convert them on the GPU into the BGR frames the pipeline keeps
+ * resident.
+ * A frame is a Y plane [height][width] plus chroma at half resolution in both directions; width and height must be even.  Chroma is
+ * REPLICATED: pixel (x, y) uses the sample at (x >> 1, y >> 1), no siting filter.  Exact integer arithmetic; with u = U - 128,
+ * v = V - 128, >> an arithmetic shift and clamp to 0 .. 255:
+ *   FRP_YUV_BT601 / FRP_YUV_BT709 (limited "video" range):   y = max(0, Y - 16) * CY
+ *       R = clamp((y + CVR * v + 2^19) >> 20)   G = clamp((y - CVG * v - CUG * u + 2^19) >> 20)   B = clamp((y + CUB * u + 2^19) >> 20)
+ *       the constants are round(c * 2^20) of the usual three-decimal coefficients -
+ *       601: CY 1220542 (1.164), CVR 1673527 (1.596), CVG 852492 (0.813), CUG 409993 (0.391), CUB 2116026 (2.018)
+ *       709: CY 1220542,         CVR 1880097 (1.793), CVG 558891 (0.533), CUG 223347 (0.213), CUB 2214593 (2.112)
+ *   FRP_YUV_JFIF (full range, libjpeg's rule - what the JPEG ingest applies):
+ *       R = clamp(Y + ((91881 * v + 32768) >> 16))   G = clamp(Y + ((-22554 * u - 46802 * v + 32768) >> 16))
+ *       B = clamp(Y + ((116130 * u + 32768) >> 16))
+ * These formulas are the contract.  The 601 constants are believed to be OpenCV's (COLOR_YUV2BGR_NV12); parity with cv2 is neither
+ * claimed nor tested. */
+#define FRP_YUV_NV12 0       /* Y plane, then one plane of interleaved U,V */
+#define FRP_YUV_NV21 1       /* Y plane, then one plane of interleaved V,U */
+#define FRP_YUV_I420 2       /* Y, U, V planes */
+#define FRP_YUV_YV12 3       /* Y, V, U planes */
+#define FRP_YUV_BT601 0
+#define FRP_YUV_BT709 1
+#define FRP_YUV_JFIF 2
+#define FRP_YUV_DEVICE 1     /* frp_yuv_desc.flags: the plane pointers are device memory of the handle's GPU */
+typedef struct frp_yuv_desc {
+    int32_t struct_size, layout, matrix, flags;   /* sizeof(frp_yuv_desc), FRP_YUV_NV12 ..., FRP_YUV_BT601 ..., 0 or FRP_YUV_DEVICE */
+    int32_t width, height;                         /* even, width * height <= 2^30 */
+    int64_t y_pitch, c_pitch;                      /* bytes per row of the Y plane / of each chroma plane (NV12 / NV21: of the UV plane) */
+} frp_yuv_desc;
+/* planes: [B][3] pointers per frame, the planes in the order the layout names them - Y, U, V for FRP_YUV_I420; Y, V, U for
+ * FRP_YUV_YV12; Y, the interleaved plane, NULL for NV12 / NV21.  Frames may lie anywhere: there is no frame stride.  1 <= B <= 1024.
+ * A bad argument is FRP_ERR_INVALID with a message that names the field; nothing is queued then and a staged batch stays staged.
+ * Host sources (pageable or page-locked; only page-locked memory overlaps with compute) are copied plane by plane into a packed device
+ * buffer; device sources are read in place through their pitches.
+ * LIFETIME of the surfaces, host and device alike: complete before the call.  The blocking call has read them when it returns.  The
+ * staged call only QUEUES its copies and its kernel on the copy stream and returns at once: the surfaces must stay untouched - not
+ * refilled by the decoder, not freed - until frp_swap_frames has been called AND a call that waits for the compute stream
+ * (frp_fetch_results, frp_synchronize) has returned - the pipeline's own order.
+ * frp_upload_yuv: blocking, on the compute stream, the batch is resident on return (as frp_upload_frames).  frp_upload_yuv_async: staged
+ * on the copy stream (as frp_upload_frames_async): follow with frp_swap_frames. */
+int frp_upload_yuv(frp_handle* h, const frp_yuv_desc* desc, const uint8_t* const* planes, int32_t B);
+int frp_upload_yuv_async(frp_handle* h, const frp_yuv_desc* desc, const uint8_t* const* planes, int32_t B);
+/* the resident BGR frames as they lie, frames [first, first + n) of the batch -> out (n * H * W * 3 bytes; parity tests, snapshots).
+ * Waits for the compute stream; needs no weights.  FRP_ERR_INVALID when nothing is resident, when the range is empty or outside the
+ * batch, or when out_bytes is too small. */
+int frp_get_frames(frp_handle* h, uint8_t* out, int64_t out_bytes, int32_t first, int32_t n);
+
 /* ---- multi-GPU: one process per GPU, ONE collective ----------------------------------------------------
  * Frames are sharded one stream per GPU and never exchanged.  The watch list is: every rank builds (decrypts) rows
  * [rank * ceil(N / R), ...) and the unit fp16 matrix is all-gathered over RCCL / xGMI straight into a reserved snapshot of

@@ -51,6 +51,32 @@ struct Ingest {   // frame ingest (ingest_api.cpp: nothing else reads or writes 
     bool yuv_pending[2] = {false, false};
 };
 
+// The matcher's host half (match_api.cpp).  Other readers: fetch_results (frp_api.cpp) copies best_idx / best_cos of the pass out,
+// the pipeline refuses a flagged pass while within_cap is 0, frp_destroy releases the buffers.
+struct Matcher {
+    frp::DevBuf q16;                                     // [round_up(n, 32), 512] unit fp16 queries, zero padded (stage_queries)
+    frp::DevBuf part_cos, part_idx, best_cos, best_idx;  // per-workgroup partial and final top-1 (fill_match_params)
+    // radius match (frp_set_within, FRP_FLAG_WITHIN): bound and list size for the flagged passes to come; the lists of the last one
+    float within_min_cos = 0.f;
+    int within_cap = 0;                                  // 0: frp_set_within has not been called
+    frp::DevBuf hit_cnt, hit_idx, hit_cos;               // [n], [n x cap], [n x cap] per compact face of the last flagged pass
+};
+
+// Everything that describes the last pass, i.e. what the handle's result buffers hold.  Started as a whole where a pass begins
+// (run_faces; the detect-only entry points), never field by field: a new pass cannot inherit a flag of the one before.
+struct Pass {
+    int B = 0, K = 0;            // shape of the result slots
+    int nfaces = 0;              // faces of the pass; -1: the count is still on the device (settle_count)
+    int cap = 0;                 // the most faces it can hold: the count where the host knew it at the start, else B x K
+    bool matched = false;        // best_idx / best_cos hold its top-1
+    int within_cap = 0;          // list size of the pass, 0: it ran without FRP_FLAG_WITHIN
+    bool within_lists = false;   // ... and it matched (faces and a gallery): hit_* hold its lists
+    bool q16_of_pass = false;    // q16 still holds its queries (a list that overflowed is rebuilt from them at fetch time)
+    // device-count pass: the embedder's FLOPs were charged for pend_cap faces, corrected once the count is known (settle_count)
+    int pend_cap = 0;
+    double pend_flops = 0.0, pend_f8flops = 0.0;
+};
+
 struct frp_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -85,24 +111,15 @@ struct frp_handle {
     frp::DevBuf det_hashes;               // frp_debug_det_hashes: one 64-bit hash per detector op, taken right behind the op
     bool det_hash_on = false;
     // per-call results (device)
-    frp::DevBuf boxes, kps, scores, counts, anchor, face_slot, nfaces, q16, part_cos, part_idx, best_cos, best_idx, scratch, splitk_ws, dense_logits;
-    int last_B = 0, last_K = 0, last_nfaces = 0;   // last_nfaces -1: count still on the device (resolve_count)
-    int last_cap = 0, pend_cap = 0;
-    double pend_flops = 0.0, pend_f8flops = 0.0;
+    frp::DevBuf boxes, kps, scores, counts, anchor, face_slot, nfaces, scratch, splitk_ws, dense_logits;
+    Matcher m;                 // queries, work buffers and hit lists of the matcher
+    Pass pass;                 // what the buffers above hold: the last pass
     bool ev_pending = false;   // frp_process_resident's stage events are recorded but not yet read (see settle_events)
-    bool last_matched = false;
-    // radius match (frp_set_within, FRP_FLAG_WITHIN): bound and list size for the flagged passes to come; the lists of the last one
-    float within_min_cos = 0.f;
-    int within_cap = 0;               // 0: frp_set_within has not been called
-    frp::DevBuf hit_cnt, hit_idx, hit_cos;   // [n], [n x cap], [n x cap] per compact face of the last flagged pass
-    int last_within_cap = 0;          // list size of the last pass, 0: it ran without FRP_FLAG_WITHIN
-    bool last_within_lists = false;   // ... and it matched (faces and a gallery): the buffers above hold its lists
-    bool q16_of_pass = false;         // q16 still holds that pass's queries (a list that overflowed is rebuilt from them at fetch time)
     // frp_face_quality: rectangles + tile prefix in, per-tile partials + per-rectangle sums out (its own: the last pass's results stay)
     frp::DevBuf quality_in, quality_out;
     // frp_encode_jpeg: rectangles + tables in, quantised coefficients, the scans' work arrays, the unstuffed bit stream, the files (its own)
     frp::DevBuf jenc_in, jenc_coef, jenc_work, jenc_bits, jenc_out;
-    int32_t* h_nfaces = nullptr;   // pinned
+    int32_t* h_nfaces = nullptr;   // pinned: the face count of a device-count pass, copied behind it (read by settle_count alone)
     unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
     size_t pin_cap = 0;
     // gallery snapshot
@@ -180,8 +197,19 @@ public:
     DevBuf take() { return std::exchange(b, DevBuf()); }
 };
 
-// What the files of entry points share (frp_api.cpp, ingest_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp, jpeg_encode_api.cpp)
+// What the files of entry points share (frp_api.cpp, match_api.cpp, ingest_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp,
+// jpeg_encode_api.cpp)
 FRP_LOCAL void settle_events(frp_handle* h, bool stream_is_idle);   // frp_api.cpp
+// frp_api.cpp: the pending face count of a device-count pass - waits for the stream unless it is idle, reads the count, corrects the
+// counters.  Called by whatever reuses or discards the pass's slots (h_nfaces, Pass) or needs its count; a no-op otherwise.
+FRP_LOCAL int settle_count(frp_handle* h, bool stream_is_idle);
+FRP_LOCAL int ensure_pinned(frp_handle* h, size_t bytes);           // frp_api.cpp: h->pin_stage, the page-locked staging of the fetches
+// match_api.cpp: q16 holds n zero-padded queries behind this - unit rows made of `rows` (host fp32), the fp16 bits `f16` (host) as they
+// are, or, with neither, whatever the caller launches next (run_embed: the l2norm); the last pass's queries are gone
+FRP_LOCAL int stage_queries(frp_handle* h, int n, const float* rows = nullptr, const void* f16 = nullptr);
+// match_api.cpp: the match of a pass (run_faces) - top-1 of the n queries in q16 (n_dev: the count in device memory) and, `within`,
+// the hit lists of frp_set_within in the same launch; marks the pass as matched
+FRP_LOCAL int match_pass(frp_handle* h, const frp::Switches& sw, int n, const int32_t* n_dev, bool within);
 inline void rec(frp_handle* h, int which) { if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream); }   // a stage event (timers on)
 FRP_LOCAL bool init_ingest(frp_handle* h);                          // ingest_api.cpp: the copy stream and its events (frp_create)
 FRP_LOCAL void release_ingest(frp_handle* h);                       // ... and everything `in` holds (frp_destroy)

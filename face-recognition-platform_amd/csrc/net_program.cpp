@@ -399,7 +399,7 @@ int plan_net(frp_handle* h, Net& net, int batch, int H, int W, bool skip_input) 
 // ---------------------------------------------------------------- the pass
 namespace {
 
-struct Pass {       // what run_net was asked for
+struct NetPass {       // what run_net was asked for
     frp_handle* h;
     const Switches& sw;
     Net& net;
@@ -421,7 +421,7 @@ int launched(frp_handle* h, hipError_t e, const char* what) {
 
 // The detector's stem(s) straight from the u8 frames.  Both in one kernel (the stem1 map never reaches HBM); FRP_NO_FUSED_STEM12 keeps
 // stem1 (fused with the u8 normalisation) and stem2 (generic conv) apart for A/B runs.  `next`: the first op left to the walk.
-int run_det_stems(const Pass& ps, PassEffects& fx, size_t& next) {
+int run_det_stems(const NetPass& ps, PassEffects& fx, size_t& next) {
     frp_handle* h = ps.h;
     const Net& net = ps.net;
     const StemParams& st = *ps.stem;
@@ -462,7 +462,7 @@ int run_det_stems(const Pass& ps, PassEffects& fx, size_t& next) {
 
 // The embedder's stem on its dedicated kernel (FRP_NO_EMB_STEM keeps the generic one) - or, where the conv behind it takes it into its
 // own launch, its parameters for that launch (`fused`; FRP_NO_STEM_FUSE: the two launches, for A/B runs; the results are the same bits)
-int run_emb_stem(const Pass& ps, PassEffects& fx, size_t& next, FusedStem& fused) {
+int run_emb_stem(const NetPass& ps, PassEffects& fx, size_t& next, FusedStem& fused) {
     const Net& net = ps.net;
     if (!net.emb_stem || ps.sw.no_emb_stem) return FRP_OK;
     const frp_conv_op& a = net.ops[0];
@@ -489,7 +489,7 @@ int run_emb_stem(const Pass& ps, PassEffects& fx, size_t& next, FusedStem& fused
 }
 
 // the launch parameters of op `i` reading a tensor of dims `in` (`d`: the pass's dims table, for the residual)
-ConvParams conv_params_for(const Pass& ps, size_t i, const TensorDims& in, const std::vector<TensorDims>& d, const FusedStem& fused) {
+ConvParams conv_params_for(const NetPass& ps, size_t i, const TensorDims& in, const std::vector<TensorDims>& d, const FusedStem& fused) {
     const Net& net = ps.net;
     const frp_conv_op& op = net.ops[i];
     const char* wbase = ps.weights();
@@ -552,7 +552,7 @@ ConvParams conv_params_for(const Pass& ps, size_t i, const TensorDims& in, const
 }
 
 // skinny fp32-output GEMM (the FC): split K over the CUs; the slabs are reduced (+bias) by the l2norm kernel that follows
-void pick_fc_splitk(const Pass& ps, const frp_conv_op& op, const TensorDims& in, const TensorDims& out, ConvParams& p, FcSplitK& fc) {
+void pick_fc_splitk(const NetPass& ps, const frp_conv_op& op, const TensorDims& in, const TensorDims& out, ConvParams& p, FcSplitK& fc) {
     frp_handle* h = ps.h;
     // device-side count: the kernel picks the factor of the real batch itself (the same function), the slabs are
     // sized for the largest one - that of a single image - times the capacity
@@ -577,7 +577,7 @@ void charge(const frp_conv_op& op, const TensorDims& out, int batch, PassEffects
 }
 
 // One pass, launch by launch, into `fx` (nothing else on the handle or the net is written, but for the split-K workspace).
-int walk(const Pass& ps, PassEffects& fx) {
+int walk(const NetPass& ps, PassEffects& fx) {
     frp_handle* h = ps.h;
     const Net& net = ps.net;
     fx = PassEffects();
@@ -614,7 +614,7 @@ int walk(const Pass& ps, PassEffects& fx) {
 
 // The key of a pass in the graph cache: everything the launches depend on that is not fixed by the loaded weights - program, shapes,
 // family, operand pointers, the bytes of the switch snapshot; device buffers and weights are covered by the allocation epoch.  Empty: none
-std::string graph_key(const Pass& ps) {
+std::string graph_key(const NetPass& ps) {
     char kb[512];
     int len = snprintf(kb, sizeof kb, "%c|%d|%d|%d|%d|%p|%p|", ps.net.is_det ? 'd' : 'e', ps.batch, ps.H, ps.W, (int)ps.allow_wino, (const void*)ps.n_dev,
                        (const void*)ps.h->wdata.p);
@@ -627,7 +627,7 @@ std::string graph_key(const Pass& ps) {
 
 // The pass, replayed from its captured graph when it has been asked for before (FRP_NO_GRAPH: always launch by launch).  Not with the
 // detector diagnostics (they are not captured).  Either way `fx` holds the effects of exactly one pass.
-int launch_or_replay(const Pass& ps, PassEffects& fx) {
+int launch_or_replay(const NetPass& ps, PassEffects& fx) {
     frp_handle* h = ps.h;
     if (process_switches().no_graph || h->det_hash_on || h->det_op_limit >= 0) return walk(ps, fx);
     const std::string key = graph_key(ps);
@@ -694,7 +694,7 @@ int launch_or_replay(const Pass& ps, PassEffects& fx) {
 
 int run_net(frp_handle* h, const Switches& sw, Net& net, int batch, int H, int W, double* flops, int64_t* launches, const StemParams* stem,
             const int32_t* n_dev, bool allow_wino, FcSplitK* fc) {
-    const Pass ps{h, sw, net, batch, H, W, stem, n_dev, allow_wino};
+    const NetPass ps{h, sw, net, batch, H, W, stem, n_dev, allow_wino};
     PassEffects fx;
     FRPCHK(launch_or_replay(ps, fx));
     // the one place where a pass - launched, captured or replayed - leaves its mark on the host side

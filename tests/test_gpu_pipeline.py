@@ -311,6 +311,101 @@ def test_threshold_mode_face_count_stays_on_the_device(engine, monkeypatch):
         assert np.array_equal(a[key], b[key])
 
 
+def _small_resident_batch(eng):
+    """The small nets, a gallery of 300 random rows and B = 3 resident frames of 128 x 160 for K = 6 (18 slots: a threshold pass
+    keeps its face count on the device).  Seed 93 was chosen with oracle/network.py on the CPU: its decode_nms keeps 6 + 6 + 6 faces
+    at 0.3 - every frame has over 60 candidates - and 0 + 6 + 6 at 0.5, where frame 0 has no candidate at all."""
+    rng = np.random.default_rng(93)
+    frames = _frames(rng, 3, 128, 160)
+    _, blob = get_raw_and_blob((1, 2, 2, 2), (1, 1, 1, 1))
+    eng.load_weights(blob)
+    eng.gallery_set(rng.standard_normal((300, 512)).astype(np.float32))
+    eng.upload_frames(frames)
+    return 6
+
+
+_RESULT_KEYS = ("counts", "boxes", "kps", "scores", "emb", "match_idx", "match_cos")
+
+
+def _lone_threshold_pass(eng, K, thr):
+    """one fetched threshold pass on the resident frames -> (results, faces, embedder FLOPs) by the counters"""
+    eng.reset_counters()
+    eng.process_resident(max_faces=K, det_thresh=thr)
+    res = eng.fetch_results()
+    ctr = eng.counters()
+    assert ctr["faces"] == int(res["counts"].sum())
+    return res, ctr["faces"], ctr["emb_conv_flops"]
+
+
+def test_queued_threshold_passes_settle_each_other(engine):
+    """Two threshold passes queued with nothing between them: the second settles the first one's face count, which is still on
+    the device, before it reuses the count's slots.  The fetch gives the second pass alone, the counters hold both."""
+    K = _small_resident_batch(engine)
+    _, n3, f3 = _lone_threshold_pass(engine, K, 0.3)
+    want, n5, f5 = _lone_threshold_pass(engine, K, 0.5)
+    assert n3 != n5 and n3 + n5 > 0
+    engine.reset_counters()
+    engine.process_resident(max_faces=K, det_thresh=0.3)
+    engine.process_resident(max_faces=K, det_thresh=0.5)
+    got = engine.fetch_results()
+    for key in _RESULT_KEYS:
+        assert np.array_equal(got[key], want[key]), key
+    ctr = engine.counters()
+    assert ctr["faces"] == n3 + n5
+    assert abs(ctr["emb_conv_flops"] - (f3 + f5)) <= 1e-9 * (f3 + f5)      # (the same double arithmetic in another order)
+
+
+def test_overflowed_hit_list_is_not_rebuilt_from_replaced_queries(fresh_engine):
+    """A hit list that overflowed is rebuilt at fetch time from the queries the pass left on the device: refused once a later
+    match has replaced them, equal to the top-k of the fetched embeddings otherwise.  Rows and hit counts equal match(emb, topk).
+    The cosines are compared bit for bit with the matcher's score rows of the pass's own queries: the l2norm stores a unit
+    embedding e as fp32 and fp16(e) as the query, so emb.astype(float16) is that query, match_f16 takes it without normalising, and
+    a host top-k by (cosine desc, row asc) over its score matrix is the list.  (match() divides the fetched e by |e| = 1 +- a few
+    ulps first, which moves single fp16 roundings: its cosines agree only to about 1e-7.)"""
+    from frp_amd import native
+    engine = fresh_engine
+    K, cap = _small_resident_batch(engine), 4
+    engine.set_within(-2.0, cap)                                            # every gallery row is a hit: every face overflows
+    flags = native.FLAG_FORCED_K | native.FLAG_WITHIN
+    engine.process_resident(max_faces=K, flags=flags)
+    emb = engine.fetch_results()["emb"]
+    engine.match(emb[0, :1])
+    with pytest.raises(native.FrpError, match="replaced the pass's embeddings"):
+        engine.fetch_within()
+    engine.process_resident(max_faces=K, flags=flags)                       # a new pass after the refusal fetches normally
+    idx, cos, n = engine.fetch_within()
+    emb = engine.fetch_results()["emb"].reshape(-1, 512)
+    idx, cos = idx.reshape(-1, cap), cos.reshape(-1, cap)
+    assert np.all(n == 300)
+    assert np.array_equal(idx, engine.match(emb, topk=cap)[0])
+    S = engine.match_f16(emb.astype(np.float16), scores=True)[2]
+    want_idx = np.stack([np.lexsort((np.arange(300), -row))[:cap] for row in S]).astype(np.int32)
+    assert np.array_equal(idx, want_idx)
+    assert np.array_equal(cos.view(np.uint32), np.take_along_axis(S, want_idx, axis=1).view(np.uint32))
+    # a detect-only call begins a pass of its own: it has no lists, whatever the pass before it was flagged with
+    engine.detect_resident((128, 160), max_faces=K)
+    with pytest.raises(native.FrpError, match="without FRP_FLAG_WITHIN"):
+        engine.fetch_within()
+
+
+@pytest.mark.parametrize("thr", [0.3, 0.5])
+def test_discarded_pending_pass_still_reaches_the_counters(engine, thr):
+    """A threshold pass that is queued and never fetched, then discarded by a detect-only call: its faces and the FLOPs of its real
+    face count reach the counters all the same.  (Before the pending count was settled by every entry point that discards a pass,
+    this sequence showed faces == 0 and the embedder's FLOPs of the capacity B x K.)  At 0.3 every slot holds a face, so only the
+    face count tells; at 0.5 frame 0 is empty and the FLOPs of 12 faces differ from those of the 18 slots."""
+    K = _small_resident_batch(engine)
+    _, n, f = _lone_threshold_pass(engine, K, thr)
+    assert n > 0
+    engine.reset_counters()
+    engine.process_resident(max_faces=K, det_thresh=thr)
+    engine.detect_resident((128, 160), max_faces=K)
+    engine.synchronize()
+    ctr = engine.counters()
+    assert ctr["faces"] == n
+    assert abs(ctr["emb_conv_flops"] - f) <= 1e-9 * f
+
+
 def test_forced_k_and_resident_path(engine):
     rng = np.random.default_rng(77)
     raw, blob = get_raw_and_blob((1, 2, 2, 2), (1, 1, 1, 1))

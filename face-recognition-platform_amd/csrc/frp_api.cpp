@@ -53,10 +53,12 @@ float logit_threshold(float t) {
     return (float)std::log((double)t / (1.0 - (double)t));
 }
 
+bool det_size_ok(int Hs, int Ws) { return Hs > 0 && Ws > 0 && Hs <= 16384 && Ws <= 16384; }
+
 // choose the detector source: the resident frames (Hs,Ws == frame size) or a bilinear resize of them
 int select_det_source(frp_handle* h, int Hs, int Ws) {
     if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "no resident frames (call frp_upload_frames)");
-    if (Hs <= 0 || Ws <= 0 || Hs > 16384 || Ws > 16384) return fail(h, FRP_ERR_INVALID, "bad detector size");
+    if (!det_size_ok(Hs, Ws)) return fail(h, FRP_ERR_INVALID, "bad detector size");
     if (Hs == h->rH && Ws == h->rW) {
         h->det_scaled = false;
     } else {
@@ -83,8 +85,16 @@ int ensure_results(frp_handle* h, int B, int K) {
     return FRP_OK;
 }
 
-// decode + NMS of B frames' head maps (dims[l] = {h, w}) into the result buffers (ensure_results).  Forced-K: no threshold, no suppression
-int run_decode(frp_handle* h, const void* const head[3], const int dims[3][2], int B, int K, float det_thresh, float nms_iou, uint32_t flags) {
+// where a decode writes its K slots per frame instead of the handle's result buffers (frp_process_pyramid: one scale's slice)
+struct DetOut {
+    float *boxes, *kps, *scores;
+    int32_t* counts;
+};
+
+// decode + NMS of B frames' head maps (dims[l] = {h, w}) into the result buffers (ensure_results), or into `out`.  Forced-K: no threshold,
+// no suppression
+int run_decode(frp_handle* h, const void* const head[3], const int dims[3][2], int B, int K, float det_thresh, float nms_iou, uint32_t flags,
+               const DetOut* out = nullptr) {
     DecodeParams dp{};
     size_t anchors = 0;
     for (int l = 0; l < 3; ++l) {
@@ -98,8 +108,12 @@ int run_decode(frp_handle* h, const void* const head[3], const int dims[3][2], i
     const bool forced = flags & FRP_FLAG_FORCED_K;
     dp.logit_thresh = forced ? -INFINITY : logit_threshold(det_thresh);
     dp.nms_iou = forced ? 2.0f : nms_iou;
-    dp.boxes = (float*)h->boxes.p; dp.kps = (float*)h->kps.p; dp.scores = (float*)h->scores.p;
-    dp.anchor = (int32_t*)h->anchor.p; dp.counts = (int32_t*)h->counts.p;
+    if (out) {
+        dp.boxes = out->boxes; dp.kps = out->kps; dp.scores = out->scores; dp.counts = out->counts;     // (no anchor indices)
+    } else {
+        dp.boxes = (float*)h->boxes.p; dp.kps = (float*)h->kps.p; dp.scores = (float*)h->scores.p;
+        dp.anchor = (int32_t*)h->anchor.p; dp.counts = (int32_t*)h->counts.p;
+    }
     FRPCHK(ensure(h, h->dense_logits, (size_t)B * anchors * 2));
     dp.logits = (_Float16*)h->dense_logits.p;
     const hipError_t e = launch_decode_nms(dp, h->stream);
@@ -131,8 +145,9 @@ bool det_wino(const frp_handle* h) {
     return (long)h->rB * (h->canvas_h / 8) * (h->canvas_w / 8) >= 2L * 240 * (h->n_cu > 0 ? h->n_cu : 256);
 }
 
-// detector, decode + NMS, compact face list of the resident frames; touches no Pass state: the caller begins the pass
-int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float nms_iou, uint32_t flags) {
+// detector, decode + NMS, compact face list of the resident frames; touches no Pass state: the caller begins the pass.
+// With `out` the detections go there and the result buffers, the compact face list included, stay as they are.
+int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float nms_iou, uint32_t flags, const DetOut* out = nullptr) {
     if (!h->have_weights) return fail(h, FRP_ERR_NO_WEIGHTS, "no weights loaded");
     if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "no resident frames (call frp_upload_frames)");
     if (K <= 0 || K > FRP_MAX_FACES_CAP) return fail(h, FRP_ERR_INVALID, "max_faces out of range");
@@ -142,7 +157,7 @@ int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float
     // two-kernel path (preprocess to an NHWC8 blob, then the generic conv) for A/B runs.
     const bool fused = h->det.det_stem && !sw.no_fused_stem;
     FRPCHK(plan_net(h, h->det, B, Hc, Wc, fused));
-    FRPCHK(ensure_results(h, B, K));
+    if (!out) FRPCHK(ensure_results(h, B, K));
     const StemParams sp = stem_params(h, flags);
     if (!fused) {
         hipError_t e = launch_preprocess(sp.frames, B, sp.H, sp.W, sp.row_stride, sp.frame_stride, (_Float16*)h->det.bufs[h->det.in_buf].p, Hc, Wc,
@@ -161,8 +176,8 @@ int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float
         dims[l][1] = h->det.dims[bi].w;
         if (h->det.dims[bi].c != 32) return fail(h, FRP_ERR_BLOB, "detector head must have 32 channels");
     }
-    FRPCHK(run_decode(h, head, dims, B, K, det_thresh, nms_iou, flags));
-    FRPCHK(compact_faces(h, B, K));
+    FRPCHK(run_decode(h, head, dims, B, K, det_thresh, nms_iou, flags, out));
+    if (!out) FRPCHK(compact_faces(h, B, K));
     rec(h, EV_DEC);
     return FRP_OK;
 }
@@ -284,6 +299,42 @@ int run_pipeline(frp_handle* h, int K, float det_thresh, float nms_iou, uint32_t
     FRPCHK(run_detect(h, sw, K, det_thresh, nms_iou, flags));
     const long A = (long)h->det.dims[h->hdr.det_head_buf[0]].h * h->det.dims[h->hdr.det_head_buf[0]].w * 2;
     return run_faces(h, sw, K, ((flags & FRP_FLAG_FORCED_K) && A >= K) ? h->rB * K : -1, flags);   // forced-K: count known
+}
+
+// The pyramid as one device pass (frp.h: frp_process_pyramid; arguments checked by the caller): per scale the detector source, the
+// detector and decode + NMS into the scale's slice of pyr_*, the cross-scale merge into the result buffers, then the faces from
+// the full-resolution frames with the count left on the device.  Stage events: every scale records EV_PRE / EV_DET / EV_DEC again
+// and the last record stands, so the earlier scales fall between EV_H2D and the last scale's EV_PRE (ms_preprocess).
+int run_pyramid(frp_handle* h, int S, const int32_t* det_hw, int P, int K, float det_thresh, float nms_iou, uint32_t flags) {
+    const Switches sw = read_switches();
+    const int B = h->rB;
+    const size_t sl = (size_t)B * P;      // slots of one scale
+    // every buffer the launches below point into has its final size before the first of them (ensure() moves what it grows)
+    FRPCHK(ensure_results(h, B, K));
+    FRPCHK(ensure(h, h->pyr_boxes, S * sl * 16));
+    FRPCHK(ensure(h, h->pyr_kps, S * sl * 40));
+    FRPCHK(ensure(h, h->pyr_scores, S * sl * 4));
+    FRPCHK(ensure(h, h->pyr_counts, (size_t)S * B * 4));
+    PyramidMergeParams mp{};
+    for (int s = 0; s < S; ++s) {
+        mp.det_h[s] = det_hw[2 * s]; mp.det_w[s] = det_hw[2 * s + 1];
+        FRPCHK(select_det_source(h, mp.det_h[s], mp.det_w[s]));
+        const DetOut out{(float*)h->pyr_boxes.p + s * sl * 4, (float*)h->pyr_kps.p + s * sl * 10, (float*)h->pyr_scores.p + s * sl,
+                         (int32_t*)h->pyr_counts.p + (size_t)s * B};
+        FRPCHK(run_detect(h, sw, P, det_thresh, nms_iou, flags, &out));
+    }
+    mp.boxes = (const float*)h->pyr_boxes.p; mp.kps = (const float*)h->pyr_kps.p; mp.scores = (const float*)h->pyr_scores.p;
+    mp.counts = (const int32_t*)h->pyr_counts.p;
+    mp.S = S; mp.B = B; mp.P = P; mp.max_faces = K;
+    mp.frame_h = h->rH; mp.frame_w = h->rW;
+    mp.nms_iou = nms_iou;
+    mp.out_boxes = (float*)h->boxes.p; mp.out_kps = (float*)h->kps.p; mp.out_scores = (float*)h->scores.p;
+    mp.out_anchor = (int32_t*)h->anchor.p; mp.out_counts = (int32_t*)h->counts.p;
+    const hipError_t e = launch_pyramid_merge(mp, h->stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("pyramid_merge: ") + hipGetErrorString(e));
+    FRPCHK(compact_faces(h, B, K));
+    rec(h, EV_DEC);
+    return run_faces(h, sw, K, -1, flags);
 }
 
 // Stage timers (timers on): stage i runs from event i to event i + 1.  Adds the stages between two events and their span to the counters.
@@ -497,7 +548,7 @@ void frp_destroy(frp_handle* h) {
     for (DevBuf& b : h->det.bufs) release(b);
     for (DevBuf& b : h->emb.bufs) release(b);
     DevBuf* all[] = {&h->wdata, &h->frames, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
-                     &h->m.q16, &h->m.part_cos, &h->m.part_idx, &h->m.best_cos, &h->m.best_idx, &h->m.hit_cnt, &h->m.hit_idx, &h->m.hit_cos, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
+                     &h->pyr_boxes, &h->pyr_kps, &h->pyr_scores, &h->pyr_counts, &h->m.q16, &h->m.part_cos, &h->m.part_idx, &h->m.best_cos, &h->m.best_idx, &h->m.hit_cnt, &h->m.hit_idx, &h->m.hit_cos, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
                      &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->det_hashes, &h->quality_in, &h->quality_out,
                      &h->jenc_in, &h->jenc_coef, &h->jenc_work, &h->jenc_bits, &h->jenc_out};
     for (DevBuf* b : all) release(*b);
@@ -547,6 +598,29 @@ int frp_process_resident(frp_handle* h, int32_t max_faces, float det_thresh, flo
     Guard g(h);
     rec(h, EV_H2D);
     FRPCHK(run_pipeline(h, max_faces, det_thresh, nms_iou, flags));
+    h->ev_pending = h->cfg.profile != 0;
+    h->ctr.calls += 1;
+    return FRP_OK;
+}
+
+int frp_process_pyramid(frp_handle* h, int32_t n_scales, const int32_t* det_hw, int32_t per_scale, int32_t max_faces, float det_thresh,
+                        float nms_iou, uint32_t flags) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    FRPCHK(check_within_flag(h, flags));
+    if (!h->have_weights) return fail(h, FRP_ERR_INVALID, "process_pyramid: no weights loaded");
+    if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "process_pyramid: no resident frames (call frp_upload_frames)");
+    if (n_scales < 1 || n_scales > FRP_PYRAMID_MAX_SCALES || !det_hw) return fail(h, FRP_ERR_INVALID, "process_pyramid: 1 to 4 scales");
+    if (per_scale < 1 || per_scale > FRP_MAX_FACES_CAP) return fail(h, FRP_ERR_INVALID, "process_pyramid: per_scale out of range");
+    if (max_faces < 1 || max_faces > FRP_MAX_FACES_CAP) return fail(h, FRP_ERR_INVALID, "process_pyramid: max_faces out of range");
+    if (n_scales * per_scale > FRP_PYRAMID_MAX_CAND)
+        return fail(h, FRP_ERR_INVALID, "process_pyramid: more than 512 candidates per frame (n_scales x per_scale)");
+    for (int s = 0; s < n_scales; ++s)
+        if (!det_size_ok(det_hw[2 * s], det_hw[2 * s + 1])) return fail(h, FRP_ERR_INVALID, "process_pyramid: bad detector size");
+    if (flags & FRP_FLAG_FORCED_K)
+        return fail(h, FRP_ERR_INVALID, "process_pyramid: FRP_FLAG_FORCED_K has no meaning under a cross-scale merge");
+    rec(h, EV_H2D);
+    FRPCHK(run_pyramid(h, n_scales, det_hw, per_scale, max_faces, det_thresh, nms_iou, flags));
     h->ev_pending = h->cfg.profile != 0;
     h->ctr.calls += 1;
     return FRP_OK;

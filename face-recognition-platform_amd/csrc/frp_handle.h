@@ -112,6 +112,8 @@ struct frp_handle {
     bool det_hash_on = false;
     // per-call results (device)
     frp::DevBuf boxes, kps, scores, counts, anchor, face_slot, nfaces, scratch, splitk_ws, dense_logits;
+    // frp_process_pyramid: every scale's detections, scale-major [S][B][P]... (the merge kernel's input; the merged faces go to the buffers above)
+    frp::DevBuf pyr_boxes, pyr_kps, pyr_scores, pyr_counts;
     Matcher m;                 // queries, work buffers and hit lists of the matcher
     Pass pass;                 // what the buffers above hold: the last pass
     bool ev_pending = false;   // frp_process_resident's stage events are recorded but not yet read (see settle_events)

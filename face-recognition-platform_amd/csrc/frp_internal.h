@@ -220,6 +220,30 @@ struct DecodeParams {
 };
 hipError_t launch_decode_nms(const DecodeParams& p, hipStream_t stream);
 
+// K3b: cross-scale merge + NMS of the detection pyramid (pyramid_kernels.hip), one workgroup per frame: the detections K3 wrote per
+// scale, scale-major, -> K = max_faces slots per frame in frame pixels, bit for bit pyramid.merge_scales
+#define FRP_PYRAMID_MAX_SCALES 4
+#define FRP_PYRAMID_MAX_CAND 512   // S * P candidates per frame at the most: one thread and one sort slot each
+struct PyramidMergeParams {
+    const float* boxes;       // [S][B][P][4] in the coordinates of scale s's resized image
+    const float* kps;         // [S][B][P][10]
+    const float* scores;      // [S][B][P] finite, >= 0
+    const int32_t* counts;    // [S][B], each in [0, P]
+    int S, B, P, max_faces;
+    int frame_h, frame_w;
+    int det_h[FRP_PYRAMID_MAX_SCALES], det_w[FRP_PYRAMID_MAX_SCALES];   // size of scale s's resized image
+    float nms_iou;
+    float* out_boxes;         // [B, max_faces, 4] frame pixels; slots from the count on are zero
+    float* out_kps;           // [B, max_faces, 10]
+    float* out_scores;        // [B, max_faces]
+    int32_t* out_anchor;      // [B, max_faces] or null: -1 in every slot
+    int32_t* out_counts;      // [B]
+    // derived by launch_pyramid_merge():
+    float rx[FRP_PYRAMID_MAX_SCALES], ry[FRP_PYRAMID_MAX_SCALES];       // (float)frame_w / (float)det_w[s], (float)frame_h / (float)det_h[s]
+};
+// refuses (hipErrorInvalidValue) S outside 1..4, P or max_faces outside 1..FRP_MAX_FACES_CAP, S * P > FRP_PYRAMID_MAX_CAND
+hipError_t launch_pyramid_merge(PyramidMergeParams p, hipStream_t stream);
+
 // JPEG ingest, device half (jpeg_kernels.hip): quantised coefficients -> BGR frames
 struct JpegParams {
     const int16_t* coef;     // [B][blocks_per_image][64], natural order, quantised; per image the components back to back

@@ -1,5 +1,5 @@
 // The stand-alone kernel entry points of libfrp.so: one conv launch on host tensors (frp_conv2d_nhwc, frp_conv2d_f8: the parity
-// tests' way to a single kernel) and, in libfrp_lab.so only, the tuning hooks of include/frp_lab.h.
+// tests' way to a single kernel; frp_debug_pyramid_merge: the cross-scale merge on host detections) and, in libfrp_lab.so only, the tuning hooks of include/frp_lab.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -147,6 +147,63 @@ int frp_conv2d_f8(frp_handle* h, const void* x8, int32_t N, int32_t H, int32_t W
     hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go)
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("conv2d_f8: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv2d_f8 sync: ") + hipGetErrorString(e2));
+    return FRP_OK;
+}
+
+int frp_debug_pyramid_merge(frp_handle* h, int32_t n_scales, const int32_t* det_hw, int32_t B, int32_t per_scale, int32_t frame_h,
+                            int32_t frame_w, const float* boxes, const float* kps, const float* scores, const int32_t* counts,
+                            int32_t max_faces, float nms_iou, float* out_boxes, float* out_kps, float* out_scores, int32_t* out_counts) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!det_hw || !boxes || !kps || !scores || !counts || !out_boxes || !out_kps || !out_scores || !out_counts)
+        return fail(h, FRP_ERR_INVALID, "pyramid_merge: null argument");
+    if (n_scales < 1 || n_scales > FRP_PYRAMID_MAX_SCALES || per_scale < 1 || per_scale > FRP_MAX_FACES_CAP ||
+        n_scales * per_scale > FRP_PYRAMID_MAX_CAND || max_faces < 1 || max_faces > FRP_MAX_FACES_CAP || B < 1 || B > 1024 || frame_h < 1 ||
+        frame_w < 1)
+        return fail(h, FRP_ERR_INVALID, "pyramid_merge: 1..4 scales, per_scale and max_faces in 1..128, at most 512 candidates per frame");
+    const int S = n_scales, P = per_scale, K = max_faces;
+    PyramidMergeParams mp{};
+    for (int s = 0; s < S; ++s) {
+        mp.det_h[s] = det_hw[2 * s]; mp.det_w[s] = det_hw[2 * s + 1];
+        if (mp.det_h[s] < 1 || mp.det_w[s] < 1) return fail(h, FRP_ERR_INVALID, "pyramid_merge: bad detector size");
+        for (int b = 0; b < B; ++b) {
+            const int32_t n = counts[s * B + b];
+            if (n < 0 || n > P) return fail(h, FRP_ERR_INVALID, "pyramid_merge: count outside [0, per_scale]");
+            for (int j = 0; j < n; ++j) {
+                const float v = scores[((size_t)s * B + b) * P + j];
+                if (!std::isfinite(v) || v < 0.f) return fail(h, FRP_ERR_INVALID, "pyramid_merge: score of a live row not finite or below 0");
+            }
+        }
+    }
+    const size_t in = (size_t)S * B * P, on = (size_t)B * K;
+    ScopedBuf db, dk, ds, dc, ob, ok, os, oc;
+    FRPCHK(ensure(h, db, in * 16));
+    FRPCHK(ensure(h, dk, in * 40));
+    FRPCHK(ensure(h, ds, in * 4));
+    FRPCHK(ensure(h, dc, (size_t)S * B * 4));
+    FRPCHK(ensure(h, ob, on * 16));
+    FRPCHK(ensure(h, ok, on * 40));
+    FRPCHK(ensure(h, os, on * 4));
+    FRPCHK(ensure(h, oc, (size_t)B * 4));
+    hipError_t e = hipMemcpyAsync(db->p, boxes, in * 16, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dk->p, kps, in * 40, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ds->p, scores, in * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dc->p, counts, (size_t)S * B * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        mp.boxes = (const float*)db->p; mp.kps = (const float*)dk->p; mp.scores = (const float*)ds->p; mp.counts = (const int32_t*)dc->p;
+        mp.S = S; mp.B = B; mp.P = P; mp.max_faces = K;
+        mp.frame_h = frame_h; mp.frame_w = frame_w;
+        mp.nms_iou = nms_iou;
+        mp.out_boxes = (float*)ob->p; mp.out_kps = (float*)ok->p; mp.out_scores = (float*)os->p; mp.out_counts = (int32_t*)oc->p;
+        e = launch_pyramid_merge(mp, h->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_boxes, ob->p, on * 16, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_kps, ok->p, on * 40, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_scores, os->p, on * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_counts, oc->p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("pyramid_merge: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("pyramid_merge sync: ") + hipGetErrorString(e2));
     return FRP_OK;
 }
 

@@ -61,6 +61,7 @@ def cos_to_distance(cos) -> np.ndarray:
     return np.sqrt(np.maximum(0.0, 2.0 - 2.0 * np.asarray(cos, dtype=np.float64)))
 
 
+PYRAMID_PER_SCALE = 64     # det_scales: detections kept per frame and scale ahead of the cross-scale merge (Engine.process_frames_pyramid's default)
 WITHIN_CAP = 64            # hit-list slots per face of the device radius match (frp.h: FRP_MAX_TOPK)
 
 
@@ -727,7 +728,8 @@ class FaceService:
 
     # ------------------------------------------------------------------ streaming entry points (new)
     def process_frames(self, frames_bgr: np.ndarray, max_faces: int = 10, threshold: Optional[float] = None,
-                       det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False) -> List[List[Dict[str, Any]]]:
+                       det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
+                       det_scales: Optional[Sequence[float]] = None) -> List[List[Dict[str, Any]]]:
         """The live-loop body of routes/camera.py:225-259 for a batch of BGR frames, with the
         per-face compare + filter reduced to a fused device top-1: per frame a list of
         {bbox, kps, score, embedding, target, distance, cosine, confidence, match}.
@@ -735,18 +737,52 @@ class FaceService:
         tolerance and `threshold` (the reference's exact loop semantics, camera.py:246-256: a face
         can hit several near-duplicate identities), ascending by distance, under "matches".
         quality=True adds "quality" to every face: assess_face_quality (the reference's enrolment gate, routes/face.py:217) of the
-        frame at box_to_location(bbox), the pixel half from the batch's still-resident frames in one device call."""
+        frame at box_to_location(bbox), the pixel half from the batch's still-resident frames in one device call.
+        det_scales=(1.0, 0.5, ...) detects at those scales of every frame (the `det_size` of an anchor-dense detector: a 4K camera
+        detects at half size), merges the scales on the device and embeds from the full-resolution frames - one device pass
+        (Engine.process_pyramid_resident); 1 to 4 scales, each in (0, 2].  None: at native size only."""
         return self._process_frames_on(self._eng(), self.ENCODINGS.locked(), frames_bgr, max_faces, threshold, det_thresh, all_matches,
-                                       quality=quality)
+                                       quality=quality, det_scales=det_scales)
+
+    @staticmethod
+    def _check_det_scales(eng, det_scales) -> Optional[Tuple[float, ...]]:
+        """det_scales as a tuple of floats, or None; ValueError before anything reaches the engine"""
+        if det_scales is None:
+            return None
+        try:
+            scales = tuple(float(s) for s in det_scales)
+        except TypeError:
+            raise ValueError("det_scales must be a sequence of 1 to 4 scales") from None
+        if not 1 <= len(scales) <= 4:
+            raise ValueError(f"det_scales must hold 1 to 4 scales, not {len(scales)}")
+        if not all(0.0 < s <= 2.0 for s in scales):          # (NaN fails the comparison too)
+            raise ValueError(f"det_scales must lie in (0, 2]: {scales}")
+        if len(scales) * PYRAMID_PER_SCALE > 512:
+            raise ValueError("det_scales: more than 512 candidates per frame")
+        if not hasattr(eng, "process_pyramid_resident"):
+            raise ValueError("det_scales needs an engine with process_pyramid_resident")
+        return scales
+
+    @staticmethod
+    def _run_on(eng, frames, scales, max_faces, dt, fl) -> None:
+        """the asynchronous pass on the resident frames (`frames`: the batch they came from): at native size, or the pyramid of `scales`"""
+        if scales is None:
+            eng.process_resident(max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
+        else:
+            from . import pyramid
+            hw = frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[-3:-1]
+            eng.process_pyramid_resident([pyramid.scaled_size(int(hw[0]), int(hw[1]), s) for s in scales], per_scale=PYRAMID_PER_SCALE,
+                                         max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
 
     def _process_frames_on(self, eng, guard, frames_bgr, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None,
-                           quality=False):
+                           quality=False, det_scales=None):
         """`take_next` / `staged` (process_stream on a real engine): the overlapped-ingest form - this batch goes to the device
         through the engine's staging buffer (already there when the previous call staged it), the batch the lane will get
         next is claimed and its upload started on the copy stream while this batch's kernels run."""
         tol = self.tolerance if threshold is None else min(self.tolerance, threshold)   # camera.py:250
         G = self.ENCODINGS
         overlapped = take_next is not None and staged is not None
+        scales = self._check_det_scales(eng, det_scales)
         if isinstance(frames_bgr, YuvBatch):
             frames_bgr.validate()                                      # (an odd size, mixed geometry: before anything reaches the engine)
         # The device returns gallery ROW indices; store/delete move rows (swap-remove).  The guard (exclusive for
@@ -768,7 +804,7 @@ class FaceService:
                 eng.set_within(within_min_cos(tol), WITHIN_CAP)
                 fl |= native.FLAG_WITHIN
             if overlapped:
-                eng.process_resident(max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)       # asynchronous
+                self._run_on(eng, frames_bgr, scales, max_faces, dt, fl)                        # asynchronous
                 nxt = take_next()
                 if nxt is not None:
                     self._stage_on(eng, nxt)                           # copy stream: under this batch's kernels
@@ -783,14 +819,18 @@ class FaceService:
                 with eng.sequence():
                     self._stage_on(eng, frames_bgr)
                     eng.swap_frames()
-                    eng.process_resident(max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
+                    self._run_on(eng, frames_bgr, scales, max_faces, dt, fl)
                     out = eng.fetch_results()
                     qual = self._stream_quality(eng, frames_bgr, out) if quality else None
             else:
                 if isinstance(frames_bgr, _SOURCE_BATCHES):
                     frames_bgr = frames_bgr.decode()                   # an engine without the device decoder / converter (tests' FakeEngine)
                 with (self._sequence_of(eng) if quality else contextlib.nullcontext()):
-                    out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
+                    if scales is None:
+                        out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
+                    else:
+                        out = eng.process_frames_pyramid(frames_bgr, scales=scales, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU,
+                                                         per_scale=PYRAMID_PER_SCALE, flags=fl, on_device=True)
                     qual = self._stream_quality(eng, frames_bgr, out) if quality else None
             n_gallery = len(G)
             row_names = {int(r): G.name_of_row(int(r)) for r in np.unique(out["match_idx"]) if r >= 0}
@@ -886,7 +926,8 @@ class FaceService:
         eng.upload_frames_async(batch)
 
     def process_stream(self, batches, max_faces: int = 10, threshold: Optional[float] = None,
-                       det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False):
+                       det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
+                       det_scales: Optional[Sequence[float]] = None):
         """process_frames for a stream of batches with TWO batches in flight on the GPU (lanes.py: a second handle and
         host thread; +7...13 % faces/s).  Yields one process_frames result per batch, in order.  Enrolment and deletion
         may run concurrently: they wait for the batches inside their device call and reach both gallery copies under
@@ -896,16 +937,18 @@ class FaceService:
         e2 = self._eng2()
         if e2 is not None:
             engines.append(e2)
+        for e in engines:
+            self._check_det_scales(e, det_scales)          # (here, not at the first batch)
         def on(eng):
             if not all(hasattr(eng, m) for m in ("upload_frames_async", "swap_frames", "process_resident", "fetch_results", "sequence")):
                 return lambda frames, take_next: self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold,
-                                                                         det_thresh, all_matches, quality=quality)
+                                                                         det_thresh, all_matches, quality=quality, det_scales=det_scales)
             staged = {}                         # which batch sits in this lane's staging buffer
 
             def fn(frames, take_next):
                 with eng.sequence():            # upload -> swap -> process -> fetch of one lane is one uninterrupted sequence
                     return self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold, det_thresh, all_matches,
-                                                   take_next, staged, quality=quality)
+                                                   take_next, staged, quality=quality, det_scales=det_scales)
             return fn
         return lanes.run_ordered(batches, [on(e) for e in engines], prefetch=True)
 
@@ -925,7 +968,7 @@ class FaceService:
             frame = frame_bgr_or_path
         cfg = metadata or {}
         return self.process_frames(frame[None], max_faces=int(cfg.get("max_faces", 10)),
-                                   threshold=cfg.get("confidence_threshold"))[0]
+                                   threshold=cfg.get("confidence_threshold"), det_scales=cfg.get("det_scales"))[0]
 
     # ------------------------------------------------------------------ statistics / housekeeping (:617-763)
     def get_quality_statistics(self) -> Dict[str, Any]:

@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
-    "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
+    "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
     "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
@@ -215,6 +215,9 @@ def load_library() -> C.CDLL:
     lib.frp_detect_resident.argtypes = [vp, i32, i32, i32, i32, f32, f32, u32, vp, vp, vp, vp, vp]
     lib.frp_get_det_source.argtypes = [vp, vp, i64, C.POINTER(i32), C.POINTER(i32)]
     lib.frp_finish_faces.argtypes = [vp, i32, vp, vp, vp, vp, i32, u32, vp, vp, vp]
+    if hasattr(lib, "frp_process_pyramid"):  # (as frp_match_within below: an older A/B partner build has none)
+        lib.frp_process_pyramid.argtypes = [vp, i32, vp, i32, i32, f32, f32, u32]
+        lib.frp_debug_pyramid_merge.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]
     lib.frp_get_head_map.argtypes = [vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32)]
     lib.frp_debug_jpeg_device_batches.argtypes = [vp]
     lib.frp_debug_jpeg_device_batches.restype = C.c_int64
@@ -636,12 +639,49 @@ class Engine:
         self._last_shape = (B, max_faces)
         return o
 
+    def process_pyramid_resident(self, det_hws, per_scale: int = 64, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4,
+                                 flags: int = 0):
+        """the pyramid as ONE device pass on the resident frames (frp.h: frp_process_pyramid): detect at every size of det_hws
+        [(h, w), ...], merge + NMS across the scales on the device (bit for bit pyramid.merge_scales), align / embed / match from the
+        full-resolution frames.  Asynchronous like process_resident: fetch_results() waits for it and returns frame-pixel results."""
+        hw = np.ascontiguousarray(det_hws, dtype=np.int32).reshape(-1, 2)
+        self._chk(self._lib.frp_process_pyramid(self._h, hw.shape[0], _ptr(hw), per_scale, max_faces, det_thresh, nms_iou, flags))
+        self._last_k = max_faces
+        self._last_shape = (self._resident[0], max_faces)
+
+    def pyramid_merge(self, det_hws, frame_hw, boxes, kps, scores, counts, max_faces: int, nms_iou: float = 0.4):
+        """the cross-scale merge launch alone (frp.h: frp_debug_pyramid_merge) on host detections, scale-major: boxes [S, B, P, 4],
+        kps [S, B, P, 5, 2], scores [S, B, P], counts [S, B] in the coordinates of each scale's det_hws[s] = (h, w) image
+        -> boxes [B, K, 4], kps [B, K, 5, 2], scores [B, K], counts [B] in frame pixels (pyramid.merge_scales' return value)"""
+        hw = np.ascontiguousarray(det_hws, dtype=np.int32).reshape(-1, 2)
+        scores = np.ascontiguousarray(scores, np.float32)
+        if scores.ndim != 3 or scores.shape[0] != hw.shape[0]:
+            raise ValueError("scores must be [n_scales, B, per_scale]")
+        S, B, P = scores.shape
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(S, B, P, 4)
+        kps = np.ascontiguousarray(kps, np.float32).reshape(S, B, P, 10)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(S, B)
+        K = int(max_faces)
+        ob, ok = np.zeros((B, max(K, 0), 4), np.float32), np.zeros((B, max(K, 0), 5, 2), np.float32)
+        osc, oc = np.zeros((B, max(K, 0)), np.float32), np.zeros((B,), np.int32)
+        self._chk(self._lib.frp_debug_pyramid_merge(self._h, S, _ptr(hw), B, P, int(frame_hw[0]), int(frame_hw[1]), _ptr(boxes), _ptr(kps),
+                                                    _ptr(scores), _ptr(counts), K, nms_iou, _ptr(ob), _ptr(ok), _ptr(osc), _ptr(oc)))
+        return ob, ok, osc, oc
+
     def process_frames_pyramid(self, frames, scales=(1.0, 0.5, 0.25), max_faces=10, det_thresh=0.5, nms_iou=0.4,
-                               per_scale=64, flags=0):
+                               per_scale=64, flags=0, on_device: bool = False):
         """BASELINE config 4: detect at several scales of every frame, merge + NMS across scales
-        (pyramid.merge_scales), then align / embed / match from the full-resolution frames."""
+        (pyramid.merge_scales), then align / embed / match from the full-resolution frames.
+        on_device: the whole pass in one call (process_pyramid_resident: the merge on the device, the face count never visits the
+        host mid-pass, FLAG_WITHIN honoured) instead of one blocking call per scale and the merge here; the same bits."""
         from . import pyramid
         frames, B, H, W, _ = self._frames(frames)
+        if on_device:
+            with self._seq:
+                self.upload_frames(frames)
+                self.process_pyramid_resident([pyramid.scaled_size(H, W, s) for s in scales], per_scale=per_scale, max_faces=max_faces,
+                                              det_thresh=det_thresh, nms_iou=nms_iou, flags=flags)
+                return self.fetch_results()
         with self._seq:
             self.upload_frames(frames)
             per = []
@@ -770,7 +810,7 @@ class Engine:
         self._within_cap = int(cap)
 
     def fetch_within(self):
-        """hit lists of the last pass that ran with FLAG_WITHIN (process_frames / process_resident / finish_faces)
+        """hit lists of the last pass that ran with FLAG_WITHIN (process_frames / process_resident / process_pyramid_resident / finish_faces)
         -> (idx [B, K, cap], cos [B, K, cap], n_hits [B, K]); slots without a face have n_hits 0"""
         B, K = self._last_shape
         cap = self._within_cap

@@ -332,6 +332,30 @@ int frp_get_det_source(frp_handle* h, uint8_t* out, int64_t out_bytes, int32_t* 
 /* B: the resident batch the face list and the output buffers were sized for (checked under the handle mutex) */
 int frp_finish_faces(frp_handle* h, int32_t B, const float* boxes, const float* kps, const float* scores, const int32_t* counts,
                      int32_t max_faces, uint32_t flags, float* emb, int32_t* match_idx, float* match_cos);
+/* the whole pass on the resident frames: per scale resize + detector + decode/NMS (threshold mode, per_scale slots),
+   cross-scale merge + NMS on the device, then align / embed / match from the FULL-RESOLUTION frames with the face count
+   left in device memory.  Asynchronous like frp_process_resident; results through frp_fetch_results(B, max_faces)
+   (boxes / kps / scores / counts in frame pixels), hit lists through frp_fetch_within.
+   The merge equals pyramid.merge_scales bit for bit: coordinates times (float)W / (float)det_w resp. (float)H / (float)det_h in one
+   fp32 multiply, no clipping; scale order, then detector order, score descending, ties to the earlier; the +1-pixel-area greedy NMS.
+   FRP_ERR_INVALID: no weights, no resident frames, n_scales outside 1..4, per_scale or max_faces outside 1..128,
+   n_scales * per_scale > 512, a size outside 1..16384, FRP_FLAG_FORCED_K (a forced top-K per scale has no meaning under a merge),
+   FRP_FLAG_WITHIN without frp_set_within; nothing of the last pass is overwritten then.  FRP_FLAG_RGB, FRP_FLAG_NO_MATCH and
+   FRP_FLAG_WITHIN mean what they mean to frp_process_resident; the embedder's kernel family follows B * max_faces, as for every
+   process call.
+   The call leaves the detector source at the LAST scale: frp_get_det_source and frp_get_head_map report that scale, and the next
+   frp_process_frames / frp_process_resident switches back to full size by itself.
+   Stage timers: the stages still add up to ms_total.  ms_det_conv and ms_decode hold the last scale's detector and its decode + the
+   merge; everything the earlier scales ran (resize, detector, decode) is counted, with the last scale's resize, in ms_preprocess. */
+int frp_process_pyramid(frp_handle* h, int32_t n_scales, const int32_t* det_hw /* [n_scales][2]: h, w */, int32_t per_scale,
+                        int32_t max_faces, float det_thresh, float nms_iou, uint32_t flags);
+/* the merge launch alone on caller-supplied detections (host arrays, scale-major [n_scales][B][per_scale]...): needs neither
+   weights nor resident frames.  counts[s][b] must lie in [0, per_scale] and the scores of live rows must be finite and >= 0
+   (FRP_ERR_INVALID otherwise); the last pass's results stay as they are (parity tests) */
+int frp_debug_pyramid_merge(frp_handle* h, int32_t n_scales, const int32_t* det_hw, int32_t B, int32_t per_scale,
+                            int32_t frame_h, int32_t frame_w, const float* boxes, const float* kps, const float* scores,
+                            const int32_t* counts, int32_t max_faces, float nms_iou,
+                            float* out_boxes, float* out_kps, float* out_scores, int32_t* out_counts);
 
 /* raw detector head maps of the last detect/process call, per stride level 0..2:
  * [B, H/stride, W/stride, 32] fp16 (parity tests) */

@@ -27,19 +27,45 @@ import logging
 import os
 import threading
 import time
-from collections import deque
+from collections import deque, namedtuple
 from datetime import datetime
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import lanes, native
+from . import ingest, lanes, native, pyramid
 from .gallery import Gallery
 from .mjpeg import JpegBatch
 from .yuv import YuvBatch
 
 _SOURCE_BATCHES = (JpegBatch, YuvBatch)      # batches that are not pixel arrays yet: they carry `hw` and `decode()`
+
+
+def frames_hw(frames) -> Tuple[int, int]:
+    """(height, width) of the frames of a batch: a source batch carries it, an array is [B, H, W, 3] or one frame [H, W, 3]"""
+    return tuple(int(v) for v in (frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[-3:-1]))
+
+
+# What an engine can do, as this file asks it (native.Engine: all of it; the tests' partial engines: some): field -> the methods it
+# stands for.  Found by duck typing, here and nowhere else; questions that sound alike and are asked differently are separate fields.
+_CAPS = {
+    "exact_gallery": ("gallery_exact",),             # float64 rows as enrolled behind the compat calls
+    "sequence": ("sequence",),                       # the multi-call lock
+    "face_quality": ("face_quality",),               # ... on the resident frames
+    "match_within": ("match_within",),               # the stand-alone radius match (batch_compare_faces)
+    "pass_within": ("fetch_within",),                # the radius match fused into a pass: set_within before it, fetch_within after it
+    "pyramid": ("process_pyramid_resident",),        # det_scales=
+    "lane": ("upload_frames_async", "swap_frames", "process_resident", "fetch_results", "sequence"),    # process_stream's overlapped form
+    "stage_jpeg": ("upload_jpeg_async",),            # process_frames stages a JpegBatch: upload, swap, pass, fetch under sequence()
+    "stage_yuv": ("upload_yuv_async", "swap_frames"),                                                    # ... a YuvBatch
+}
+EngineCaps = namedtuple("EngineCaps", list(_CAPS))
+
+
+def engine_caps(eng) -> EngineCaps:
+    return EngineCaps(*(all(hasattr(eng, m) for m in methods) for methods in _CAPS.values()))
+
 
 logger = logging.getLogger(__name__)
 
@@ -91,6 +117,60 @@ def within_to_matches(rows, cos, n_hits, tol: float, pos_of_row) -> List[Tuple[i
     return list(zip(pos[order].tolist(), d[order].tolist()))
 
 
+def match_dicts(targets: Sequence[str], tol: float, hits=None, row=None, flag: bool = False) -> List[Dict[str, Any]]:
+    """One query's list of the targets within `tol`, ascending by distance, ties in the order of `targets` (the reference sorts
+    stably: face_service.py:432,479): from `hits` = [(position, distance)] as within_to_matches orders them, or from `row`, the
+    distances to all targets.  flag: batch_compare_faces' form, with "match": True."""
+    if hits is None:
+        row = np.asarray(row)
+        order = np.argsort(row, kind="stable")
+        order = order[row[order] <= tol]
+        hits = zip(order.tolist(), row[order].tolist())
+    if flag:
+        return [{"target": targets[j], "match": True, "distance": d, "confidence": confidence_level(d)} for j, d in hits]
+    return [{"target": targets[j], "distance": d, "confidence": confidence_level(d)} for j, d in hits]
+
+
+def face_dicts(out: Dict[str, np.ndarray], row_names: Dict[int, str], tol: float, all_matches: bool = False, names: Optional[List[str]] = None,
+               hits=None, dist_rows=None, qual=None) -> Tuple[List[List[Dict[str, Any]]], int]:
+    """The fetched arrays `out` of one pass -> (per frame its list of face dicts, the number of faces).  `row_names`: gallery row -> name
+    as it was under the guard; all_matches: every face gets "matches" - match_dicts of `names` from `hits` or `dist_rows` (one entry per
+    face), [] when neither is given; `qual`: per face its quality dict.  Host arithmetic on its arguments: no device call, no lock.
+    One pass of array arithmetic for the whole batch (distance, bucket, threshold), ONE tolist() per field; the per-face work left is
+    building the dict (the reference builds N of them per face, camera.py:243-259)."""
+    counts = np.asarray(out["counts"], dtype=np.int64)
+    K = out["match_idx"].shape[1]
+    live = np.arange(K)[None, :] < counts[:, None]                    # [B, K]: slots that hold a face
+    rows = out["match_idx"][live].astype(np.int64)
+    hit = rows >= 0
+    cos = out["match_cos"][live].astype(np.float64)
+    dist = cos_to_distance(cos)
+    conf = np.where(dist < 0.4, "high", np.where(dist < 0.6, "medium", "low"))         # confidence_level, vectorised
+    is_match = hit & (dist <= tol)
+    boxes, kps, scores = out["boxes"][live].tolist(), out["kps"][live].tolist(), out["scores"][live].tolist()
+    emb = out["emb"][live]                                            # [n, 512]: one gather, rows handed out as views
+    rows_l, hit_l, cos_l, dist_l, conf_l, match_l = rows.tolist(), hit.tolist(), cos.tolist(), dist.tolist(), conf.tolist(), is_match.tolist()
+    result = []
+    n = 0
+    for c in counts.tolist():
+        faces = []
+        for i in range(n, n + c):
+            h_ = hit_l[i]
+            face = {"bbox": boxes[i], "kps": kps[i], "score": scores[i], "embedding": emb[i],
+                    "target": row_names.get(rows_l[i]) if h_ else None,
+                    "distance": dist_l[i] if h_ else None, "cosine": cos_l[i] if h_ else None,
+                    "confidence": conf_l[i] if h_ else None, "match": match_l[i]}
+            if all_matches:
+                face["matches"] = (match_dicts(names, tol, hits=hits[i]) if hits is not None else
+                                   match_dicts(names, tol, row=dist_rows[i]) if dist_rows is not None else [])
+            if qual is not None:
+                face["quality"] = qual[i]
+            faces.append(face)
+        n += c
+        result.append(faces)
+    return result, n
+
+
 def confidence_level(distance: float) -> str:                         # :486-492
     return "high" if distance < 0.4 else ("medium" if distance < 0.6 else "low")
 
@@ -131,6 +211,66 @@ class NullStorage:
         return None
 
 
+class _Plan(NamedTuple):
+    """what one frame pass asks of the engine: decided once per call (FaceService._plan), ahead of the route's branch"""
+    max_faces: int
+    tol: float                               # min(service tolerance, threshold)
+    det_thresh: float
+    flags: int                               # FLAG_NO_MATCH on an empty gallery, FLAG_WITHIN when `within`
+    scales: Optional[Tuple[float, ...]]      # det_scales, checked; None: at native size only
+    within: bool                             # the radius match is armed: set_within before the pass, fetch_within after it
+    list_all: bool                           # all_matches on a gallery that has rows
+    quality: bool
+
+
+BLOCKING, STAGED, OVERLAPPED = "blocking", "staged", "overlapped"
+
+
+def _route(caps: EngineCaps, frames, overlapped: bool) -> str:
+    """how a batch gets onto the device.  OVERLAPPED: process_stream's lane form (its caller found caps.lane); STAGED: a source batch on
+    an engine that decodes / converts it on the way; BLOCKING: one process call on host pixels (a source batch is decoded here first)"""
+    if overlapped:
+        return OVERLAPPED
+    if (isinstance(frames, JpegBatch) and caps.stage_jpeg) or (isinstance(frames, YuvBatch) and caps.stage_yuv):
+        return STAGED
+    return BLOCKING
+
+
+def _check_det_scales(caps: EngineCaps, det_scales) -> Optional[Tuple[float, ...]]:
+    """det_scales as a tuple of floats, or None; ValueError before anything reaches the engine"""
+    if det_scales is None:
+        return None
+    try:
+        scales = tuple(float(s) for s in det_scales)
+    except TypeError:
+        raise ValueError("det_scales must be a sequence of 1 to 4 scales") from None
+    if not 1 <= len(scales) <= 4:
+        raise ValueError(f"det_scales must hold 1 to 4 scales, not {len(scales)}")
+    if not all(0.0 < s <= 2.0 for s in scales):          # (NaN fails the comparison too)
+        raise ValueError(f"det_scales must lie in (0, 2]: {scales}")
+    if len(scales) * PYRAMID_PER_SCALE > 512:
+        raise ValueError("det_scales: more than 512 candidates per frame")
+    if not caps.pyramid:
+        raise ValueError("det_scales needs an engine with process_pyramid_resident")
+    return scales
+
+
+def _bring_in(eng, frames, staged: Optional[dict] = None) -> None:
+    """the batch into the engine's resident frames through its staging buffer; `staged`: the lane's note of what is staged already"""
+    if staged is None or staged.pop("key", None) != id(frames):
+        ingest.stage_on(eng, frames)
+    eng.swap_frames()
+
+
+def _run_resident(eng, plan: _Plan, hw: Tuple[int, int]) -> None:
+    """the asynchronous pass on the resident frames of size `hw`: at native size, or the pyramid of plan.scales"""
+    if plan.scales is None:
+        eng.process_resident(plan.max_faces, det_thresh=plan.det_thresh, nms_iou=NMS_IOU, flags=plan.flags)
+    else:
+        eng.process_pyramid_resident([pyramid.scaled_size(hw[0], hw[1], s) for s in plan.scales], per_scale=PYRAMID_PER_SCALE,
+                                     max_faces=plan.max_faces, det_thresh=plan.det_thresh, nms_iou=NMS_IOU, flags=plan.flags)
+
+
 class FaceService:
     def __init__(self, engine: Optional[Any] = None, storage: Optional[Any] = None, device: Optional[int] = None,
                  weights_blob: Optional[bytes] = None, second_engine: Optional[Any] = None):
@@ -148,7 +288,7 @@ class FaceService:
         # rows that are not unit vectors and for 128-d rows.  FRP_EXACT_COMPAT=0: cosines of the unit fp16 rows instead
         # (4 KB per identity less device memory; distances good to ~2e-3, 0.03 near 0).
         self._exact = os.getenv("FRP_EXACT_COMPAT", "1") != "0"
-        if engine is not None and self._exact and hasattr(engine, "gallery_exact"):
+        if engine is not None and self._exact and engine_caps(engine).exact_gallery:
             engine.gallery_exact(True)
             self.ENCODINGS.exact = True
         # process_stream keeps two batches in flight on the GPU (lanes.py): a second handle with its own copy of the
@@ -230,8 +370,7 @@ class FaceService:
     @staticmethod
     def _sequence_of(eng):
         """the engine's multi-call lock (a pass and the face_quality call on its still-resident frames are one sequence)"""
-        seq = getattr(eng, "sequence", None)
-        return seq() if seq is not None else contextlib.nullcontext()
+        return eng.sequence() if engine_caps(eng).sequence else contextlib.nullcontext()
 
     def _quality_of(self, eng, frames, faces: List[Tuple[int, Tuple[int, int, int, int]]], rgb: bool) -> List[Dict[str, Any]]:
         """assess_face_quality for `faces` = [(frame index, (top, right, bottom, left))] of the batch `frames` ([B,H,W,3] in RGB or
@@ -240,7 +379,7 @@ class FaceService:
         face_quality (the tests' FakeEngine).  In the order of `faces`."""
         if not faces:
             return []
-        H, W = frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[1:3]
+        H, W = frames_hw(frames)
         pixels = [None if isinstance(frames, _SOURCE_BATCHES) else frames]
 
         def on_host(b, loc):
@@ -249,7 +388,8 @@ class FaceService:
             img = pixels[0][b]
             return self.assess_face_quality(img if rgb else img[..., ::-1], loc)
 
-        on_dev = [hasattr(eng, "face_quality") and 0 <= loc[0] < loc[2] <= H and 0 <= loc[3] < loc[1] <= W for _, loc in faces]
+        has = engine_caps(eng).face_quality
+        on_dev = [has and 0 <= loc[0] < loc[2] <= H and 0 <= loc[3] < loc[1] <= W for _, loc in faces]
         sums = iter(eng.face_quality([(b, *loc) for (b, loc), ok in zip(faces, on_dev) if ok], rgb=rgb)) if any(on_dev) else None
         return [self.quality_from_sums((H, W, 3), loc, (loc[2] - loc[0]) * (loc[1] - loc[3]), next(sums)) if ok else on_host(b, loc)
                 for (b, loc), ok in zip(faces, on_dev)]
@@ -261,7 +401,7 @@ class FaceService:
         try:
             eng = self._eng()
             with self._sequence_of(eng):
-                _, H, W = eng._resident
+                _, H, W = eng.resident_shape
                 return eng.encode_jpeg([(int(frame), 0, W, H, 0)], quality=quality)[0]
         except Exception as e:
             logger.exception("Error encoding snapshot of frame %s: %s", frame, e)
@@ -273,7 +413,7 @@ class FaceService:
         try:
             eng = self._eng()
             with self._sequence_of(eng):
-                B, H, W = eng._resident
+                B, H, W = eng.resident_shape
                 return eng.encode_jpeg([(b, 0, W, H, 0) for b in range(B)], quality=quality)
         except Exception as e:
             logger.exception("Error encoding the resident frames: %s", e)
@@ -286,7 +426,7 @@ class FaceService:
         try:
             eng = self._eng()
             with self._sequence_of(eng):
-                _, H, W = eng._resident
+                _, H, W = eng.resident_shape
                 rects = []
                 for b, (top, right, bottom, left) in faces:
                     dy, dx = int(round(margin * (bottom - top))), int(round(margin * (right - left)))
@@ -616,31 +756,29 @@ class FaceService:
         G = self.ENCODINGS
         if len(test_encodings) == 0:
             return []
+        tol = self.tolerance
+        hits = None
         try:
             with G.locked():
                 targets = G.names() if target_names is None else [t for t in target_names if t in G]
                 if not targets:
                     return [[] for _ in test_encodings]
+                eng = self._eng()
                 if G.exact:
                     Q = np.stack([np.asarray(q, dtype=np.float64).reshape(-1) for q in test_encodings])
-                    D = self._eng().gallery_distances(Q)[:, G.rows_of(targets)]
+                    D = eng.gallery_distances(Q)[:, G.rows_of(targets)]
                 else:
                     Q = np.stack([np.asarray(q, dtype=np.float32).reshape(-1) for q in test_encodings])
-                    hits = self._within_hits(self._eng(), Q, targets, self.tolerance)
-                    if hits is not None:
-                        return [[{"target": targets[i], "match": True, "distance": d, "confidence": confidence_level(d)} for i, d in hl]
-                                for hl in hits]
-                    D = cos_to_distance(self._eng().match_scores(Q)[:, G.rows_of(targets)])
+                    hits = self._within_hits(self.use_within and engine_caps(eng).match_within, targets, tol,
+                                             lambda: eng.match_within(Q, within_min_cos(tol), WITHIN_CAP))
+                    if hits is None:
+                        D = cos_to_distance(eng.match_scores(Q)[:, G.rows_of(targets)])
         except Exception as e:
             logger.exception("Error in batch comparison: %s", e)
             return [[] for _ in test_encodings]
-        out = []
-        for d in D:
-            res = [{"target": targets[i], "match": True, "distance": float(d[i]), "confidence": confidence_level(d[i])}
-                   for i in np.nonzero(d <= self.tolerance)[0]]
-            res.sort(key=lambda x: x["distance"])
-            out.append(res)
-        return out
+        if hits is not None:
+            return [match_dicts(targets, tol, hits=hl, flag=True) for hl in hits]
+        return [match_dicts(targets, tol, row=d, flag=True) for d in D]
 
     def _pos_of_row(self, targets: List[str]) -> Optional[np.ndarray]:
         """gallery row -> position in `targets` (-1: not a target); None when a name is listed twice (a row then has two positions)"""
@@ -650,19 +788,21 @@ class FaceService:
         pos[rows] = np.arange(len(rows))
         return pos if int((pos >= 0).sum()) == len(rows) else None
 
-    def _within_hits(self, eng, Q: np.ndarray, targets: List[str], tol: float):
-        """per query [(position in targets, distance)] within tol by the device radius match (one gallery pass, hit lists only);
-        None: not on this path - switched off, an engine without it, or a query with more hits than a list holds (the
-        reference lists every target, so a list may not be cut: the caller takes the full-row path).  Gallery lock held."""
-        if not (self.use_within and hasattr(eng, "match_within")):
+    def _within_hits(self, armed: bool, targets: List[str], tol: float, lists: Callable[[], Tuple[np.ndarray, np.ndarray, np.ndarray]]):
+        """per query [(position in targets, distance)] within tol from the device radius match: `lists()` -> (idx [M, cap], cos [M, cap],
+        n_hits [M]), one hit list per query (Engine.match_within, or Engine.fetch_within cut down to the slots that hold a face).
+        None: not on this path - `armed` is off (switched off, or an engine without it; lists() is not called then), a name listed
+        twice, or a query with more hits than a list holds (the reference lists every target, so a list may not be cut): the caller
+        takes the full score rows.  Gallery lock held."""
+        if not armed:
             return None
         pos_of_row = self._pos_of_row(targets)
         if pos_of_row is None:
             return None
-        idx, cos, n_hits = eng.match_within(Q, within_min_cos(tol), WITHIN_CAP)
+        idx, cos, n_hits = lists()
         if int(n_hits.max(initial=0)) > WITHIN_CAP:
             return None
-        return [within_to_matches(idx[i], cos[i], n_hits[i], tol, pos_of_row) for i in range(len(Q))]
+        return [within_to_matches(r, c, k, tol, pos_of_row) for r, c, k in zip(idx, cos, n_hits)]
 
     def _get_confidence_level(self, distance: float) -> str:
         return confidence_level(distance)
@@ -744,186 +884,113 @@ class FaceService:
         return self._process_frames_on(self._eng(), self.ENCODINGS.locked(), frames_bgr, max_faces, threshold, det_thresh, all_matches,
                                        quality=quality, det_scales=det_scales)
 
-    @staticmethod
-    def _check_det_scales(eng, det_scales) -> Optional[Tuple[float, ...]]:
-        """det_scales as a tuple of floats, or None; ValueError before anything reaches the engine"""
-        if det_scales is None:
-            return None
-        try:
-            scales = tuple(float(s) for s in det_scales)
-        except TypeError:
-            raise ValueError("det_scales must be a sequence of 1 to 4 scales") from None
-        if not 1 <= len(scales) <= 4:
-            raise ValueError(f"det_scales must hold 1 to 4 scales, not {len(scales)}")
-        if not all(0.0 < s <= 2.0 for s in scales):          # (NaN fails the comparison too)
-            raise ValueError(f"det_scales must lie in (0, 2]: {scales}")
-        if len(scales) * PYRAMID_PER_SCALE > 512:
-            raise ValueError("det_scales: more than 512 candidates per frame")
-        if not hasattr(eng, "process_pyramid_resident"):
-            raise ValueError("det_scales needs an engine with process_pyramid_resident")
-        return scales
-
-    @staticmethod
-    def _run_on(eng, frames, scales, max_faces, dt, fl) -> None:
-        """the asynchronous pass on the resident frames (`frames`: the batch they came from): at native size, or the pyramid of `scales`"""
-        if scales is None:
-            eng.process_resident(max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
-        else:
-            from . import pyramid
-            hw = frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[-3:-1]
-            eng.process_pyramid_resident([pyramid.scaled_size(int(hw[0]), int(hw[1]), s) for s in scales], per_scale=PYRAMID_PER_SCALE,
-                                         max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
-
-    def _process_frames_on(self, eng, guard, frames_bgr, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None,
+    def _process_frames_on(self, eng, guard, frames, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None,
                            quality=False, det_scales=None):
-        """`take_next` / `staged` (process_stream on a real engine): the overlapped-ingest form - this batch goes to the device
-        through the engine's staging buffer (already there when the previous call staged it), the batch the lane will get
-        next is claimed and its upload started on the copy stream while this batch's kernels run."""
-        tol = self.tolerance if threshold is None else min(self.tolerance, threshold)   # camera.py:250
+        """One frame pass on `eng`.  `take_next` / `staged` (process_stream on an engine with the lane calls): the overlapped form - this
+        batch goes to the device through the engine's staging buffer (already there when the previous call staged it), the batch the
+        lane will get next is claimed and its upload started on the copy stream while this batch's kernels run."""
+        caps = engine_caps(eng)
+        scales = _check_det_scales(caps, det_scales)
+        if isinstance(frames, YuvBatch):
+            frames.validate()                                          # (an odd size, mixed geometry: before anything reaches the engine)
+        route = _route(caps, frames, take_next is not None and staged is not None)
+        if route == OVERLAPPED:
+            _bring_in(eng, frames, staged)                             # (ahead of the guard: the lane owns its staging buffer)
         G = self.ENCODINGS
-        overlapped = take_next is not None and staged is not None
-        scales = self._check_det_scales(eng, det_scales)
-        if isinstance(frames_bgr, YuvBatch):
-            frames_bgr.validate()                                      # (an odd size, mixed geometry: before anything reaches the engine)
         # The device returns gallery ROW indices; store/delete move rows (swap-remove).  The guard (exclusive for
         # process_frames, shared between the lanes of process_stream) is held over the device call and the
         # row -> name snapshot, so a concurrent delete can neither mis-attribute a face to the identity that was
         # moved into its row nor shrink the table under the lookup.
-        if overlapped:
-            key = id(frames_bgr)
-            if staged.pop("key", None) != key:                         # not staged by the previous call: stage it now
-                self._stage_on(eng, frames_bgr)
-            eng.swap_frames()
         with guard:
-            have_gallery = len(G) > 0
-            dt = DET_THRESH if det_thresh is None else det_thresh
-            fl = 0 if have_gallery else native.FLAG_NO_MATCH
-            # all_matches on the device: the pass's own match kernel also lists every row within the bound (FLAG_WITHIN)
-            within = all_matches and have_gallery and self.use_within and hasattr(eng, "fetch_within")
-            if within:
-                eng.set_within(within_min_cos(tol), WITHIN_CAP)
-                fl |= native.FLAG_WITHIN
-            if overlapped:
-                self._run_on(eng, frames_bgr, scales, max_faces, dt, fl)                        # asynchronous
-                nxt = take_next()
-                if nxt is not None:
-                    self._stage_on(eng, nxt)                           # copy stream: under this batch's kernels
-                    staged["key"] = id(nxt)
-                idle = getattr(take_next, "idle", None)
-                if idle is not None:
-                    idle()                                             # the PREVIOUS batch's result dicts, under this batch's kernels
-                out = eng.fetch_results()                              # waits for the pass
-                qual = self._stream_quality(eng, frames_bgr, out) if quality else None      # (before the lane's next swap_frames)
-            elif (isinstance(frames_bgr, JpegBatch) and hasattr(eng, "upload_jpeg_async")) or \
-                    (isinstance(frames_bgr, YuvBatch) and hasattr(eng, "upload_yuv_async") and hasattr(eng, "swap_frames")):
+            plan = self._plan(caps, len(G) > 0, max_faces, threshold, det_thresh, all_matches, quality, scales)
+            if plan.within:
+                eng.set_within(within_min_cos(plan.tol), WITHIN_CAP)
+            if route == OVERLAPPED:
+                out, qual = self._overlapped_pass(eng, frames, plan, take_next, staged)
+            elif route == STAGED:
                 with eng.sequence():
-                    self._stage_on(eng, frames_bgr)
-                    eng.swap_frames()
-                    self._run_on(eng, frames_bgr, scales, max_faces, dt, fl)
-                    out = eng.fetch_results()
-                    qual = self._stream_quality(eng, frames_bgr, out) if quality else None
+                    _bring_in(eng, frames)
+                    _run_resident(eng, plan, frames_hw(frames))
+                    out, qual = self._fetch(eng, frames, plan)
             else:
-                if isinstance(frames_bgr, _SOURCE_BATCHES):
-                    frames_bgr = frames_bgr.decode()                   # an engine without the device decoder / converter (tests' FakeEngine)
-                with (self._sequence_of(eng) if quality else contextlib.nullcontext()):
-                    if scales is None:
-                        out = eng.process_frames(frames_bgr, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU, flags=fl)
-                    else:
-                        out = eng.process_frames_pyramid(frames_bgr, scales=scales, max_faces=max_faces, det_thresh=dt, nms_iou=NMS_IOU,
-                                                         per_scale=PYRAMID_PER_SCALE, flags=fl, on_device=True)
-                    qual = self._stream_quality(eng, frames_bgr, out) if quality else None
+                out, qual = self._blocking_pass(eng, frames, plan)
             n_gallery = len(G)
             row_names = {int(r): G.name_of_row(int(r)) for r in np.unique(out["match_idx"]) if r >= 0}
-            all_d = names = all_hits = None
-            if all_matches and have_gallery and int(out["counts"].sum()) > 0:
-                names = G.names()
-                if within:
-                    w_idx, w_cos, w_n = eng.fetch_within()
-                    live_w = np.arange(w_n.shape[1])[None, :] < np.asarray(out["counts"])[:, None]
-                    if int(w_n[live_w].max(initial=0)) <= WITHIN_CAP:       # else a list was cut: the full rows below
-                        pos_of_row = self._pos_of_row(names)
-                        all_hits = [within_to_matches(r, c, k, tol, pos_of_row) for r, c, k in zip(w_idx[live_w], w_cos[live_w], w_n[live_w])]
-                if all_hits is None:
-                    Q = np.concatenate([out["emb"][b, :int(c)] for b, c in enumerate(out["counts"])])
-                    all_d = cos_to_distance(eng.match_scores(Q)[:, G.rows_of(names)])
-        def build():
-            # One pass of array arithmetic for the whole batch (distance, bucket, threshold), ONE tolist() per field; the per-face
-            # work left is building the dict (the reference builds N of them per face, camera.py:243-259).
-            counts = np.asarray(out["counts"], dtype=np.int64)
-            K = out["match_idx"].shape[1]
-            live = np.arange(K)[None, :] < counts[:, None]                    # [B, K]: slots that hold a face
-            rows = out["match_idx"][live].astype(np.int64)
-            hit = rows >= 0
-            cos = out["match_cos"][live].astype(np.float64)
-            dist = cos_to_distance(cos)
-            conf = np.where(dist < 0.4, "high", np.where(dist < 0.6, "medium", "low"))         # confidence_level, vectorised
-            is_match = hit & (dist <= tol)
-            boxes, kps, scores = out["boxes"][live].tolist(), out["kps"][live].tolist(), out["scores"][live].tolist()
-            emb = out["emb"][live]                                            # [n, 512]: one gather, rows handed out as views
-            rows_l, hit_l, cos_l, dist_l, conf_l, match_l = rows.tolist(), hit.tolist(), cos.tolist(), dist.tolist(), conf.tolist(), is_match.tolist()
-            result = []
-            f_idx = 0
-            for c in counts.tolist():
-                faces = []
-                for _ in range(c):
-                    i = f_idx
-                    h_ = hit_l[i]
-                    face = {"bbox": boxes[i], "kps": kps[i], "score": scores[i], "embedding": emb[i],
-                            "target": row_names.get(rows_l[i]) if h_ else None,
-                            "distance": dist_l[i] if h_ else None, "cosine": cos_l[i] if h_ else None,
-                            "confidence": conf_l[i] if h_ else None, "match": match_l[i]}
-                    if all_matches:
-                        hits = []
-                        if all_hits is not None:
-                            hits = [{"target": names[j], "distance": d, "confidence": confidence_level(d)} for j, d in all_hits[i]]
-                        elif all_d is not None:
-                            dd = all_d[i]
-                            order = np.argsort(dd, kind="stable")          # compare_faces sorts ascending (:432)
-                            hits = [{"target": names[j], "distance": float(dd[j]), "confidence": confidence_level(float(dd[j]))}
-                                    for j in order if dd[j] <= tol]
-                        face["matches"] = hits
-                    if qual is not None:
-                        face["quality"] = qual[i]
-                    faces.append(face)
-                    f_idx += 1
-                result.append(faces)
-            n_total = f_idx
+            listed = self._all_matches_of(eng, out, plan) if plan.list_all and int(out["counts"].sum()) > 0 else {}
+
+        def finish():
+            result, n = face_dicts(out, row_names, plan.tol, all_matches, qual=qual, **listed)
             with self._metrics_lock:
-                self._metrics["total_encodings"] += n_total
-                self._metrics["total_comparisons"] += n_total * n_gallery
+                self._metrics["total_encodings"] += n
+                self._metrics["total_comparisons"] += n * n_gallery
             return result
 
         # process_stream: the dicts of this batch are built by the lane's thread while its NEXT batch is on the device
         # (lanes.Deferred); everything they need was taken above, under the guard.
-        return lanes.Deferred(build) if overlapped else build()
+        return lanes.Deferred(finish) if route == OVERLAPPED else finish()
+
+    def _plan(self, caps: EngineCaps, have_gallery: bool, max_faces, threshold, det_thresh, all_matches, quality, scales) -> "_Plan":
+        tol = self.tolerance if threshold is None else min(self.tolerance, threshold)   # camera.py:250
+        list_all = bool(all_matches) and have_gallery
+        # all_matches on the device: the pass's own match kernel also lists every row within the bound (FLAG_WITHIN)
+        within = bool(list_all and self.use_within and caps.pass_within)
+        flags = (0 if have_gallery else native.FLAG_NO_MATCH) | (native.FLAG_WITHIN if within else 0)
+        return _Plan(max_faces, tol, DET_THRESH if det_thresh is None else det_thresh, flags, scales, within, list_all, bool(quality))
+
+    def _overlapped_pass(self, eng, frames, plan: "_Plan", take_next, staged):
+        """what only the lane form does, between the shared steps: stage the lane's next batch and build the PREVIOUS one's dicts (idle)"""
+        _run_resident(eng, plan, frames_hw(frames))                    # asynchronous
+        nxt = take_next()
+        if nxt is not None:
+            ingest.stage_on(eng, nxt)                                  # copy stream: under this batch's kernels
+            staged["key"] = id(nxt)
+        idle = getattr(take_next, "idle", None)
+        if idle is not None:
+            idle()
+        return self._fetch(eng, frames, plan)                          # (quality: before the lane's next swap_frames)
+
+    def _fetch(self, eng, frames, plan: "_Plan"):
+        """-> (the results of the queued pass - waits for it -, the quality list of its faces while the frames are still resident, or None)"""
+        out = eng.fetch_results()
+        return out, (self._stream_quality(eng, frames, out) if plan.quality else None)
+
+    def _blocking_pass(self, eng, frames, plan: "_Plan"):
+        """the pass as ONE engine call on host pixels -> (results, quality list or None)"""
+        if isinstance(frames, _SOURCE_BATCHES):
+            frames = frames.decode()                                   # an engine without the device decoder / converter (tests' FakeEngine)
+        kw = dict(max_faces=plan.max_faces, det_thresh=plan.det_thresh, nms_iou=NMS_IOU, flags=plan.flags)
+        with (self._sequence_of(eng) if plan.quality else contextlib.nullcontext()):
+            if plan.scales is None:
+                out = eng.process_frames(frames, **kw)
+            else:
+                out = eng.process_frames_pyramid(frames, scales=plan.scales, per_scale=PYRAMID_PER_SCALE, on_device=True, **kw)
+            return out, (self._stream_quality(eng, frames, out) if plan.quality else None)
+
+    def _all_matches_of(self, eng, out, plan: "_Plan") -> Dict[str, Any]:
+        """face_dicts' `names` and `hits` or `dist_rows` for the faces of `out`: the hit lists of the pass where the radius match was
+        armed and no list was cut, else one full-row pass over the gallery.  Gallery guard held."""
+        G = self.ENCODINGS
+        names = G.names()
+        counts = np.asarray(out["counts"])
+
+        def lists():
+            idx, cos, n_hits = eng.fetch_within()
+            live = np.arange(n_hits.shape[1])[None, :] < counts[:, None]
+            return idx[live], cos[live], n_hits[live]
+
+        hits = self._within_hits(plan.within, names, plan.tol, lists)
+        if hits is not None:
+            return {"names": names, "hits": hits}
+        Q = np.concatenate([out["emb"][b, :int(c)] for b, c in enumerate(counts)])
+        return {"names": names, "dist_rows": cos_to_distance(eng.match_scores(Q)[:, G.rows_of(names)])}
 
     def _stream_quality(self, eng, frames_bgr, out) -> List[Dict[str, Any]]:
         """quality dicts of a fetched batch's faces, frame by frame (the order of the face dicts), from the frames still resident on `eng`"""
         frames = frames_bgr if isinstance(frames_bgr, _SOURCE_BATCHES) or frames_bgr.ndim == 4 else frames_bgr[None]
-        H, W = frames.hw if isinstance(frames, _SOURCE_BATCHES) else frames.shape[1:3]
+        H, W = frames_hw(frames)
         K = out["boxes"].shape[1]
         faces = [(b, box_to_location(out["boxes"][b, k], H, W)) for b, c in enumerate(out["counts"]) for k in range(min(int(c), K))]
         return self._quality_of(eng, frames, faces, rgb=False)
-
-    @staticmethod
-    def _stage_on(eng, batch) -> None:
-        """start moving a batch into the lane's staging frame buffer: pixel arrays by DMA, encoded batches (mjpeg.JpegBatch)
-        through the engine's JPEG path - bit streams decoded here on host threads, pixels produced on the copy stream -
-        unless the device decoder does not cover the batch (progressive frames, mixed sampling): then PIL decodes it; decoded
-        YUV 4:2:0 surfaces (yuv.YuvBatch) through the engine's converter where it has one, else converted here"""
-        if isinstance(batch, YuvBatch):
-            if hasattr(eng, "upload_yuv_async"):
-                eng.upload_yuv_async(batch)
-                return
-            batch = batch.decode()
-        if isinstance(batch, JpegBatch):
-            from . import ingest
-            jp = ingest.device_jpeg_batch(batch, len(batch), batch.hw)
-            if jp is not None:
-                eng.upload_jpeg_async(jp)
-                return
-            batch = batch.decode()
-        eng.upload_frames_async(batch)
 
     def process_stream(self, batches, max_faces: int = 10, threshold: Optional[float] = None,
                        det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
@@ -938,17 +1005,19 @@ class FaceService:
         if e2 is not None:
             engines.append(e2)
         for e in engines:
-            self._check_det_scales(e, det_scales)          # (here, not at the first batch)
+            _check_det_scales(engine_caps(e), det_scales)  # (here, not at the first batch)
+
         def on(eng):
-            if not all(hasattr(eng, m) for m in ("upload_frames_async", "swap_frames", "process_resident", "fetch_results", "sequence")):
-                return lambda frames, take_next: self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold,
-                                                                         det_thresh, all_matches, quality=quality, det_scales=det_scales)
+            def run(frames, take_next=None, staged=None):
+                return self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold, det_thresh, all_matches,
+                                               take_next, staged, quality=quality, det_scales=det_scales)
+            if not engine_caps(eng).lane:
+                return lambda frames, take_next: run(frames)
             staged = {}                         # which batch sits in this lane's staging buffer
 
             def fn(frames, take_next):
                 with eng.sequence():            # upload -> swap -> process -> fetch of one lane is one uninterrupted sequence
-                    return self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold, det_thresh, all_matches,
-                                                   take_next, staged, quality=quality, det_scales=det_scales)
+                    return run(frames, take_next, staged)
             return fn
         return lanes.run_ordered(batches, [on(e) for e in engines], prefetch=True)
 

@@ -25,6 +25,8 @@ from typing import Iterable, Iterator, List, Sequence, Tuple, Union
 import numpy as np
 
 from . import native
+from .mjpeg import JpegBatch
+from .yuv import YuvBatch
 
 Source = Union[str, bytes, np.ndarray]
 
@@ -65,6 +67,25 @@ def device_jpeg_batch(sources: Sequence[Source], batch: int, hw: Tuple[int, int]
         sampling = key
         out.append(s)
     return out
+
+
+def stage_on(eng, batch) -> None:
+    """start moving a batch into the engine's staging frame buffer (FaceService's staged and overlapped passes): pixel arrays by DMA,
+    encoded batches (mjpeg.JpegBatch) through the engine's JPEG path - bit streams decoded here on host threads, pixels produced on
+    the copy stream - unless the device decoder does not cover the batch (progressive frames, mixed sampling): then PIL decodes it;
+    decoded YUV 4:2:0 surfaces (yuv.YuvBatch) through the engine's converter where it has one, else converted here"""
+    if isinstance(batch, YuvBatch):
+        if hasattr(eng, "upload_yuv_async"):
+            eng.upload_yuv_async(batch)
+            return
+        batch = batch.decode()
+    if isinstance(batch, JpegBatch):
+        jp = device_jpeg_batch(batch, len(batch), batch.hw)
+        if jp is not None:
+            eng.upload_jpeg_async(jp)
+            return
+        batch = batch.decode()
+    eng.upload_frames_async(batch)
 
 
 def batched(sources: Sequence[Source], batch: int) -> Iterator[Sequence[Source]]:

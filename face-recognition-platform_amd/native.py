@@ -293,11 +293,19 @@ class Engine:
         # threads sharing one Engine take this lock around a whole sequence (`with eng.sequence(): ...`).  The
         # C side additionally checks every caller-sized buffer against the handle's state under its own mutex.
         self._seq = threading.RLock()
+        # The shapes the caller-sized buffers of later calls follow; the library checks every one of them against the handle's own state,
+        # so a call on an engine that has had no batch or pass reaches it with zeros and comes back as its refusal (FrpError).
+        self._resident = (0, 0, 0)       # (B, H, W) of the resident frames
+        self._staged = (0, 0, 0)         # ... of the staging frame buffer: resident at swap_frames()
+        self._pass = (0, 0)              # (B, K) of the last pass that embeds faces: what fetch_results / fetch_within are sized for
+        self._det_batch = 0              # frames of the detector run head_maps() reads back
         self._within_cap = 0             # set_within
-        self._last_shape = (0, 0)        # (B, K) of the last process / finish call (fetch_within)
+        self._yuv_keep = ()              # host planes of the last two upload_yuv_async batches
+
+    _h = None                            # (an object whose __init__ raised is still closed by __del__)
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
+        if self._h is not None and self._h.value:
             self._lib.frp_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -314,6 +322,19 @@ class Engine:
     def _chk(self, rc: int):
         if rc != 0:
             raise FrpError(rc, (self._lib.frp_last_error(self._h) or b"").decode("utf-8", "replace"))
+
+    @property
+    def resident_shape(self) -> Tuple[int, int, int]:
+        """(B, H, W) of the resident frames; zeros before the first batch"""
+        return self._resident
+
+    def _began(self, B: int, K: Optional[int] = None, heads: bool = False):
+        """a pass over B frames has been taken by the library.  K: it embeds up to K faces per frame - the (B, K) fetch_results and
+        fetch_within size their buffers for; heads: a detector run whose head maps head_maps() reads back, B frames of them"""
+        if K is not None:
+            self._pass = (B, K)
+        if heads:
+            self._det_batch = B
 
     # -- weights / gallery
     def load_weights(self, blob: bytes):
@@ -505,10 +526,16 @@ class Engine:
 
     @staticmethod
     def _alloc(B, K):
+        """zeroed result arrays of a pass over B frames with up to K faces each"""
         return dict(boxes=np.zeros((B, K, 4), np.float32), kps=np.zeros((B, K, 5, 2), np.float32),
                     scores=np.zeros((B, K), np.float32), counts=np.zeros((B,), np.int32),
                     emb=np.zeros((B, K, EMB_DIM), np.float32), match_idx=np.full((B, K), -1, np.int32),
                     match_cos=np.full((B, K), -1.0, np.float32))
+
+    @classmethod
+    def _alloc_det(cls, B, K):
+        """... of a detector-only call: the same arrays and the anchor index of every detection"""
+        return dict(cls._alloc(B, K), anchor_idx=np.full((B, K), -1, np.int32))
 
     def process_frames(self, frames: np.ndarray, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4,
                        flags: int = 0) -> dict:
@@ -517,8 +544,7 @@ class Engine:
         self._chk(self._lib.frp_process_frames(self._h, _ptr(frames), B, H, W, rs, max_faces, det_thresh, nms_iou, flags,
                                                _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]),
                                                _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
-        self._det_batch = B
-        self._last_shape = (B, max_faces)
+        self._began(B, max_faces, heads=True)
         return o
 
     def upload_frames(self, frames: np.ndarray):
@@ -532,7 +558,7 @@ class Engine:
         n = B * H * W * 3
         p = self._lib.frp_host_alloc(self._h, n)
         if not p:
-            raise FrpError(self._lib.frp_last_error(self._h).decode())
+            raise FrpError(-6, (self._lib.frp_last_error(self._h) or b"frp_host_alloc failed").decode("utf-8", "replace"))      # FRP_ERR_OOM
         buf = (C.c_uint8 * n).from_address(p)
         return np.frombuffer(buf, dtype=np.uint8).reshape(B, H, W, 3)
 
@@ -570,11 +596,11 @@ class Engine:
         second call after it returns - so that dropping a batch does not free memory under a running copy; it cannot keep a
         caller from REWRITING them."""
         self._staged, keep = self._yuv(self._lib.frp_upload_yuv_async, batch)
-        self._yuv_keep = (getattr(self, "_yuv_keep", ()) + (keep,))[-2:]
+        self._yuv_keep = (self._yuv_keep + (keep,))[-2:]
 
     def get_frames(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """the resident BGR frames as they lie -> u8 [n, H, W, 3] (frp.h: frp_get_frames; parity tests, snapshots)"""
-        B, H, W = getattr(self, "_resident", (0, 0, 0))
+        B, H, W = self._resident
         n = B - first if n is None else n
         out = np.empty((max(n, 0), H, W, 3), np.uint8)
         self._chk(self._lib.frp_get_frames(self._h, _ptr(out), out.nbytes, first, n))
@@ -582,39 +608,34 @@ class Engine:
 
     def process_resident(self, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4, flags: int = 0):
         self._chk(self._lib.frp_process_resident(self._h, max_faces, det_thresh, nms_iou, flags))
-        self._last_k = max_faces
-        self._last_shape = (self._resident[0], max_faces)
+        self._began(self._resident[0], max_faces)
 
     def synchronize(self):
         self._chk(self._lib.frp_synchronize(self._h))
 
     def fetch_results(self) -> dict:
-        B = self._resident[0]
-        o = self._alloc(B, self._last_k)
-        self._chk(self._lib.frp_fetch_results(self._h, B, self._last_k, _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]),
+        B, K = self._pass
+        o = self._alloc(B, K)
+        self._chk(self._lib.frp_fetch_results(self._h, B, K, _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]),
                                               _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
         return o
 
     # -- stages
     def detect(self, frames: np.ndarray, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4, flags: int = 0):
         frames, B, H, W, rs = self._frames(frames)
-        o = self._alloc(B, max_faces)
-        anchor = np.full((B, max_faces), -1, np.int32)
+        o = self._alloc_det(B, max_faces)
         self._chk(self._lib.frp_detect(self._h, _ptr(frames), B, H, W, rs, max_faces, det_thresh, nms_iou, flags,
-                                       _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]), _ptr(anchor)))
-        o["anchor_idx"] = anchor
-        self._det_batch = B
+                                       _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]), _ptr(o["anchor_idx"])))
+        self._began(B, heads=True)
         return o
 
     def detect_resident(self, det_hw, max_faces=10, det_thresh=0.5, nms_iou=0.4, flags=0):
         """detect on the resident frames resized to det_hw (pyramid scale); coordinates of the resized image"""
         B = self._resident[0]
-        o = self._alloc(B, max_faces)
-        anchor = np.full((B, max_faces), -1, np.int32)
+        o = self._alloc_det(B, max_faces)
         self._chk(self._lib.frp_detect_resident(self._h, B, det_hw[0], det_hw[1], max_faces, det_thresh, nms_iou, flags,
-                                                _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]), _ptr(anchor)))
-        o["anchor_idx"] = anchor
-        self._det_batch = B
+                                                _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]), _ptr(o["anchor_idx"])))
+        self._began(B, heads=True)
         return {k: o[k] for k in ("boxes", "kps", "scores", "counts", "anchor_idx")}
 
     def det_source(self) -> np.ndarray:
@@ -636,7 +657,7 @@ class Engine:
         self._chk(self._lib.frp_finish_faces(self._h, B, _ptr(boxes), _ptr(kps), _ptr(scores), _ptr(counts), max_faces, flags,
                                              _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
         o.update(boxes=boxes, kps=kps, scores=scores, counts=counts)
-        self._last_shape = (B, max_faces)
+        self._began(B, max_faces)
         return o
 
     def process_pyramid_resident(self, det_hws, per_scale: int = 64, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4,
@@ -646,8 +667,7 @@ class Engine:
         full-resolution frames.  Asynchronous like process_resident: fetch_results() waits for it and returns frame-pixel results."""
         hw = np.ascontiguousarray(det_hws, dtype=np.int32).reshape(-1, 2)
         self._chk(self._lib.frp_process_pyramid(self._h, hw.shape[0], _ptr(hw), per_scale, max_faces, det_thresh, nms_iou, flags))
-        self._last_k = max_faces
-        self._last_shape = (self._resident[0], max_faces)
+        self._began(self._resident[0], max_faces)
 
     def pyramid_merge(self, det_hws, frame_hw, boxes, kps, scores, counts, max_faces: int, nms_iou: float = 0.4):
         """the cross-scale merge launch alone (frp.h: frp_debug_pyramid_merge) on host detections, scale-major: boxes [S, B, P, 4],
@@ -676,14 +696,12 @@ class Engine:
         host mid-pass, FLAG_WITHIN honoured) instead of one blocking call per scale and the merge here; the same bits."""
         from . import pyramid
         frames, B, H, W, _ = self._frames(frames)
-        if on_device:
-            with self._seq:
-                self.upload_frames(frames)
+        with self._seq:
+            self.upload_frames(frames)
+            if on_device:
                 self.process_pyramid_resident([pyramid.scaled_size(H, W, s) for s in scales], per_scale=per_scale, max_faces=max_faces,
                                               det_thresh=det_thresh, nms_iou=nms_iou, flags=flags)
                 return self.fetch_results()
-        with self._seq:
-            self.upload_frames(frames)
             per = []
             for s in scales:
                 hw = pyramid.scaled_size(H, W, s)
@@ -722,12 +740,10 @@ class Engine:
     def decode_heads(self, heads, canvas_hw, max_faces=10, det_thresh=0.5, nms_iou=0.4, flags=0):
         hs = [np.ascontiguousarray(x, dtype=np.float16) for x in heads]
         B = hs[0].shape[0]
-        o = self._alloc(B, max_faces)
-        anchor = np.full((B, max_faces), -1, np.int32)
+        o = self._alloc_det(B, max_faces)
         self._chk(self._lib.frp_decode_heads(self._h, _ptr(hs[0]), _ptr(hs[1]), _ptr(hs[2]), B, canvas_hw[0], canvas_hw[1],
                                              max_faces, det_thresh, nms_iou, flags, _ptr(o["boxes"]), _ptr(o["kps"]),
-                                             _ptr(o["scores"]), _ptr(o["counts"]), _ptr(anchor)))
-        o["anchor_idx"] = anchor
+                                             _ptr(o["scores"]), _ptr(o["counts"]), _ptr(o["anchor_idx"])))
         return o
 
     def align(self, frame: np.ndarray, kps: np.ndarray, flags: int = 0) -> np.ndarray:
@@ -812,7 +828,7 @@ class Engine:
     def fetch_within(self):
         """hit lists of the last pass that ran with FLAG_WITHIN (process_frames / process_resident / process_pyramid_resident / finish_faces)
         -> (idx [B, K, cap], cos [B, K, cap], n_hits [B, K]); slots without a face have n_hits 0"""
-        B, K = self._last_shape
+        B, K = self._pass
         cap = self._within_cap
         idx = np.empty((B, K, cap), np.int32)
         cos = np.empty((B, K, cap), np.float32)

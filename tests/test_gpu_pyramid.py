@@ -189,9 +189,10 @@ def test_refusals_leave_the_handle_working(fresh_engine):
     _refused(lambda: eng.process_pyramid_resident(hws, max_faces=K, flags=native.FLAG_WITHIN))   # frp_set_within never called
     # none of them overwrote the pass queued before them
     _same(eng.fetch_results(), want)
-    eng._last_k = K // 2                                                                      # fetch_results with another K
+    eng._pass = (eng._pass[0], K // 2)                                                        # fetch_results with another K
     _refused(eng.fetch_results)
-    eng._last_k = K
+    eng._pass = (eng._pass[0], K)
+    _same(eng.fetch_results(), want)
     # the debug entry: a count above per_scale, a NaN score on a live row (a dead row may hold anything)
     case = next(c for c in CASES if c["name"] == "exact_iou")
     args = lambda **kw: [kw.get(k, case[k]) for k in ("boxes", "kps", "scores", "counts")] + [case["K"], case["nms_iou"]]

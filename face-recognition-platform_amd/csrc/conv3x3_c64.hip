@@ -424,78 +424,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(ConvParams p_in) {
     wait_vmcnt<0>();
 }
 
-static int c64_variant(const ConvParams& p);
-// tile width for a map: the geometry that wastes fewer tile pixels (32 x 8 on a tie: its halo is the smaller share of the DMA)
-static int c64_tile_width(const ConvParams& p, double* fill = nullptr) {
-    double best = 0;
-    int tw_best = 32;
-    for (int tw : {32, 16}) {
-        const int th = 256 / tw;
-        const double f = (double)p.H * p.W / ((double)((p.H + th - 1) / th * th) * (double)((p.W + tw - 1) / tw * tw));
-        if (f > best + 1e-9) { best = f; tw_best = tw; }
-    }
-    if (fill) *fill = best;
-    return tw_best;
-}
-static long c64_tiles(const ConvParams& p, int tw) {
-    const int th = 256 / tw;
-    return (long)p.N * ((p.H + th - 1) / th) * ((p.W + tw - 1) / tw);
-}
-// Shapes the kernel covers (`p` with launch_conv()'s derived fields) - and where it pays: at least two rounds of tiles.
-bool conv3x3_c64_eligible(const ConvParams& p) {
-    if (p.KS != 3 || p.stride != 1 || p.Cin != 64 || p.Cout != 64 || p.ksplit != 1 || p.x2 || p.out2) return false;
-    if (p.flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_F8 | FRP_FLAG_OUT_FP8 | FRP_FLAG_RES_UP2)) return false;
-    if (p.Ho != p.H || p.Wo != p.W) return false;
-    if ((long)p.N * p.H * p.W * 128 >= 0x7f000000L) return false;                  // signed 32-bit byte offsets (+ a patch of slack)
-    if (!c64_variant(p)) return false;
-    if (p.act == FRP_ACT_PRELU && !p.slope) return false;
-    if (p.stem_x && (c64_variant(p) != 3 || !p.stem_w || !p.stem_bias || !p.stem_slope || !p.stem_out || (long)p.N * p.H * p.W * 16 >= 0x7f000000L))
-        return false;
-    double fill = 0;
-    const int tw = c64_tile_width(p, &fill);
-    if (c64_tiles(p, tw) < 2L * (p.n_cu > 0 ? p.n_cu : 256)) return false;
-    // where it pays (tools/c64_probe.py, profiles/r5/c64_probe.txt): x1.11 / x1.14 over the row-patch kernel on maps whose tiles are all
-    // full (the detector's 272 x 480 in 32 x 8 tiles, the embedder's 112 x 112 in 16 x 16 tiles); x0.99-1.03 on its 56 x 56 maps, where
-    // either geometry leaves an eighth of the tile pixels empty - those stay on the row-patch kernel (CONV_DBG_C64_ALL takes every
-    // eligible shape: the parity tests)
-    return (p.dbg & CONV_DBG_C64_ALL) || fill >= 0.95;
-}
-
-template <int ACT, bool RES, bool BORDER, int TW, bool STEM = false>
-static hipError_t launch_c64_geo(const ConvParams& p, hipStream_t stream) {
-    static bool attr_set[64] = {};
-    auto kern = conv3x3_c64_kernel<ACT, RES, BORDER, TW, STEM>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
-    const long tiles = c64_tiles(p, TW);
-    if (tiles <= 0 || tiles > 0x7fffffffL) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(tiles < ncu ? tiles : ncu);       // persistent: one workgroup per CU
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), C64_LDS, stream, p);
-    return hipGetLastError();
-}
-
-// maps on which the launch of the embedder's first 64 -> 64 conv also computes the stem in front of it (net_program.cpp: run_net): where the
-// kernel is routed anyway
-bool conv3x3_c64_fuses_stem(int N, int H, int W, int n_cu) {
-    ConvParams q{};
-    q.N = N; q.H = H; q.W = W; q.n_cu = n_cu;
-    double fill = 0;
-    const int tw = c64_tile_width(q, &fill);
-    return (long)N * H * W * 128 < 0x7f000000L && c64_tiles(q, tw) >= 2L * (n_cu > 0 ? n_cu : 256) && fill >= 0.95;
-}
-
-template <int ACT, bool RES, bool BORDER>
-static hipError_t launch_c64_cfg(const ConvParams& p, hipStream_t stream) {
-    return c64_tile_width(p) == 16 ? launch_c64_geo<ACT, RES, BORDER, 16>(p, stream) : launch_c64_geo<ACT, RES, BORDER, 32>(p, stream);
-}
-
 // the four (activation, residual, border bias) combinations the two networks have on these layers
 static int c64_variant(const ConvParams& p) {
     const bool res = p.res != nullptr, border = (p.flags & FRP_FLAG_BORDER_BIAS) != 0;
@@ -504,18 +432,70 @@ static int c64_variant(const ConvParams& p) {
     if (p.act == FRP_ACT_NONE && res && !border) return 4;             // IResNet conv2
     return 0;
 }
+// what a launch on p's map looks like: the kernel variant (0: none), and the tile geometry that wastes fewer tile pixels (32 x 8 on a
+// tie: its halo is the smaller share of the DMA) with its tile count and the share of real pixels in its tiles
+static C64Plan c64_plan(const ConvParams& p) {
+    C64Plan g{c64_variant(p), 32, 0, 0.};
+    for (int tw : {32, 16}) {
+        const int th = 256 / tw;
+        const double f = (double)p.H * p.W / ((double)((p.H + th - 1) / th * th) * (double)((p.W + tw - 1) / tw * tw));
+        if (f > g.fill + 1e-9) { g.fill = f; g.tile_w = tw; }
+    }
+    const int th = 256 / g.tile_w;
+    g.tiles = (long)p.N * ((p.H + th - 1) / th) * ((p.W + g.tile_w - 1) / g.tile_w);
+    return g;
+}
+// Where the kernel is in reach (signed 32-bit byte offsets + a patch of slack) and pays: at least two rounds of tiles (p.n_cu as the engine
+// set it, 256 for a stand-alone call: conv_launch.cpp, conv_derive), and (tools/c64_probe.py, profiles/r5/c64_probe.txt) x1.11 / x1.14 over
+// the row-patch kernel on maps whose tiles are all full (the detector's 272 x 480 in 32 x 8 tiles, the embedder's 112 x 112 in 16 x 16
+// tiles); x0.99-1.03 on its 56 x 56 maps, where either geometry leaves an eighth of the tile pixels empty - those stay on the row-patch
+// kernel (`all`, CONV_DBG_C64_ALL, takes every eligible shape: the parity tests)
+static bool c64_pays(const ConvParams& p, const C64Plan& g, bool all) {
+    if ((long)p.N * p.H * p.W * 128 >= 0x7f000000L) return false;
+    return g.tiles >= 2L * (p.n_cu > 0 ? p.n_cu : 256) && (all || g.fill >= 0.95);
+}
+// Shapes the kernel takes (`p` with conv_derive()'s fields); *plan: what its launcher needs
+bool conv3x3_c64_eligible(const ConvParams& p, C64Plan* plan) {
+    if (p.KS != 3 || p.stride != 1 || p.Cin != 64 || p.Cout != 64 || p.ksplit != 1 || p.x2 || p.out2) return false;
+    if (p.flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_F8 | FRP_FLAG_OUT_FP8 | FRP_FLAG_RES_UP2)) return false;
+    if (p.Ho != p.H || p.Wo != p.W) return false;
+    *plan = c64_plan(p);
+    if (!plan->variant) return false;
+    if (p.act == FRP_ACT_PRELU && !p.slope) return false;
+    if (p.stem_x && (plan->variant != 3 || !p.stem_w || !p.stem_bias || !p.stem_slope || !p.stem_out || (long)p.N * p.H * p.W * 16 >= 0x7f000000L))
+        return false;
+    return c64_pays(p, *plan, (p.dbg & CONV_DBG_C64_ALL) != 0);
+}
+// maps on which the launch of the embedder's first 64 -> 64 conv also computes the stem in front of it (net_program.cpp: run_net): where the
+// kernel is routed anyway, whatever CONV_DBG_C64_ALL says
+bool conv3x3_c64_fuses_stem(int N, int H, int W, int n_cu) {
+    ConvParams q{};
+    q.N = N; q.H = H; q.W = W; q.n_cu = n_cu;
+    return c64_pays(q, c64_plan(q), false);
+}
 
-hipError_t launch_conv3x3_c64(const ConvParams& p, hipStream_t stream) {
-    if (!conv3x3_c64_eligible(p)) return hipErrorInvalidValue;
-    switch (c64_variant(p)) {
-        case 1: return launch_c64_cfg<FRP_ACT_RELU, false, false>(p, stream);
-        case 2: return launch_c64_cfg<FRP_ACT_RELU, true, false>(p, stream);
+template <int ACT, bool RES, bool BORDER, int TW, bool STEM = false>
+static hipError_t launch_c64_geo(const ConvParams& p0, long tiles, hipStream_t stream) {
+    ConvParams p = p0;
+    // persistent: one workgroup per CU
+    return conv_launch<conv3x3_c64_kernel<ACT, RES, BORDER, TW, STEM>>(C64_LDS, C64_LDS, tiles, 1, 512, p, stream);
+}
+template <int ACT, bool RES, bool BORDER>
+static hipError_t launch_c64_cfg(const ConvParams& p, const C64Plan& g, hipStream_t stream) {
+    return g.tile_w == 16 ? launch_c64_geo<ACT, RES, BORDER, 16>(p, g.tiles, stream) : launch_c64_geo<ACT, RES, BORDER, 32>(p, g.tiles, stream);
+}
+
+// `g`: conv3x3_c64_eligible()'s plan of `p`
+hipError_t launch_conv3x3_c64(const ConvParams& p, const C64Plan& g, hipStream_t stream) {
+    switch (g.variant) {
+        case 1: return launch_c64_cfg<FRP_ACT_RELU, false, false>(p, g, stream);
+        case 2: return launch_c64_cfg<FRP_ACT_RELU, true, false>(p, g, stream);
         case 3:
             if (p.stem_x)
-                return c64_tile_width(p) == 16 ? launch_c64_geo<FRP_ACT_PRELU, false, true, 16, true>(p, stream)
-                                               : launch_c64_geo<FRP_ACT_PRELU, false, true, 32, true>(p, stream);
-            return launch_c64_cfg<FRP_ACT_PRELU, false, true>(p, stream);
-        case 4: return launch_c64_cfg<FRP_ACT_NONE, true, false>(p, stream);
+                return g.tile_w == 16 ? launch_c64_geo<FRP_ACT_PRELU, false, true, 16, true>(p, g.tiles, stream)
+                                      : launch_c64_geo<FRP_ACT_PRELU, false, true, 32, true>(p, g.tiles, stream);
+            return launch_c64_cfg<FRP_ACT_PRELU, false, true>(p, g, stream);
+        case 4: return launch_c64_cfg<FRP_ACT_NONE, true, false>(p, g, stream);
         default: return hipErrorInvalidValue;
     }
 }

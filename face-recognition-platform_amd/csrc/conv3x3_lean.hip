@@ -454,35 +454,12 @@ static hipError_t launch_lean_cfg(const ConvParams& p0, hipStream_t stream) {
     p.n_ptiles = (p.M + TP - 1) / TP;
     p.n_ctiles = (p.Cout + TC - 1) / TC;
     const int lds = (TP == 512 ? 2 : 3) * (TP + 8) * 128 + 3 * TC * 128 + 256 + 11 * TC * 4;
-    static bool attr_set[64] = {};
-    auto kern = conv3x3_lean_kernel<TC, WP, WC, F8, TP, TCU>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const long ntiles = (long)p.n_ptiles * p.n_ctiles;
-    if (ntiles <= 0 || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
-    const long slots = (long)ncu * (TP == 128 ? 2 : 1);                // persistent: one workgroup per CU (quarter tiles: two)
-    unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
-    p.n_workers = 0;
-    // a launch of at most 128 tiles (a call of up to ~20 faces: where the latency of ONE call is what counts) leaves three quarters
-    // of the slots empty: 64 more workgroups warm the L2s for the next launch.  Larger quarter-tile launches (config 4's ~36 faces
-    // on two lanes) keep their spare CUs for the other lane's kernels: there the prefetchers cost 4 % of the throughput.
-    if (TP == 128 && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots) {
-        p.n_workers = (int)grid;
-        grid += CONV_PF_WGS;
-    }
-    if (grid > 256) p.stamps = nullptr;                                // (the diagnostic stamp buffer holds 256 workgroups)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, p);
-    return hipGetLastError();
+    // persistent: one workgroup per CU (quarter tiles: two)
+    return conv_launch<conv3x3_lean_kernel<TC, WP, WC, F8, TP, TCU>>(lds, lds, (long)p.n_ptiles * p.n_ctiles, TP == 128 ? 2 : 1, 512, p, stream,
+                                                                      conv_direct_grid<TP == 128>);
 }
 
-// Shapes the row-patch kernel covers; `p` carries the derived fields of launch_conv().
+// Shapes the row-patch kernel covers; `p` carries the derived fields of conv_derive().
 bool conv3x3_rows_eligible(const ConvParams& p) {
     if (p.KS != 3 || p.stride != 1 || (p.Cin & 63) || p.ksplit != 1) return false;
     if (p.Ho != p.H || p.Wo != p.W) return false;
@@ -491,22 +468,16 @@ bool conv3x3_rows_eligible(const ConvParams& p) {
     return reach < 0x7fffffffL;
 }
 
-hipError_t launch_conv3x3_lean(const ConvParams& p, hipStream_t stream) {
-    if (!conv3x3_rows_eligible(p)) return hipErrorInvalidValue;
-    if (p.flags & FRP_FLAG_F8) {                   // fp8 operands: whole 128-channel rows, 128-cout tiles only
-        if ((p.Cin & 127) || !p.wscale) return hipErrorInvalidValue;
-        return launch_lean_cfg<128, 4, 2, true, 256>(p, stream);
-    }
-    {                                              // few tiles (small maps, few faces): quarter tiles, two workgroups per CU
-        int ncu = p.n_cu;                          // (set by the engine; standalone callers: ask the runtime)
-        if (ncu <= 0) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-            ncu = device_cu_count(dev);
-        }
-        const long def_tiles = p.Cout > 64 ? (long)((p.M + 255) / 256) * ((p.Cout + 127) / 128) : (long)((p.M + 511) / 512);
-        if (conv_small_m(p, def_tiles, ncu)) return launch_lean_cfg<64, 4, 2, false, 128>(p, stream);
-    }
+// tiles of the default tiling (256 x 128, 512 x 64 up to 64 couts): what conv_small_m goes by for this kernel
+long conv3x3_lean_default_tiles(const ConvParams& p) {
+    return p.Cout > 64 ? (long)((p.M + 255) / 256) * ((p.Cout + 127) / 128) : (long)((p.M + 511) / 512);
+}
+
+// `p`: a shape conv_pick() found eligible (fp8 operands: whole 128-channel rows, with their scales); few: quarter tiles, two
+// workgroups per CU (few tiles: small maps, few faces)
+hipError_t launch_conv3x3_lean(const ConvParams& p, bool few, hipStream_t stream) {
+    if (p.flags & FRP_FLAG_F8) return launch_lean_cfg<128, 4, 2, true, 256>(p, stream);   // 128-cout tiles only
+    if (few) return launch_lean_cfg<64, 4, 2, false, 128>(p, stream);
     if (p.Cout > 64) return launch_lean_cfg<128, 4, 2, false, 256>(p, stream);
     if (p.dbg & CONV_DBG_LEAN_TILE256) return launch_lean_cfg<64, 8, 1, false, 256>(p, stream);                      // (A/B)
     if (p.Cout <= 32 && !(p.dbg & CONV_DBG_LEAN_ALL_ROWS)) return launch_lean_cfg<64, 8, 1, false, 512, 32>(p, stream);   // head outputs

@@ -534,27 +534,13 @@ static hipError_t launch_rows_cfg(const ConvParams& p0, hipStream_t stream) {
     p.n_ptiles = (p.M + 255) / 256;
     p.n_ctiles = (p.Cout + TC - 1) / TC;
     const int lds = 3 * 264 * 128 + 3 * TC * 128 + 256 + 10 * TC * 4;
-    static bool attr_set[64] = {};
-    auto kern = conv3x3_rows_kernel<TC, WP, WC, PF, ABL>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const long ntiles = (long)p.n_ptiles * p.n_ctiles;
-    if (ntiles <= 0 || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
-    const unsigned grid = (unsigned)(ntiles < ncu ? ntiles : ncu);     // persistent: one workgroup per CU
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, p);
-    return hipGetLastError();
+    // persistent: one workgroup per CU
+    return conv_launch<conv3x3_rows_kernel<TC, WP, WC, PF, ABL>>(lds, lds, (long)p.n_ptiles * p.n_ctiles, 1, 512, p, stream);
 }
 
-hipError_t launch_conv3x3_rows(const ConvParams& p, hipStream_t stream) {
-    if (!conv3x3_rows_eligible(p)) return hipErrorInvalidValue;
-    if (p.out2) return launch_conv3x3_lean(p, stream);   // the fp8-copy epilogue lives in the static-loop generation only
+// `p`: a shape conv_pick() found eligible (conv3x3_rows_eligible); few: the lean kernel's tile class
+hipError_t launch_conv3x3_rows(const ConvParams& p, bool few, hipStream_t stream) {
+    if (p.out2) return launch_conv3x3_lean(p, few, stream);   // the fp8-copy epilogue lives in the static-loop generation only
     // timing-only ablations of the 128-cout kernel (wrong results; conv_bench only)
     if (p.Cout > 64) switch (conv_dbg_field(p.dbg, CONV_DBG_ROWS_ABLATION)) {
         case 1: return launch_rows_cfg<128, 4, 2, false, 1>(p, stream);
@@ -578,7 +564,7 @@ hipError_t launch_conv3x3_rows(const ConvParams& p, hipStream_t stream) {
         if (p.Cout > 64) return launch_rows_cfg<128, 4, 2, true>(p, stream);
         return launch_rows_cfg<64, 8, 1, true>(p, stream);
     }
-    return launch_conv3x3_lean(p, stream);       // second generation: static k-loop (conv3x3_lean.hip)
+    return launch_conv3x3_lean(p, few, stream);  // second generation: static k-loop (conv3x3_lean.hip)
 }
 
 }  // namespace frp

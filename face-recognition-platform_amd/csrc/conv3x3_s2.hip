@@ -353,7 +353,7 @@ static int log2_exact(int v) {
     return (1 << s) == v ? s : -1;
 }
 
-// Shapes the kernel covers (`p` with launch_conv()'s derived fields: M, Ho, Wo, Ktot incl. the x2 segment, x_bytes, w_bytes, x2_bytes).
+// Shapes the kernel covers (`p` with conv_derive()'s fields: M, Ho, Wo, Ktot incl. the x2 segment, x_bytes, w_bytes, x2_bytes).
 bool conv3x3_s2_eligible(const ConvParams& p) {
     if (p.KS != 3 || p.stride != 2 || p.ksplit != 1 || p.out2 || p.res) return false;
     if (p.flags & (FRP_FLAG_BORDER_BIAS | FRP_FLAG_OUT_F32 | FRP_FLAG_F8 | FRP_FLAG_OUT_FP8 | FRP_FLAG_RES_UP2 | FRP_FLAG_FLATTEN)) return false;
@@ -370,30 +370,16 @@ bool conv3x3_s2_eligible(const ConvParams& p) {
 template <int ACT>
 static hipError_t launch_s2_cfg(const ConvParams& p0, hipStream_t stream) {
     ConvParams p = p0;
-    static bool attr_set[64] = {};
-    auto kern = conv3x3_s2_kernel<ACT>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S2_LDS);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
     p.n_ptiles = (p.M + S2_TP - 1) / S2_TP;
     p.n_ctiles = p.Cout / S2_CT;
     p.cin_shift = log2_exact(p.Cin) + 1;                       // this kernel: log2 of a pixel's bytes in x ...
     p.x2_shift = p.x2 ? log2_exact(p.Cin2) + 1 : 0;            // ... and in x2
-    const long tiles = (long)p.n_ptiles * p.n_ctiles;
-    if (tiles <= 0 || tiles > 0x7fffffffL) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(tiles < ncu ? tiles : ncu);       // persistent: one workgroup per CU
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), S2_LDS, stream, p);
-    return hipGetLastError();
+    // persistent: one workgroup per CU
+    return conv_launch<conv3x3_s2_kernel<ACT>>(S2_LDS, S2_LDS, (long)p.n_ptiles * p.n_ctiles, 1, 512, p, stream);
 }
 
+// `p`: a shape conv_pick() found eligible (conv3x3_s2_eligible)
 hipError_t launch_conv3x3_s2(const ConvParams& p, hipStream_t stream) {
-    if (!conv3x3_s2_eligible(p)) return hipErrorInvalidValue;
     return p.act == FRP_ACT_RELU ? launch_s2_cfg<FRP_ACT_RELU>(p, stream) : launch_s2_cfg<FRP_ACT_NONE>(p, stream);
 }
 

@@ -1049,11 +1049,10 @@ static int wino_form(const ConvParams& p) {
     return wino_2d_pays(p) ? 2 : 0;
 }
 
-// Shapes the Winograd kernel covers; `p` carries the derived fields of launch_conv().
-bool conv3x3_wino_eligible(const ConvParams& p) {
-    if (!wino_form(p)) return false;
+// The form (wino_form) in which the Winograd kernel takes a launch, 0: not at all; `p` carries the derived fields of conv_derive().
+int conv3x3_wino_form(const ConvParams& p) {
     const long reach = ((long)p.M + 2L * p.W + 600) * p.Cin * 2;       // signed 32-bit patch offsets
-    return reach < 0x7fffffffL;
+    return reach < 0x7fffffffL ? wino_form(p) : 0;
 }
 
 // The same answer in the shipped and in the lab build: frp_load_weights builds Winograd images - and run_net routes layers to
@@ -1066,6 +1065,15 @@ bool conv3x3_wino_lab_shape_ok(int W, int Cin, int ksize, int stride) {      // 
     return ksize == 3 && stride == 1 && !(Cin & 63) && !(W & 1) && W >= 2;
 }
 #endif
+// a layer geometry for which a stand-alone call may hand launch_conv() a weight image (kernel_api.cpp): the flattened tiles, the 2-D
+// tiles where they pay, in the lab build whatever its dbg bits force
+bool conv3x3_wino_call_ok(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int n_cu, bool has_res, int dbg) {
+#ifdef FRP_LAB
+    if ((dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride)) return true;
+#endif
+    (void)dbg;
+    return conv3x3_wino_shape_ok(W, Cin, ksize, stride) || (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, n_cu, has_res));
+}
 
 // bytes of the transformed weight image of a layer (the `w` operand of the Winograd kernel)
 size_t conv3x3_wino_image_bytes(int Cin, int Cout) {
@@ -1080,22 +1088,9 @@ static hipError_t launch_wino_cfg(const ConvParams& p0, hipStream_t stream) {
     const size_t img = conv3x3_wino_image_bytes(p.Cin, p.Cout);
     if (img >= 0x7fffffffUL) return hipErrorInvalidValue;
     p.w_bytes = (unsigned)img;
-    const int lds = ROWP ? wino_rowp_lds_bytes() : wino_lds_bytes(p.W);
-    static int attr_lds[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (attr_lds[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>((conv3x3_wino_kernel<NW, ABL, ROWP>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_lds[dev] = 160 * 1024;
-    }
-    const long ntiles = (long)p.n_ptiles * p.n_ctiles;
-    if (ntiles <= 0 || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
-    const unsigned grid = (unsigned)(ntiles < ncu ? ntiles : ncu);     // persistent: one workgroup per CU
-    hipLaunchKernelGGL((conv3x3_wino_kernel<NW, ABL, ROWP>), dim3(grid), dim3(NW * 64), lds, stream, p);
-    return hipGetLastError();
+    // persistent: one workgroup per CU
+    return conv_launch<conv3x3_wino_kernel<NW, ABL, ROWP>>(160 * 1024, ROWP ? wino_rowp_lds_bytes() : wino_lds_bytes(p.W), (long)p.n_ptiles * p.n_ctiles, 1,
+                                                            NW * 64, p, stream);
 }
 
 template <int VAR>
@@ -1109,27 +1104,12 @@ static hipError_t launch_wino2_cfg(const ConvParams& p0, hipStream_t stream) {
     p.w_bytes = (unsigned)img;
     if (T2D && (p.n_dev || (long)p.N * p.H * p.W != (long)p.M)) return hipErrorInvalidValue;
     if (!T2D && wino_half_rows(p.W) != WN2_PPW * 32) return hipErrorInvalidValue;          // 5 patch pieces per wave
-    const int lds = wino_lds_bytes(T2D ? 14 : p.W);
-    static int attr_lds[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (attr_lds[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>((conv3x3_wino2_kernel<VAR>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_lds[dev] = 160 * 1024;
-    }
-    const long ntiles = (long)p.n_ptiles * p.n_ctiles;
-    if (ntiles <= 0 || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
-    const unsigned grid = (unsigned)(ntiles < ncu ? ntiles : ncu);     // persistent: one workgroup per CU
-    hipLaunchKernelGGL((conv3x3_wino2_kernel<VAR>), dim3(grid), dim3(512), lds, stream, p);
-    return hipGetLastError();
+    // persistent: one workgroup per CU
+    return conv_launch<conv3x3_wino2_kernel<VAR>>(160 * 1024, wino_lds_bytes(T2D ? 14 : p.W), (long)p.n_ptiles * p.n_ctiles, 1, 512, p, stream);
 }
 
-hipError_t launch_conv3x3_wino(const ConvParams& p, hipStream_t stream) {
-    const int form = wino_form(p);
-    if (!form || !conv3x3_wino_eligible(p)) return hipErrorInvalidValue;
+// `p`: a launch conv_pick() gave this family, p.w = its weight image; form: its conv3x3_wino_form()
+hipError_t launch_conv3x3_wino(const ConvParams& p, int form, hipStream_t stream) {
     if (form == 2) return launch_wino2_cfg<32>(p, stream);            // 2-D tiles
 #ifdef FRP_LAB   // CONV_DBG_WINO_KLOOP_GEN1: the first generation of the k-loop (compiler-scheduled; A/B partner of the hand-ordered one)
     if (!(p.dbg & (CONV_DBG_WINO_KLOOP_GEN1 | CONV_DBG_WINO_ONE_WAVE | CONV_DBG_WINO_ROW_PATCH)) && wino_super_patch(p.W))

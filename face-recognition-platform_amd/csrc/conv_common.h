@@ -1,4 +1,4 @@
-// Device helpers shared by the MFMA convolution kernels (conv_mfma.hip, conv3x3_rows.hip).
+// Device helpers shared by the MFMA convolution kernels, and the host side of their launch (conv_launch: every family's launcher ends there).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,6 +61,12 @@ static int device_cu_count(int dev) {
     }
     return n_cu[dev];
 }
+// the device the calling thread launches on, and its CU count
+static inline hipError_t conv_device(int* dev, int* ncu) {
+    if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= 64) return hipErrorInvalidDevice;
+    *ncu = device_cu_count(*dev);
+    return *ncu > 0 ? hipSuccess : hipErrorInvalidDevice;
+}
 
 // Small-M rule shared by the conv launchers: quarter tiles (128 pixels x 64 couts, two workgroups per CU) when the default
 // tiling would leave at least half of the CUs without a tile - small pyramid scales, a handful of faces, single images.
@@ -90,6 +96,43 @@ __device__ __forceinline__ void conv_prefetch_weights(const ConvParams& p, int k
         acc ^= v.x ^ v.y ^ v.z ^ v.w;
     }
     if (acc == 0x9e3779b9u && p.stamps) p.stamps[0] = acc;          // (keeps the loads; never true in practice, harmless if it is)
+}
+// The grid of the two direct families (the generic and the lean kernel; QUARTER: their 128-pixel tiles, two workgroups per CU).
+template <bool QUARTER>
+static void conv_direct_grid(ConvParams& p, unsigned& grid, long slots) {
+    p.n_workers = 0;
+    // a launch of at most 128 tiles (a call of up to ~20 faces: where the latency of ONE call is what counts) leaves three quarters
+    // of the slots empty: 64 more workgroups warm the L2s for the next launch.  Larger quarter-tile launches (config 4's ~36 faces
+    // on two lanes) keep their spare CUs for the other lane's kernels: there the prefetchers cost 4 % of the throughput.
+    if (QUARTER && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots) {
+        p.n_workers = (int)grid;
+        grid += CONV_PF_WGS;
+    }
+    if (grid > 256) p.stamps = nullptr;                                // (the diagnostic stamp buffer holds 256 workgroups)
+}
+
+// The launch of every conv kernel family: a persistent grid of `per_cu` workgroups per CU, or one per tile where there are fewer.
+// Kern's dynamic LDS limit is raised to lds_attr once per device (per instantiation, so per kernel: whenever a launch needs more
+// than was asked for so far - the Winograd launchers ask for the 160 KiB of a CU at once, the others for their one size);
+// `grid_rule` (conv_direct_grid) may add workgroups and edit the parameters once the grid is known.
+template <auto Kern>
+static hipError_t conv_launch(int lds_attr, int lds, long ntiles, int per_cu, int block, ConvParams& p, hipStream_t stream,
+                              void (*grid_rule)(ConvParams&, unsigned&, long) = nullptr) {
+    static int attr_lds[64] = {};
+    int dev = 0, ncu = 0;
+    hipError_t e = conv_device(&dev, &ncu);
+    if (e != hipSuccess) return e;
+    if (attr_lds[dev] < lds) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr);
+        if (e != hipSuccess) return e;
+        attr_lds[dev] = lds_attr;
+    }
+    if (ntiles <= 0 || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
+    const long slots = (long)ncu * per_cu;
+    unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
+    if (grid_rule) grid_rule(p, grid, slots);
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, stream, p);
+    return hipGetLastError();
 }
 
 // q = m / d, r = m % d for 0 <= m < 2^24 via a float reciprocal and one correction step

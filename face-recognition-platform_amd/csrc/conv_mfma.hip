@@ -434,129 +434,27 @@ static hipError_t launch_cfg(const ConvParams& p0, hipStream_t stream) {
     p.n_ptiles = (p.M + TP - 1) / TP;
     p.n_ctiles = (p.Cout + TC - 1) / TC;
     const int lds = NS * (TP + TC) * 128 + 10 * TC * 4;   // operand ring + epilogue parameter cache
-    static bool attr_set[64] = {};
-    auto kern = conv_mfma_kernel<TP, TC, WP, WC, NS, NW, SMALL>;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const int ncu = device_cu_count(dev);
-    if (ncu <= 0) return hipErrorInvalidDevice;
+    int dev = 0, ncu = 0;
+    hipError_t e = conv_device(&dev, &ncu);
+    if (e != hipSuccess) return e;
     // (device-side split choice: the grid is sized for the largest split, that of a single image)
     const int ks_grid = p.ksplit < 0 ? conv_pick_ksplit(p.Ho * p.Wo, p.Cout, p.Ktot, p.flags, p.res != nullptr, ncu) : p.ksplit;
-    const long ntiles = (long)p.n_ptiles * p.n_ctiles * ks_grid;
-    if (ntiles <= 0 || ntiles > 0x7fffffffL) return hipErrorInvalidValue;
-    p.n_cu = ncu;
+    p.n_cu = ncu;                                          // (the kernel's own split choice goes by the device's count: conv_launch.cpp, conv_derive)
     // persistent: as many workgroups per CU as the LDS ring allows (1 or 2), each walks a
     // contiguous range of tiles
-    const long slots = (long)ncu * (lds <= 80 * 1024 ? 2 : 1);
-    unsigned grid = (unsigned)(ntiles < slots ? ntiles : slots);
-    p.n_workers = 0;
-    // a launch of at most 128 tiles (a call of up to ~20 faces: where the latency of ONE call is what counts) leaves three quarters
-    // of the slots empty: 64 more workgroups warm the L2s for the next launch.  Larger quarter-tile launches (config 4's ~36 faces
-    // on two lanes) keep their spare CUs for the other lane's kernels: there the prefetchers cost 4 % of the throughput.
-    if (TP == 128 && p.pf_ptr && p.pf_bytes >= 4096 && grid <= 128 && (long)grid + CONV_PF_WGS <= slots) {
-        p.n_workers = (int)grid;
-        grid += CONV_PF_WGS;
-    }
-    if (grid > 256) p.stamps = nullptr;                                // (the diagnostic stamp buffer holds 256 workgroups)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, stream, p);
-    return hipGetLastError();
+    return conv_launch<conv_mfma_kernel<TP, TC, WP, WC, NS, NW, SMALL>>(lds, lds, (long)p.n_ptiles * p.n_ctiles * ks_grid, lds <= 80 * 1024 ? 2 : 1,
+                                                                         NW * 64, p, stream, conv_direct_grid<TP == 128>);
 }
 
-// Host-side shape checks + tile selection.  Returns hipErrorInvalidValue on a shape the
-// kernel does not cover instead of launching (a faulting kernel can take the node down).
-hipError_t launch_conv(const ConvParams& in, hipStream_t stream) {
-    ConvParams p = in;
-    if (!(p.KS == 1 || p.KS == 3) || !(p.stride == 1 || p.stride == 2)) return hipErrorInvalidValue;
-    if (p.Cin < 8 || (p.Cin & 7) || (p.Cout & 7) || p.N <= 0 || p.H <= 0 || p.W <= 0) return hipErrorInvalidValue;
-    p.pad = p.KS / 2;
-    p.Ho = (p.H + 2 * p.pad - p.KS) / p.stride + 1;
-    p.Wo = (p.W + 2 * p.pad - p.KS) / p.stride + 1;
-    const long M = (long)p.N * p.Ho * p.Wo;
-    if (M <= 0 || M > 0x7fffffffL) return hipErrorInvalidValue;
-    p.M = (int)M;
-    p.Ktot = p.KS * p.KS * p.Cin;
-    p.x2_bytes = 0;
-    p.x2_shift = 0;
-    if (p.x2) {                                  // K-concat: generic kernel, whole channel blocks, plain fp16 epilogue input
-        if (p.KS != 3 || (p.Cin & 63) || p.Cin2 <= 0 || (p.Cin2 & 63) || !(p.Cin == p.Cin2 || p.Cin == 2 * p.Cin2) || p.ksplit > 1 ||
-            (p.flags & (FRP_FLAG_F8 | FRP_FLAG_BORDER_BIAS)) || p.wino_w)
-            return hipErrorInvalidValue;
-        const long x2b = (long)p.N * p.H * p.W * p.Cin2 * 2;
-        if (x2b >= 0x7fffffffL) return hipErrorInvalidValue;
-        p.x2_bytes = (unsigned)x2b;
-        p.x2_shift = p.Cin == p.Cin2 ? 0 : 1;
-        p.Ktot += p.Cin2;
-    }
-    p.nk = (p.Ktot + 63) / 64;
-    if (p.ksplit < 0 && !(p.n_dev && (p.flags & FRP_FLAG_OUT_F32) && !p.res && !(p.Cin & 63))) return hipErrorInvalidValue;
-    if (p.ksplit == 0) p.ksplit = 1;
-    if (p.ksplit > 1 && (p.nk % p.ksplit != 0 || !(p.flags & FRP_FLAG_OUT_F32) || p.res || (p.Cin & 63)))
-        return hipErrorInvalidValue;             // split-K: exact slices, fp32 slabs, aligned path only
-    // buffer descriptors carry 32-bit sizes and the kernel does signed 32-bit offset math
-    const bool f8 = (p.flags & FRP_FLAG_F8) != 0;
-    const int es = f8 ? 1 : 2;
-    const long xb = (long)p.N * p.H * p.W * p.Cin * es, wb = (long)p.Cout * p.Ktot * es;
-    if (xb >= 0x7fffffffL || wb >= 0x7fffffffL) return hipErrorInvalidValue;
-    if ((p.flags & FRP_FLAG_OUT_FP8) && !f8) return hipErrorInvalidValue;
-    if ((p.out2 || f8) && ((p.flags & FRP_FLAG_OUT_F32) || p.ksplit != 1 || !(p.out_scale > 0.f))) return hipErrorInvalidValue;
-    p.x_bytes = (unsigned)xb;
-    p.w_bytes = (unsigned)wb;
+// The generic kernel's tile selection; `few`: quarter tiles (conv_small_m on the 256 x 128 tile count, conv_launch.cpp: conv_pick).
+// Measured on MI355X, tools/conv_bench.py:
+//   Cout > 64 : 256 pixels x 128 couts, 8 waves (64x64 each), 3-slot ring (144 KiB, one
+//               workgroup per CU).  Two independent 4-wave 128x128 groups per CU (2-slot
+//               rings) were 20-25 % slower; a 128x64 per-wave tile does not fit 256 VGPRs.
+//   Cout <= 64: 256 x 64, 8 waves (32x64 each), 3-slot ring (a 512 x 64 tile with 64x64 per wave
+//               measured 10 % slower, two co-resident 4-wave 128 x 64 groups 0-4 % slower).
+hipError_t launch_conv_generic(const ConvParams& p, bool few, hipStream_t stream) {
     const bool small = (p.Cin & 63) != 0;
-    p.cin_shift = 0;
-    if (small) {
-        if (p.Cin & (p.Cin - 1)) return hipErrorInvalidValue;   // small path needs power-of-two Cin
-        while ((1 << p.cin_shift) < p.Cin) ++p.cin_shift;
-    }
-    if ((p.flags & FRP_FLAG_BORDER_BIAS) && !(p.KS == 3 && p.stride == 1 && p.Ho >= 2 && p.Wo >= 2))
-        return hipErrorInvalidValue;
-    if ((p.flags & FRP_FLAG_RES_UP2) && (!p.res || p.Hr * 2 != p.Ho || p.Wr * 2 != p.Wo)) return hipErrorInvalidValue;
-    if (!p.x || !p.w || !p.bias || !p.out) return hipErrorInvalidValue;
-    if (p.act == FRP_ACT_PRELU && !p.slope) return hipErrorInvalidValue;
-    // 3x3 stride-1 layers with whole 64-channel blocks: row-patch kernel (a third of the LDS-DMA traffic)
-    if (f8) {                                        // fp8 operands: only the static-loop row-patch kernel covers them
-        if (!conv3x3_rows_eligible(p) || (p.Cin & 127) || !p.wscale || !(p.in_scale > 0.f)) return hipErrorInvalidValue;
-        return launch_conv3x3_lean(p, stream);
-    }
-    int ncu_ = p.n_cu;                               // (set by the engine; standalone callers: ask the runtime)
-    if (ncu_ <= 0) {
-        int dev_ = 0;
-        if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) return hipErrorInvalidDevice;
-        ncu_ = device_cu_count(dev_);
-    }
-    // few 256 x 128 tiles (small pyramid scales, a handful of faces): quarter tiles, two workgroups per CU (conv_small_m)
-    const bool few = conv_small_m(p, (long)((p.M + 255) / 256) * ((p.Cout + 127) / 128), ncu_);
-    // (a caller that hands over the Winograd image has chosen the kernel FAMILY - frp_api.cpp: run_embed, by the slots of the
-    // call -; the tile count of a single launch does not overrule it: the families differ in the last bits)
-    if (p.wino_w && !p.x2 && !(p.dbg & CONV_DBG_GENERIC) && conv3x3_wino_eligible(p)) {      // Winograd F(2,3) along the rows: 1.5 x fewer MFMAs
-        p.w = p.wino_w;
-        return launch_conv3x3_wino(p, stream);
-    }
-    // 3x3 stride-2 layers: row patches with shared neighbour entries (conv3x3_s2.hip).  OPT-IN (CONV_DBG_S2: FRP_S2 in the engine,
-    // flags bit 21 of frp_conv2d_nhwc): on the headline shapes it measures 9-13 % SLOWER than this kernel's per-tap images
-    // (profiles/r5/s2_probe.txt)
-    if ((p.dbg & CONV_DBG_S2) && !(p.dbg & CONV_DBG_GENERIC) && !few && conv3x3_s2_eligible(p)) return launch_conv3x3_s2(p, stream);
-    // the embedder's stem fused into the conv behind it: only conv3x3_c64.hip does that (the caller asked conv3x3_c64_fuses_stem first)
-    if (p.stem_x) return (p.small_m <= 0 && conv3x3_c64_eligible(p)) ? launch_conv3x3_c64(p, stream) : hipErrorInvalidValue;
-    // 64 -> 64 layers on large maps: weights in registers, 2-D tiles (conv3x3_c64.hip; CONV_DBG_NO_C64: the row-patch kernel instead -
-    // A/B runs; bit-identical results either way)
-    if (!(p.dbg & (CONV_DBG_GENERIC | CONV_DBG_NO_C64)) && p.small_m <= 0 && conv3x3_c64_eligible(p)) return launch_conv3x3_c64(p, stream);
-#ifdef FRP_LAB   // lab build: dbg bits select the first-generation kernel and its timing ablations (conv3x3_rows.hip)
-    if (!(p.dbg & CONV_DBG_GENERIC) && !p.x2 && conv3x3_rows_eligible(p)) return launch_conv3x3_rows(p, stream);
-#else
-    if (!(p.dbg & CONV_DBG_GENERIC) && !p.x2 && conv3x3_rows_eligible(p)) return launch_conv3x3_lean(p, stream);
-#endif
-    // Tile selection (measured on MI355X, tools/conv_bench.py):
-    //   Cout > 64 : 256 pixels x 128 couts, 8 waves (64x64 each), 3-slot ring (144 KiB, one
-    //               workgroup per CU).  Two independent 4-wave 128x128 groups per CU (2-slot
-    //               rings) were 20-25 % slower; a 128x64 per-wave tile does not fit 256 VGPRs.
-    //   Cout <= 64: 256 x 64, 8 waves (32x64 each), 3-slot ring (a 512 x 64 tile with 64x64 per wave
-    //               measured 10 % slower, two co-resident 4-wave 128 x 64 groups 0-4 % slower).
     if (!small && few) return launch_cfg<128, 64, 4, 2, 3, 8, false>(p, stream);
     if (p.Cout > 64)
         return small ? launch_cfg<256, 128, 4, 2, 3, 8, true>(p, stream) : launch_cfg<256, 128, 4, 2, 3, 8, false>(p, stream);

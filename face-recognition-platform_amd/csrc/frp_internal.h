@@ -99,14 +99,14 @@ struct ConvParams {
     _Float16* stem_out;         // [N,H,W,64]: the stem's output, written by this launch
     int stem_even_only;         // only the pixels (even y, even x) of stem_out are written: its one reader is a 1x1 stride-2 conv (the block's
                                 // shortcut, riding in a later k-loop) - a quarter of the map's bytes
-    // derived by launch_conv():
+    // derived by conv_derive() (conv_launch.cpp):
     int pad, Ho, Wo, M, Ktot, nk, cin_shift, n_ptiles, n_ctiles;
     unsigned x_bytes, w_bytes, x2_bytes;   // buffer-descriptor sizes (each < 2 GiB)
     int x2_shift;           // log2(Cin / Cin2)
 };
 
 // ConvParams::dbg: kernel A/B bits for parity tests, conv_bench and A/B runs.  frp_conv2d_nhwc / frp_conv_bench take them from their
-// `flags` (include/frp.h; frp_api.cpp: conv_route_from_abi_flags), the engine's passes from its switches (Switches, ProcessSwitches).
+// `flags` (include/frp.h; kernel_api.cpp: conv_route_from_abi_flags), the engine's passes from its switches (Switches, ProcessSwitches).
 constexpr int CONV_DBG_GENERIC = 1;               // the generic kernel also for shapes a specialised one covers
 constexpr int CONV_DBG_WINO_2D = 256;             // lab: the Winograd kernel's 2-D tiles whatever the shape
 constexpr int CONV_DBG_NO_C64 = 512;              // not the 64 -> 64 kernel (conv3x3_c64.hip): the row-patch one, bit-identical
@@ -132,31 +132,51 @@ static_assert(conv_dbg_disjoint(CONV_DBG_GENERIC, CONV_DBG_WINO_2D, CONV_DBG_NO_
               "the dbg bits one kernel family reads must be disjoint");
 constexpr int conv_dbg_field(int dbg, int field) { return (dbg & field) / (field & -field); }   // the number a multi-bit field holds
 
+// One conv launch (conv_launch.cpp): conv_derive checks the arguments and fills the derived fields, conv_pick chooses the kernel
+// family - a pure function: the routing of a layer without a GPU -, launch_conv is derive, pick, the family's launcher.
+enum class ConvFamily { Wino, S2, C64, RowPatch, Generic, Invalid };
+struct C64Plan {            // conv3x3_c64.hip: what a launch on a map looks like
+    int variant;            // the kernel's (activation, residual, border bias) combination, 0: none of them
+    int tile_w;             // 32 (x 8 rows) or 16 (x 16)
+    long tiles;
+    double fill;            // share of real pixels in the tiles
+};
+struct ConvRoute {
+    ConvFamily family;
+    bool few;               // Generic, RowPatch: quarter tiles (conv_common.h: conv_small_m on the family's default tile count)
+    int wino_form;          // Wino: 1 flattened tiles, 2 the 2-D tiles
+    C64Plan c64;            // C64
+};
+hipError_t conv_derive(ConvParams& p, int* ncu);
+ConvRoute conv_pick(const ConvParams& p, int ncu);
 hipError_t launch_conv(const ConvParams& p, hipStream_t stream);
-// row-patch variant for 3x3 stride-1 layers with Cin % 64 == 0 (conv3x3_rows.hip); launch_conv()
-// routes eligible shapes to it.  `p` must carry launch_conv()'s derived fields.
+// The families' predicates and launchers: `p` carries conv_derive()'s fields, and a launcher gets what conv_pick() found eligible.
+hipError_t launch_conv_generic(const ConvParams& p, bool few, hipStream_t stream);   // conv_mfma.hip: every shape
+// row-patch kernel for 3x3 stride-1 layers with Cin % 64 == 0 (conv3x3_lean.hip: static k-loop generation)
 bool conv3x3_rows_eligible(const ConvParams& p);
+long conv3x3_lean_default_tiles(const ConvParams& p);
 #ifdef FRP_LAB
-hipError_t launch_conv3x3_rows(const ConvParams& p, hipStream_t stream);   // first generation + ablations (lab build only)
+hipError_t launch_conv3x3_rows(const ConvParams& p, bool few, hipStream_t stream);   // first generation + ablations (conv3x3_rows.hip; lab build only)
 #endif
-hipError_t launch_conv3x3_lean(const ConvParams& p, hipStream_t stream);   // static k-loop generation (conv3x3_lean.hip)
+hipError_t launch_conv3x3_lean(const ConvParams& p, bool few, hipStream_t stream);
 // 3x3 stride-1 64 -> 64 layers on large maps (conv3x3_c64.hip): weights resident in registers, 2-D pixel tiles, one barrier per tile
-bool conv3x3_c64_eligible(const ConvParams& p);
+bool conv3x3_c64_eligible(const ConvParams& p, C64Plan* plan);
 bool conv3x3_c64_fuses_stem(int N, int H, int W, int n_cu);   // maps on which the kernel takes the embedder's stem into the launch of the conv behind it
-hipError_t launch_conv3x3_c64(const ConvParams& p, hipStream_t stream);
+hipError_t launch_conv3x3_c64(const ConvParams& p, const C64Plan& plan, hipStream_t stream);
 // 3x3 stride-2 layers (conv3x3_s2.hip): row patches whose left / right neighbour entries are shared by consecutive output pixels
 bool conv3x3_s2_eligible(const ConvParams& p);
 hipError_t launch_conv3x3_s2(const ConvParams& p, hipStream_t stream);
-// Winograd F(2,3) along the image rows (conv3x3_wino.hip): eligibility of a shape (`p` with launch_conv()'s derived fields),
-// the same from the static layer geometry, the size of a layer's weight image, the launch (p.w = the image)
-bool conv3x3_wino_eligible(const ConvParams& p);
+// Winograd F(2,3) along the image rows (conv3x3_wino.hip): the form in which it takes a launch (0: not), eligibility from the static
+// layer geometry, the size of a layer's weight image, the launch (p.w = the image)
+int conv3x3_wino_form(const ConvParams& p);
 bool conv3x3_wino_shape_ok(int W, int Cin, int ksize, int stride);
+bool conv3x3_wino_call_ok(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int n_cu, bool has_res, int dbg);   // stand-alone calls: shape_ok, wide_pays or forced by dbg
 bool conv3x3_wino_wide_pays(int N, int H, int W, int Cin, int Cout, int n_cu, bool has_res);   // maps wider than 30: the 2-D tile form, where its tile arithmetic pays
 #ifdef FRP_LAB
 bool conv3x3_wino_lab_shape_ok(int W, int Cin, int ksize, int stride);   // + the maps only the lab's row-patch form covers (CONV_DBG_WINO_ROW_PATCH)
 #endif
 size_t conv3x3_wino_image_bytes(int Cin, int Cout);
-hipError_t launch_conv3x3_wino(const ConvParams& p, hipStream_t stream);
+hipError_t launch_conv3x3_wino(const ConvParams& p, int form, hipStream_t stream);
 
 // K1: u8 BGR frames -> normalised fp16 NHWC8 canvas (top-left letterbox, zero u8 pad)
 hipError_t launch_preprocess(const uint8_t* bgr, int B, int H, int W, long row_stride, long frame_stride,

@@ -69,11 +69,7 @@ int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t 
     const bool want_wino = (flags & (1 << 16)) != 0;
     std::vector<uint16_t> wimg;
     if (want_wino) {
-        bool shape_ok = conv3x3_wino_shape_ok(W, Cin, ksize, stride) ||
-                        (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, res != nullptr));      // (2-D tiles: wide maps)
-#ifdef FRP_LAB
-        shape_ok = shape_ok || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
-#endif
+        const bool shape_ok = conv3x3_wino_call_ok(N, H, W, Cin, Cout, ksize, stride, h->n_cu, res != nullptr, p.dbg);
         if (!shape_ok || (flags & (FRP_FLAG_OUT_F32 | FRP_FLAG_RES_UP2)))
             return fail(h, FRP_ERR_INVALID, "shape not covered by the Winograd kernel");
         wimg.resize(conv3x3_wino_image_bytes(Cin, Cout) / 2);
@@ -244,8 +240,7 @@ int frp_conv_bench(frp_handle* h, int32_t N, int32_t H, int32_t W, int32_t Cin, 
         if (with_res) p.out2 = nullptr;
     }
     conv_route_from_abi_flags(flags, p);
-    bool wino_shape = conv3x3_wino_shape_ok(W, Cin, ksize, stride) || (ksize == 3 && stride == 1 && conv3x3_wino_wide_pays(N, H, W, Cin, Cout, h->n_cu, with_res != 0));
-    wino_shape = wino_shape || ((p.dbg & (CONV_DBG_WINO_ROW_PATCH | CONV_DBG_WINO_2D)) && conv3x3_wino_lab_shape_ok(W, Cin, ksize, stride));
+    const bool wino_shape = conv3x3_wino_call_ok(N, H, W, Cin, Cout, ksize, stride, h->n_cu, with_res != 0, p.dbg);
     if ((flags & (1 << 16)) && wino_shape) {     // Winograd kernel: a random weight image (timing only)
         const size_t ib = conv3x3_wino_image_bytes(Cin, Cout);
         if (ensure(h, dwino, ib) == FRP_OK) {

@@ -33,6 +33,7 @@ Switches frp::read_switches() {
     s.no_fused_stem12 = set("FRP_NO_FUSED_STEM12"); s.no_fused_stem = set("FRP_NO_FUSED_STEM");
     s.no_emb_stem = set("FRP_NO_EMB_STEM"); s.no_stem_fuse = set("FRP_NO_STEM_FUSE");
     s.no_wino = set("FRP_NO_WINO"); s.no_kconcat = set("FRP_NO_KCONCAT");
+    s.no_block_fuse = set("FRP_NO_BLOCK_FUSE"); s.block_fuse_all = set("FRP_BLOCK_FUSE_ALL");
     return s;
 }
 

@@ -40,6 +40,8 @@ struct Switches {
     int match_v1;         // FRP_MATCH_V1 set: the per-tile matcher only, never the persistent top-1 kernel (also a host-side count)
     int no_wino;          // FRP_NO_WINO set, read at weight load: no Winograd weight images, direct kernels only
     int no_kconcat;       // FRP_NO_KCONCAT set, read at weight load: no 1x1 shortcut conv folded into its consumer's k-loop
+    int no_block_fuse;    // FRP_NO_BLOCK_FUSE set: a 64 -> 64 residual block as its two conv launches, never the fused one (conv3x3_block64.hip)
+    int block_fuse_all;   // FRP_BLOCK_FUSE_ALL set: the fused block launch on every eligible shape, also where it does not pay (tests on small maps)
 };
 static_assert(std::has_unique_object_representations_v<Switches>, "run_net keys captured graphs by the bytes of a Switches");
 Switches read_switches();
@@ -163,6 +165,58 @@ hipError_t launch_conv3x3_lean(const ConvParams& p, bool few, hipStream_t stream
 bool conv3x3_c64_eligible(const ConvParams& p, C64Plan* plan);
 bool conv3x3_c64_fuses_stem(int N, int H, int W, int n_cu);   // maps on which the kernel takes the embedder's stem into the launch of the conv behind it
 hipError_t launch_conv3x3_c64(const ConvParams& p, const C64Plan& plan, hipStream_t stream);
+// A residual block of two 3x3 stride-1 64 -> 64 convs in one launch (conv3x3_block64.hip): out = act2(conv2(act1(conv1(x))) + x), the
+// intermediate tensor in LDS only.  Not a family of launch_conv: net_program.cpp's walk launches a marked pair of ops through it.
+#define BLOCK64_STRIP_W 30          // output columns of a strip: the intermediate row (+ 2 halo columns) is one 32-pixel MFMA block
+#define BLOCK64_IN_W 34             // input columns under a strip
+#define BLOCK64_LDS_BYTES 159232    // input ring 4 x 20 KiB, intermediate ring 16 rows x 4608 B (+ 512), epilogue parameters 3 KiB
+#define BLOCK64_MIN_FILL 0.70       // conv3x3_block64_pays: least share of real output pixels in the launch's pixel slots
+struct Block64Params {
+    const _Float16* x;      // [N,H,W,64]: conv1's input and the block's residual
+    const _Float16* w1;     // [64][3][3][64]
+    const float* bias1;     // [64] or [9][64] (flags1 & FRP_FLAG_BORDER_BIAS)
+    const float* slope1;    // [64] (PReLU) or null
+    const _Float16* w2;
+    const float* bias2;     // [64]
+    const float* slope2;    // [64] or null
+    void* out;              // [N,H,W,64] fp16, not x
+    const int32_t* n_dev;   // null, or the number of images that really exist (<= N) in device memory
+    int N, H, W;
+    int act1, flags1, act2;
+    int n_cu;               // compute units the plan is made for (<= 0: 256)
+    int strips, segs, seg_rows;   // filled by the launcher from conv3x3_block64_plan()
+};
+struct Block64Plan {
+    int strips, segs, seg_rows;   // per image: strips of 30 columns x segments of seg_rows rows (a multiple of 4; the last may be shorter)
+    int steps;                    // steps of the longest work item
+    long items;                   // work items: N x strips x segs
+    int grid, lds;
+    double fill;                  // real output pixels / (rounds x CUs x steps x 120 pixel slots)
+};
+// work item `item` of a launch: image n, output rows ys .. ye - 1, output columns x0 .. x0 + 29 (clipped to the map), K conv1 steps
+// (the item takes K + 1 steps).  Host and device evaluate the same function (the kernel; tests/native/block64_plan_harness.cpp).
+struct Block64Item { int n, ys, ye, x0, K; };
+__host__ __device__ inline Block64Item block64_item(int item, int strips, int segs, int seg_rows, int H) {
+    Block64Item it;
+    const int per_img = strips * segs;
+    it.n = item / per_img;
+    const int r = item - it.n * per_img, seg = r / strips;
+    it.ys = seg * seg_rows;
+    it.ye = it.ys + seg_rows < H ? it.ys + seg_rows : H;
+    it.x0 = (r - seg * strips) * BLOCK64_STRIP_W;
+    it.K = (it.ye - it.ys + 2 + 3) >> 2;
+    return it;
+}
+// the input rows an item fetches (groups of four from two rows above its first output row: its groups 1 .. K + 1) and its input columns
+// (34 from two columns left of its first output column): the halo the plan declares - at most BLOCK64_HALO_DOWN rows below the segment
+#define BLOCK64_HALO_UP 2
+#define BLOCK64_HALO_DOWN 7
+__host__ __device__ inline int block64_first_in_row(const Block64Item& it) { return it.ys - 6 + 4; }
+__host__ __device__ inline int block64_last_in_row(const Block64Item& it) { return it.ys - 6 + 4 * (it.K + 1) + 3; }
+int conv3x3_block64_variant(int act1, int flags1, bool slope1, int act2, int flags2);   // 0: none, 1: detector (ReLU, ReLU), 2: embedder (PReLU + border classes, none)
+bool conv3x3_block64_plan(int N, int H, int W, int n_cu, Block64Plan* plan);             // false: out of 32-bit reach
+bool conv3x3_block64_pays(const Block64Plan& plan);
+hipError_t launch_conv3x3_block64(const Block64Params& p, hipStream_t stream);
 // 3x3 stride-2 layers (conv3x3_s2.hip): row patches whose left / right neighbour entries are shared by consecutive output pixels
 bool conv3x3_s2_eligible(const ConvParams& p);
 hipError_t launch_conv3x3_s2(const ConvParams& p, hipStream_t stream);

@@ -146,6 +146,59 @@ int frp_conv2d_f8(frp_handle* h, const void* x8, int32_t N, int32_t H, int32_t W
     return FRP_OK;
 }
 
+int frp_conv_block64(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t W, const void* w1, const float* bias1, const float* slope1,
+                     int32_t act1, int32_t flags1, const void* w2, const float* bias2, const float* slope2, int32_t act2, void* out) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!x || !w1 || !bias1 || !w2 || !bias2 || !out || N <= 0 || H <= 0 || W <= 0) return fail(h, FRP_ERR_INVALID, "bad block arguments");
+    if (!conv3x3_block64_variant(act1, flags1, slope1 != nullptr, act2, 0)) return fail(h, FRP_ERR_INVALID, "block epilogues not covered by the fused kernel");
+    Block64Plan plan;
+    if (!conv3x3_block64_plan(N, H, W, h->n_cu, &plan) || ((flags1 & FRP_FLAG_BORDER_BIAS) && (H < 2 || W < 2)))
+        return fail(h, FRP_ERR_INVALID, "block shape out of the fused kernel's reach");
+    const size_t tb = (size_t)N * H * W * 128, wb = (size_t)64 * 576 * 2, guard = 4096;
+    const size_t b1 = (size_t)64 * 4 * ((flags1 & FRP_FLAG_BORDER_BIAS) ? 9 : 1);
+    ScopedBuf dx, dw1, dw2, db1, db2, ds1, ds2, dout;
+    FRPCHK(ensure(h, dx, tb + 2 * guard));
+    FRPCHK(ensure(h, dout, tb + 2 * guard));
+    FRPCHK(ensure(h, dw1, wb));
+    FRPCHK(ensure(h, dw2, wb));
+    FRPCHK(ensure(h, db1, b1));
+    FRPCHK(ensure(h, db2, 256));
+    if (slope1) FRPCHK(ensure(h, ds1, 256));
+    if (slope2) FRPCHK(ensure(h, ds2, 256));
+    std::vector<uint16_t> nan(guard, 0x7e00u), back(guard);          // (guard bytes front + guard bytes back)
+    char *gx = (char*)dx->p, *go = (char*)dout->p;
+    hipError_t e = hipMemcpyAsync(gx, nan.data(), guard, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(gx + guard + tb, nan.data(), guard, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(go, nan.data(), guard, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(go + guard + tb, nan.data(), guard, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(go + guard, 0x7e, tb, h->stream);          // (a pixel the launch does not write stays a NaN)
+    if (e == hipSuccess) e = hipMemcpyAsync(gx + guard, x, tb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw1->p, w1, wb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw2->p, w2, wb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db1->p, bias1, b1, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db2->p, bias2, 256, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && slope1) e = hipMemcpyAsync(ds1->p, slope1, 256, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && slope2) e = hipMemcpyAsync(ds2->p, slope2, 256, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        Block64Params p{};
+        p.x = (const _Float16*)(gx + guard); p.out = go + guard;
+        p.w1 = (const _Float16*)dw1->p; p.bias1 = (const float*)db1->p; p.slope1 = slope1 ? (const float*)ds1->p : nullptr;
+        p.w2 = (const _Float16*)dw2->p; p.bias2 = (const float*)db2->p; p.slope2 = slope2 ? (const float*)ds2->p : nullptr;
+        p.N = N; p.H = H; p.W = W; p.act1 = act1; p.flags1 = flags1; p.act2 = act2;
+        p.n_cu = h->n_cu;
+        e = launch_conv3x3_block64(p, h->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, go + guard, tb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), go, guard, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)back.data() + guard, go + guard + tb, guard, hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go)
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("conv_block64: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("conv_block64 sync: ") + hipGetErrorString(e2));
+    if (back != nan) return fail(h, FRP_ERR_HIP, "conv_block64: the launch wrote outside its output tensor");
+    return FRP_OK;
+}
+
 int frp_debug_pyramid_merge(frp_handle* h, int32_t n_scales, const int32_t* det_hw, int32_t B, int32_t per_scale, int32_t frame_h,
                             int32_t frame_w, const float* boxes, const float* kps, const float* scores, const int32_t* counts,
                             int32_t max_faces, float nms_iou, float* out_boxes, float* out_kps, float* out_scores, int32_t* out_counts) {
@@ -252,6 +305,14 @@ int frp_conv_bench(frp_handle* h, int32_t N, int32_t H, int32_t W, int32_t Cin, 
         (void)hipMemsetAsync(dst->p, 0, 256 * 8 * 8, h->stream);
         p.stamps = (unsigned long long*)dst->p;
     }
+    if (flags & (1 << 23)) {                    // the fused residual block (conv3x3_block64.hip) this conv1 opens: conv1 (act, border bias), conv2 + x
+        Block64Params bp{};                     // (+ ReLU behind a ReLU conv1: the detector's block; none behind PReLU: the embedder's)
+        bp.x = p.x; bp.out = p.out; bp.w1 = bp.w2 = p.w; bp.bias1 = bp.bias2 = p.bias; bp.slope1 = p.slope;
+        bp.N = N; bp.H = H; bp.W = W; bp.act1 = act; bp.flags1 = flags & FRP_FLAG_BORDER_BIAS; bp.act2 = act == FRP_ACT_RELU ? FRP_ACT_RELU : FRP_ACT_NONE;
+        bp.n_cu = h->n_cu;
+        if (Cin != 64 || Cout != 64 || ksize != 3 || stride != 1) e = hipErrorInvalidValue;
+        if (e == hipSuccess) e = time_launches(h, 2, iters, [&] { return launch_conv3x3_block64(bp, h->stream); }, &ms);
+    } else
     if (e == hipSuccess) e = time_launches(h, 2, iters, [&] { return launch_conv(p, h->stream); }, &ms);
     if (e == hipSuccess && stamps_out && p.stamps) e = hipMemcpy(stamps_out, p.stamps, 256 * 8 * 8, hipMemcpyDeviceToHost);
     (void)hipStreamSynchronize(h->stream);      // (before the buffers go)

@@ -309,8 +309,35 @@ void analyse_emb_stem(Net& net) {
     }
 }
 
+// Residual blocks of two 3x3 stride-1 64 -> 64 convs that the fused block kernel can take (conv3x3_block64.hip): ops (i, i + 1) where the
+// intermediate tensor has no reader but op i + 1, the residual is op i's input and the output lands in a third buffer.  A blob that
+// fails a precondition runs the two launches, as with K-concat.  `read_outside`: the buffers something behind the program reads.
+void analyse_block64(Net& net, const std::vector<int>& read_outside) {
+    const int n = (int)net.ops.size();
+    net.block64.assign(n, 0);
+    for (int i = 0; i + 1 < n; ++i) {
+        const frp_conv_op &a = net.ops[i], &b = net.ops[i + 1];
+        auto c64 = [](const frp_conv_op& o) { return o.ksize == 3 && o.stride == 1 && o.cin == 64 && o.cout == 64 && o.out2_buf < 0; };
+        if (!c64(a) || !c64(b) || net.kc_skip[i] || net.kc_skip[i + 1] || net.kc_src[i] >= 0 || net.kc_src[i + 1] >= 0) continue;
+        if (a.res_buf >= 0 || b.in_buf != a.out_buf || b.res_buf != a.in_buf || b.out_buf == a.in_buf || b.out_buf == a.out_buf) continue;
+        if (a.in_buf == net.in_buf && net.in_ch != 64) continue;
+        if (!conv3x3_block64_variant(a.act, a.flags, a.slope_off >= 0, b.act, b.flags)) continue;       // (also: no fp8 / OUT_F32 / RES_UP2 flag)
+        if (net.fuse_ok && i == net.fuse_op) continue;                                                   // the launch that computes the embedder's stem
+        bool ok = true;
+        for (int q = i + 2; q < n && ok; ++q) {                  // the intermediate tensor has no other reader while the buffer holds it
+            const frp_conv_op& o = net.ops[q];
+            if (o.in_buf == a.out_buf || o.res_buf == a.out_buf) ok = false;
+            if (o.out_buf == a.out_buf || o.out2_buf == a.out_buf) break;
+        }
+        for (int r : read_outside) ok &= r != a.out_buf;
+        if (!ok) continue;
+        net.block64[i] = 1;
+        ++i;                                                     // (op i + 1 belongs to this pair)
+    }
+}
+
 // every fact of the finished op table (K-concat plan included) that a pass would otherwise re-derive
-void analyse_net(Net& net) {
+void analyse_net(Net& net, const std::vector<int>& read_outside) {
     const int n = (int)net.ops.size();
     net.det_stem = stem_fusable(net);
     net.det_stem12 = stem12_fusable(net);
@@ -323,6 +350,7 @@ void analyse_net(Net& net) {
     net.emb_stem = net.fuse_ok = net.fuse_even_only = false;
     net.fuse_op = -1;
     if (n) analyse_emb_stem(net);
+    analyse_block64(net, read_outside);
 }
 
 }  // namespace
@@ -357,8 +385,8 @@ int load_program(frp_handle* h, const frp_blob_header& hd, const unsigned char* 
         plan_kconcat(det, {(int)hd.det_head_buf[0], (int)hd.det_head_buf[1], (int)hd.det_head_buf[2]}, image);
         plan_kconcat(emb, {(int)hd.emb_out_buf}, image);
     }
-    analyse_net(det);
-    analyse_net(emb);
+    analyse_net(det, {(int)hd.det_head_buf[0], (int)hd.det_head_buf[1], (int)hd.det_head_buf[2]});
+    analyse_net(emb, {(int)hd.emb_out_buf});
     return FRP_OK;
 }
 
@@ -576,6 +604,17 @@ void charge(const frp_conv_op& op, const TensorDims& out, int batch, PassEffects
     if (op.flags & FRP_OPFLAG_FP8_MFMA) { fx.f8_flops += fl; fx.f8_launches += 1; }
 }
 
+// Does this pass run a marked residual block (Net::block64) on maps of dims `in` as the fused launch?  Where its plan pays
+// (conv3x3_block64.hip: conv3x3_block64_pays; FRP_BLOCK_FUSE_ALL: wherever the kernel reaches); never with FRP_NO_BLOCK_FUSE or forced
+// quarter tiles.  (The walk adds: not with the per-op hashes, not when the diagnostic op limit cuts the pair.)
+bool block64_fuses(const NetPass& ps, const TensorDims& in) {
+    if (ps.sw.no_block_fuse || ps.sw.small_m > 0) return false;
+    Block64Plan plan;
+    if (!conv3x3_block64_plan(ps.batch, in.h, in.w, ps.h->n_cu, &plan)) return false;
+    if ((in.h < 2 || in.w < 2)) return false;
+    return ps.sw.block_fuse_all || conv3x3_block64_pays(plan);
+}
+
 // One pass, launch by launch, into `fx` (nothing else on the handle or the net is written, but for the split-K workspace).
 int walk(const NetPass& ps, PassEffects& fx) {
     frp_handle* h = ps.h;
@@ -598,6 +637,30 @@ int walk(const NetPass& ps, PassEffects& fx) {
         if (net.kc_skip[i]) {                  // a shortcut conv its consumer computes (K-concat): FLOPs charged here
             set_out_dims(d, op, out);
             fx.flops += 2.0 * ps.batch * out.h * out.w * (double)op.cin * op.cout;
+            continue;
+        }
+        if (net.block64[i] && i + 1 < end && !hashing && block64_fuses(ps, in)) {
+            // the residual block (i, i + 1) as ONE launch: both ops' dims and FLOPs, one launch; op i's output buffer is not written
+            const frp_conv_op& op2 = net.ops[i + 1];
+            const char* wbase = ps.weights();
+            Block64Params bp{};
+            bp.x = (const _Float16*)net.bufs[op.in_buf].p;
+            bp.out = net.bufs[op2.out_buf].p;
+            bp.w1 = (const _Float16*)(wbase + op.w_off); bp.bias1 = (const float*)(wbase + op.bias_off);
+            bp.slope1 = op.slope_off >= 0 ? (const float*)(wbase + op.slope_off) : nullptr;
+            bp.w2 = (const _Float16*)(wbase + op2.w_off); bp.bias2 = (const float*)(wbase + op2.bias_off);
+            bp.slope2 = op2.slope_off >= 0 ? (const float*)(wbase + op2.slope_off) : nullptr;
+            bp.n_dev = ps.n_dev;
+            bp.N = ps.batch; bp.H = in.h; bp.W = in.w;
+            bp.act1 = op.act; bp.flags1 = op.flags & FRP_FLAG_BORDER_BIAS; bp.act2 = op2.act;
+            bp.n_cu = h->n_cu;
+            FRPCHK(launched(h, launch_conv3x3_block64(bp, h->stream), "launch_conv3x3_block64"));
+            set_out_dims(d, op, out);
+            set_out_dims(d, op2, out);
+            charge(op, out, ps.batch, fx);
+            charge(op2, out, ps.batch, fx);
+            fx.launches -= 1;
+            ++i;
             continue;
         }
         ConvParams p = conv_params_for(ps, i, in, d, fused);

@@ -41,6 +41,8 @@ struct Net {
     int fuse_op = -1;               // the first op behind op 0 that launches: the candidate to compute the embedder's stem itself
     bool fuse_ok = false;           // that op is a plain 64 -> 64 conv reading the stem's map, no K-concat consumer, no buffer an alias
     bool fuse_even_only = false;    // the stem's map has no reader besides fuse_op but shortcut convs riding in a later k-loop
+    std::vector<char> block64;      // per op: 1 = this op and the next are a residual block of two 3x3 stride-1 64 -> 64 convs that one fused
+                                    // launch can compute (conv3x3_block64.hip): the intermediate tensor then never reaches its buffer
     int fc_op = -1;                 // the final op when it writes fp32 (the FC: split-K candidate), or -1
     std::vector<int> next_launch;   // per op: the next op that really launches (its weights are the prefetch target), or -1
 };

@@ -43,7 +43,7 @@ ABI_SYMBOLS = [
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -255,6 +255,8 @@ def load_library() -> C.CDLL:
         lib.frp_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, u32, vp, i64, vp]
         lib.frp_encode_jpeg_coefficients.argtypes = [vp, vp, i32, i32, i32, u32, vp, i64]
     lib.frp_conv2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]
+    if hasattr(lib, "frp_conv_block64"):   # (an older build loaded through FRP_LIB as an A/B partner has none)
+        lib.frp_conv_block64.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
     lib.frp_conv2d_f8.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp]
     if hasattr(lib, "frp_kstep_lab"):            # the FRP_LAB build (libfrp_lab.so, include/frp_lab.h): tuning hooks
         lib.frp_conv_bench.argtypes = [vp] + [i32] * 11 + [C.POINTER(C.c_float), vp]
@@ -908,6 +910,27 @@ class Engine:
             slope = np.ascontiguousarray(slope, dtype=np.float32)
         self._chk(self._lib.frp_conv2d_nhwc(self._h, _ptr(x), N, H, W, Cin, _ptr(w), Cout, k, stride, _ptr(bias), _ptr(slope),
                                             _ptr(res), rh, rw, act, flags, _ptr(out)))
+        return out
+
+    def conv_block64(self, x, w1, bias1, w2, bias2, act1=1, act2=1, slope1=None, slope2=None, flags1=0):
+        """out = act2(conv2(act1(conv1(x))) + x), both convs 3x3 stride 1 64 -> 64, in one fused launch (conv3x3_block64.hip)"""
+        x = np.ascontiguousarray(x, dtype=np.float16)
+        w1 = np.ascontiguousarray(w1, dtype=np.float16)
+        w2 = np.ascontiguousarray(w2, dtype=np.float16)
+        bias1 = np.ascontiguousarray(bias1, dtype=np.float32)
+        bias2 = np.ascontiguousarray(bias2, dtype=np.float32)
+        if x.ndim != 4 or x.shape[3] != 64 or w1.shape != (64, 3, 3, 64) or w2.shape != (64, 3, 3, 64):
+            raise ValueError("conv_block64: x [N,H,W,64], w1 / w2 [64,3,3,64]")
+        if bias1.size != (576 if flags1 & 1 else 64) or bias2.size != 64:
+            raise ValueError("conv_block64: bias1 [64] ([9,64] with border classes), bias2 [64]")
+        if slope1 is not None:
+            slope1 = np.ascontiguousarray(slope1, dtype=np.float32)
+        if slope2 is not None:
+            slope2 = np.ascontiguousarray(slope2, dtype=np.float32)
+        N, H, W, _ = x.shape
+        out = np.empty_like(x)
+        self._chk(self._lib.frp_conv_block64(self._h, _ptr(x), N, H, W, _ptr(w1), _ptr(bias1), _ptr(slope1), act1, flags1,
+                                             _ptr(w2), _ptr(bias2), _ptr(slope2), act2, _ptr(out)))
         return out
 
     def conv2d_f8(self, x8, w8, wscale, bias, act=0, slope=None, res=None, flags=0, in_scale=1.0, out_scale=1.0,

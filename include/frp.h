@@ -479,6 +479,16 @@ int frp_conv2d_nhwc(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t 
                     const float* bias, const float* slope, const void* res, int32_t res_h, int32_t res_w,
                     int32_t act, int32_t flags, void* out);
 
+/* one residual block of two 3x3 stride-1 64 -> 64 convolutions through the fused block kernel (csrc/conv3x3_block64.hip; kernel parity
+ * tests): out = act2(conv2(act1(conv1(x))) + x) on host tensors, x and out [N,H,W,64] fp16, w1 / w2 [64][3][3][64] fp16, bias1 [64] fp32
+ * ([9][64] with FRP_FLAG_BORDER_BIAS = 1 in flags1), bias2 [64], slopes [64] or NULL.  The two epilogue combinations of the networks:
+ * (act1, flags1, act2) = (ReLU, 0, ReLU) and (PReLU, border bias, none); anything else, or a shape beyond signed 32-bit byte offsets, is
+ * FRP_ERR_INVALID.  On the device x and out lie between guard regions filled with fp16 NaNs: a read outside x poisons the result, a
+ * write outside out is reported as FRP_ERR_HIP. */
+int frp_conv_block64(frp_handle* h, const void* x, int32_t N, int32_t H, int32_t W, const void* w1, const float* bias1,
+                     const float* slope1, int32_t act1, int32_t flags1, const void* w2, const float* bias2, const float* slope2,
+                     int32_t act2, void* out);
+
 /* one 3x3 stride-1 convolution on fp8 operands through the block-scaled fp8 MFMA kernel (BASELINE config 5; kernel parity
  * tests): x8 [N,H,W,Cin] and w8 [Cout][3][3][Cin] are OCP E4M3 bytes (Cin a multiple of 128), value = code * scale with
  * one scale per output channel (wscale) and one for the input tensor (in_scale); res16 fp16 or NULL; `out` fp16, or E4M3

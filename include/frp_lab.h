@@ -10,7 +10,8 @@ extern "C" {
 #endif
 
 /* tuning hook: average milliseconds of `iters` back-to-back launches of one conv shape on
- * random device-resident operands (HIP events on the handle's stream) */
+ * random device-resident operands (HIP events on the handle's stream).  `flags` bit 23 (64 -> 64, 3x3, stride 1): instead of this
+ * conv alone the fused residual block it opens (csrc/conv3x3_block64.hip) - this conv, a second one, + x, ReLU behind a ReLU conv */
 int frp_conv_bench(frp_handle* h, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride,
                    int32_t act, int32_t flags, int32_t with_res, int32_t iters, float* ms_avg,
                    uint64_t* stamps_out /* NULL, or [256][8] per-workgroup 100 MHz phase stamps of the last launch */);

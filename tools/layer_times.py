@@ -73,7 +73,21 @@ def main():
         tot += d
         tot_gap += gap
         name = r["Kernel_Name"]
-        if "conv_mfma" in name or "conv3x3_rows" in name or "conv3x3_lean" in name or "conv3x3_wino" in name or "conv3x3_c64" in name:
+        if "conv3x3_block64" in name:
+            # a residual block in one launch (conv3x3_block64.hip): one row named after both ops, both ops' FLOPs; bytes = one read of the
+            # block input, one write of the block output, both layers' weights (the intermediate tensor stays in LDS, the residual is
+            # the input rows already there)
+            l, h, w, fl, by = next(convs)
+            l2, h2, w2, fl2, by2 = next(convs)
+            n_img = by2 // (h2 * w2 * 64 * 2 * 3)
+            fl += fl2
+            by = 2 * n_img * h * w * 64 * 2 + 2 * 64 * 64 * 9 * 2
+            bound = max(fl / 1.25e9, by / 4.5e6)
+            bounds.append((d, bound))
+            print(f"{l.name + ' + ' + l2.name.rsplit('.', 1)[-1]:28s} {h:4d}x{w:<4d} {l.cin:5d}->{l2.cout:3d} k{l.k}s{l.stride} grid {r['Grid_Size_X']:>7s} "
+                  f"{d:8.1f} us  gap {gap:6.1f}  {fl / d / 1e6:7.1f} TF  {by / d / 1e3:7.1f} GB/s  x{d / bound:4.2f} of "
+                  f"{'mfma' if fl / 1.25e9 >= by / 4.5e6 else 'hbm '} bound  fused residual block, 30-column strips, intermediate in LDS")
+        elif "conv_mfma" in name or "conv3x3_rows" in name or "conv3x3_lean" in name or "conv3x3_wino" in name or "conv3x3_c64" in name:
             l, h, w, fl, by = next(convs)
             stem_fused = "conv3x3_c64" in name and name.rstrip().endswith(", true>(frp::ConvParams)")
             if stem_fused:

@@ -1,5 +1,5 @@
 // The stand-alone kernel entry points of libfrp.so: one conv launch on host tensors (frp_conv2d_nhwc, frp_conv2d_f8: the parity
-// tests' way to a single kernel; frp_debug_pyramid_merge: the cross-scale merge on host detections) and, in libfrp_lab.so only, the tuning hooks of include/frp_lab.h.
+// tests' way to a single kernel; frp_debug_pyramid_merge: the cross-scale merge on host detections; frp_debug_fc_l2norm: the embedder's tail on host operands) and, in libfrp_lab.so only, the tuning hooks of include/frp_lab.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -253,6 +253,69 @@ int frp_debug_pyramid_merge(frp_handle* h, int32_t n_scales, const int32_t* det_
     hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go)
     if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("pyramid_merge: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("pyramid_merge sync: ") + hipGetErrorString(e2));
+    return FRP_OK;
+}
+
+int frp_debug_fc_l2norm(frp_handle* h, const void* x_f16, const void* w_f16, const float* bias, int32_t cap, int32_t n, int32_t K, int32_t D,
+                        int32_t mode, int32_t flags, float* emb, void* emb_f16, int32_t* n_cu, int32_t* host_factor) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!x_f16 || !w_f16 || !bias || !emb || !emb_f16) return fail(h, FRP_ERR_INVALID, "fc_l2norm: null argument");
+    if (cap < 1 || n < 0 || n > cap || K < 8 || D < 8 || D > 1024 || mode < FRP_FC_DEVICE_COUNT || (flags & ~((1 << 17) | (1 << 18))))
+        return fail(h, FRP_ERR_INVALID, "fc_l2norm: 0 <= n <= cap, cap >= 1, K >= 8, 8 <= D <= 1024, mode >= -1, flags bits 17 / 18 only");
+    const bool dev_count = mode == FRP_FC_DEVICE_COUNT;
+    const int N = dev_count ? cap : n;                      // the images the launches are made for
+    const int fc_flags = FRP_FLAG_OUT_F32;
+    // the launch decisions of a pass (net_program.cpp: pick_fc_splitk): host count -> the factor of n, device count -> -1 and slabs for the
+    // capacity; a forced factor s stands where the host's would (s == 1: no split, the conv's own fp32 epilogue)
+    FcSplitChoice c = fc_splitk_choice(N > 0 ? N : 1, 1, dev_count, D, K, fc_flags, false, h->n_cu);
+    if (mode >= 2) c = {mode, (size_t)mode * (N > 0 ? N : 1) * D * 4};
+    if (mode == 1) c = {0, 0};
+    if (n_cu) *n_cu = h->n_cu;
+    if (host_factor) *host_factor = conv_pick_ksplit(n, D, K, fc_flags, false, h->n_cu);
+    const size_t xb = (size_t)cap * K * 2, wb = (size_t)D * K * 2, eb = (size_t)cap * D * 4;
+    ScopedBuf dx, dw, db, dn, dws, de, de16;
+    FRPCHK(ensure(h, dx, xb));
+    FRPCHK(ensure(h, dw, wb));
+    FRPCHK(ensure(h, db, (size_t)D * 4));
+    FRPCHK(ensure(h, dn, 4));
+    FRPCHK(ensure(h, de, eb));
+    FRPCHK(ensure(h, de16, eb / 2));
+    if (c.ws_bytes) FRPCHK(ensure(h, dws, c.ws_bytes));
+    ConvParams p{};
+    conv_route_from_abi_flags(flags, p);
+    p.x = (const _Float16*)dx->p; p.w = (const _Float16*)dw->p; p.bias = (const float*)db->p;
+    p.out = c.ksplit ? dws->p : de->p;
+    p.N = N; p.H = 1; p.W = 1; p.Cin = K; p.Cout = D; p.KS = 1; p.stride = 1; p.act = FRP_ACT_NONE;
+    p.flags = fc_flags;
+    p.ksplit = c.ksplit;
+    p.n_dev = dev_count ? (const int32_t*)dn->p : nullptr;
+    p.n_cu = h->n_cu;
+    p.in_scale = p.out_scale = 1.0f;
+    if (N > 0) {                                            // what launch_conv would refuse is refused before anything is queued
+        ConvParams probe = p;
+        int ncu = 0;
+        if (conv_derive(probe, &ncu) != hipSuccess) return fail(h, FRP_ERR_INVALID, "fc_l2norm: shape or split factor the conv launch refuses");
+    }
+    // 0xFF bytes (NaN patterns) where the launches write: a slab read without having been written, a row at or beyond n written, shows
+    hipError_t e = hipMemsetAsync(de->p, 0xFF, eb, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(de16->p, 0xFF, eb / 2, h->stream);
+    if (e == hipSuccess && c.ws_bytes) e = hipMemsetAsync(dws->p, 0xFF, c.ws_bytes, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dx->p, x_f16, xb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw->p, w_f16, wb, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(db->p, bias, (size_t)D * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dn->p, &n, 4, hipMemcpyHostToDevice, h->stream);
+    if (N > 0) {                                            // (run_embed: a call without faces launches nothing)
+        if (e == hipSuccess) e = launch_conv(p, h->stream);
+        if (e == hipSuccess)
+            e = launch_l2norm((float*)de->p, (_Float16*)de16->p, N, D, h->stream, c.ksplit != 0 && c.ksplit != 1 ? (const float*)dws->p : nullptr,
+                              c.ksplit, p.bias, p.n_dev, K, h->n_cu);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(emb, de->p, eb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(emb_f16, de16->p, eb / 2, hipMemcpyDeviceToHost, h->stream);
+    hipError_t e2 = hipStreamSynchronize(h->stream);      // (before the buffers go, and `n` on this frame)
+    if (e != hipSuccess) return fail(h, e == hipErrorInvalidValue ? FRP_ERR_INVALID : FRP_ERR_HIP, std::string("fc_l2norm: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("fc_l2norm sync: ") + hipGetErrorString(e2));
     return FRP_OK;
 }
 

@@ -579,20 +579,31 @@ ConvParams conv_params_for(const NetPass& ps, size_t i, const TensorDims& in, co
     return p;
 }
 
+}  // namespace
+
+// The split-K choice of a skinny fp32-output GEMM launch (the FC) of `batch` images with `out_pixels` outputs each: the value of
+// ConvParams::ksplit and the bytes of the slab workspace.  Device-side count: the kernel picks the factor of the real batch itself (the
+// same function), the slabs are sized for the largest one - that of a single image - times the capacity.
+FcSplitChoice fc_splitk_choice(int batch, int out_pixels, bool device_count, int cout, int ktot, int flags, bool has_res, int n_cu) {
+    const int ks = conv_pick_ksplit((device_count ? 1 : batch) * out_pixels, cout, ktot, flags, has_res, n_cu);
+    if (ks <= 1) return {0, 0};
+    return {device_count ? -1 : ks, (size_t)ks * batch * cout * 4};   // 1x1 output per image for the FC shape
+}
+
+namespace {
+
 // skinny fp32-output GEMM (the FC): split K over the CUs; the slabs are reduced (+bias) by the l2norm kernel that follows
 void pick_fc_splitk(const NetPass& ps, const frp_conv_op& op, const TensorDims& in, const TensorDims& out, ConvParams& p, FcSplitK& fc) {
     frp_handle* h = ps.h;
-    // device-side count: the kernel picks the factor of the real batch itself (the same function), the slabs are
-    // sized for the largest one - that of a single image - times the capacity
-    const int ks = conv_pick_ksplit((ps.n_dev ? 1 : ps.batch) * out.h * out.w, op.cout, op.ksize * op.ksize * op.cin, op.flags, op.res_buf >= 0, h->n_cu);
-    if (ks <= 1 || in.h != 1 || in.w != 1) return;
-    const size_t slab = (size_t)ks * ps.batch * op.cout * 4;   // 1x1 output per image for the FC shape
-    if (ensure(h, h->splitk_ws, slab) != FRP_OK) return;
-    p.ksplit = ps.n_dev ? -1 : ks;
+    const int ktot = op.ksize * op.ksize * op.cin;
+    const FcSplitChoice c = fc_splitk_choice(ps.batch, out.h * out.w, ps.n_dev != nullptr, op.cout, ktot, op.flags, op.res_buf >= 0, h->n_cu);
+    if (c.ksplit == 0 || in.h != 1 || in.w != 1) return;
+    if (ensure(h, h->splitk_ws, c.ws_bytes) != FRP_OK) return;
+    p.ksplit = c.ksplit;
     p.out = h->splitk_ws.p;
     fc.ksplit = p.ksplit;
     fc.bias = p.bias;
-    fc.ktot = op.ksize * op.ksize * op.cin;
+    fc.ktot = ktot;
 }
 
 // what a launched op is charged for: algorithmic FLOPs on the unpadded channels

@@ -53,6 +53,14 @@ struct FcSplitK {
     const float* bias = nullptr;
 };
 
+// What a launch of the FC shape gets (net_program.cpp: pick_fc_splitk; kernel_api.cpp: frp_debug_fc_l2norm): `ksplit` as ConvParams and
+// launch_l2norm take it (0: no split, the conv's own fp32 epilogue), `ws_bytes` of slab workspace [ks][batch][cout] fp32
+struct FcSplitChoice {
+    int ksplit;
+    size_t ws_bytes;
+};
+FcSplitChoice fc_splitk_choice(int batch, int out_pixels, bool device_count, int cout, int ktot, int flags, bool has_res, int n_cu);
+
 // Everything a pass does on the host besides launching.  The walk fills one, run_net applies it - for a launched, a capturing and a
 // replayed pass alike.
 struct PassEffects {

@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
-    "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
+    "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_debug_fc_l2norm", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
     "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
@@ -218,6 +218,7 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "frp_process_pyramid"):  # (as frp_match_within below: an older A/B partner build has none)
         lib.frp_process_pyramid.argtypes = [vp, i32, vp, i32, i32, f32, f32, u32]
         lib.frp_debug_pyramid_merge.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]
+        lib.frp_debug_fc_l2norm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     lib.frp_get_head_map.argtypes = [vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32)]
     lib.frp_debug_jpeg_device_batches.argtypes = [vp]
     lib.frp_debug_jpeg_device_batches.restype = C.c_int64
@@ -689,6 +690,25 @@ class Engine:
         self._chk(self._lib.frp_debug_pyramid_merge(self._h, S, _ptr(hw), B, P, int(frame_hw[0]), int(frame_hw[1]), _ptr(boxes), _ptr(kps),
                                                     _ptr(scores), _ptr(counts), K, nms_iou, _ptr(ob), _ptr(ok), _ptr(osc), _ptr(oc)))
         return ob, ok, osc, oc
+
+    def debug_fc_l2norm(self, x16, w16, bias, n: int, mode="host", flags: int = 0):
+        """the embedder's tail alone (frp.h: frp_debug_fc_l2norm): x16 [cap, K] fp16, w16 [D, K] fp16, bias [D] fp32, n <= cap rows exist.
+        mode "host" / "device" / "none" / an int s >= 2 (a forced split factor); flags: the tile-class bits 17 / 18 of conv2d
+        -> (emb [cap, D] float32, emb16 [cap, D] float16, n_cu, the factor the host's rule gives n rows); rows at or beyond n of both
+        outputs hold the 0xFF fill"""
+        x16 = np.ascontiguousarray(x16, np.float16)
+        w16 = np.ascontiguousarray(w16, np.float16)
+        bias = np.ascontiguousarray(bias, np.float32)
+        if x16.ndim != 2 or w16.ndim != 2 or x16.shape[1] != w16.shape[1] or bias.shape != (w16.shape[0],):
+            raise ValueError("x16 [cap, K], w16 [D, K], bias [D]")
+        cap, K = x16.shape
+        D = w16.shape[0]
+        m = {"host": 0, "device": -1, "none": 1}.get(mode, mode)
+        emb, emb16 = np.zeros((cap, D), np.float32), np.zeros((cap, D), np.float16)
+        ncu, factor = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.frp_debug_fc_l2norm(self._h, _ptr(x16), _ptr(w16), _ptr(bias), cap, int(n), K, D, int(m), int(flags), _ptr(emb),
+                                                _ptr(emb16), C.byref(ncu), C.byref(factor)))
+        return emb, emb16, int(ncu.value), int(factor.value)
 
     def process_frames_pyramid(self, frames, scales=(1.0, 0.5, 0.25), max_faces=10, det_thresh=0.5, nms_iou=0.4,
                                per_scale=64, flags=0, on_device: bool = False):

@@ -357,6 +357,23 @@ int frp_debug_pyramid_merge(frp_handle* h, int32_t n_scales, const int32_t* det_
                             const int32_t* counts, int32_t max_faces, float nms_iou,
                             float* out_boxes, float* out_kps, float* out_scores, int32_t* out_counts);
 
+/* the embedder's tail alone on host operands (parity tests): the FC as the pipeline launches it - a 1x1 conv with fp32 output, split
+ * over K where the pass's own choice splits it - and the l2norm kernel behind it; needs neither weights nor resident frames.
+ * x [cap, K] fp16, w [D, K] fp16, bias [D] fp32 (K and D multiples of 8, D <= 1024; a split needs K % 64 == 0), n <= cap rows exist.
+ * mode FRP_FC_HOST_COUNT: launched for n rows with the factor of n chosen on the host, as a forced-K process call does;
+ *      FRP_FC_DEVICE_COUNT: launched for the capacity with n in device memory, both kernels choose the factor there (threshold mode);
+ *      1: no split - the conv's fp32 epilogue adds the bias, the plain l2norm; s >= 2: the factor s (FRP_ERR_INVALID where the conv
+ *      launch refuses it: s must divide K / 64).
+ * flags: bits 17 / 18 of frp_conv2d_nhwc (the tile class; an fp32-output launch takes the 256-pixel tiles whatever they say).
+ * emb [cap, D] fp32 and emb_f16 [cap, D]: the slab workspace and both outputs are filled with 0xFF bytes on the device before the
+ * launches, so a slab read without having been written shows as NaN and the rows at or beyond n come back as 0xFF.  n == 0 with a
+ * host count launches nothing.  *n_cu: the handle's compute units; *host_factor: the factor the host's rule gives n rows (1: none).
+ * FRP_ERR_INVALID - nothing launched - for n > cap, D > 1024 and anything else out of range. */
+#define FRP_FC_HOST_COUNT 0
+#define FRP_FC_DEVICE_COUNT (-1)
+int frp_debug_fc_l2norm(frp_handle* h, const void* x_f16, const void* w_f16, const float* bias, int32_t cap, int32_t n, int32_t K,
+                        int32_t D, int32_t mode, int32_t flags, float* emb, void* emb_f16, int32_t* n_cu, int32_t* host_factor);
+
 /* raw detector head maps of the last detect/process call, per stride level 0..2:
  * [B, H/stride, W/stride, 32] fp16 (parity tests) */
 int frp_get_head_map(frp_handle* h, int32_t level, void* out_f16, int64_t out_bytes, int32_t* hl, int32_t* wl);

@@ -236,6 +236,7 @@ int run_align(frp_handle* h, int K, int n, const int32_t* n_dev, uint32_t flags,
 int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t flags) {
     const int B = h->rB;
     const bool want_within = (flags & FRP_FLAG_WITHIN) && !(flags & FRP_FLAG_NO_MATCH);
+    const bool want_groups = (flags & FRP_FLAG_GROUPS) != 0;          // (checked by the caller: check_match_flags)
     // a device-count pass that nobody fetched or synchronised yet (two process calls queued back to back): its count and its
     // counter corrections live in single slots (h_nfaces, Pass) this pass is about to reuse - settle it first
     FRPCHK(settle_count(h, false));
@@ -262,7 +263,7 @@ int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t fl
         FRPCHK(run_align(h, K, n, n_dev, flags, h->emb.bufs[h->emb.in_buf].p));
         rec(h, EV_ALIGN);
         FRPCHK(run_embed(h, sw, n, n_dev, n_known >= 0 ? n_known : B * K));
-        if (!(flags & FRP_FLAG_NO_MATCH) && h->g_rows > 0) FRPCHK(match_pass(h, sw, n, n_dev, want_within));
+        if (!(flags & FRP_FLAG_NO_MATCH) && h->g_rows > 0) FRPCHK(match_pass(h, sw, n, n_dev, want_within, want_groups));
         rec(h, EV_MATCH);
     } else {
         rec(h, EV_ALIGN); rec(h, EV_EMB); rec(h, EV_L2); rec(h, EV_MATCH);
@@ -286,16 +287,22 @@ int begin_detect_only_pass(frp_handle* h, int B, int K) {
     return rc;
 }
 
-// a flagged pass needs frp_set_within; checked before a pass overwrites anything of the last one
-int check_within_flag(frp_handle* h, uint32_t flags) {
+// a flagged pass needs frp_set_within / frp_set_frame_groups for its B frames; checked before a pass launches anything or overwrites
+// anything of the last one
+int check_match_flags(frp_handle* h, uint32_t flags, int B) {
     if ((flags & FRP_FLAG_WITHIN) && !(flags & FRP_FLAG_NO_MATCH) && h->m.within_cap <= 0)
         return fail(h, FRP_ERR_INVALID, "FRP_FLAG_WITHIN: call frp_set_within first");
+    if (flags & FRP_FLAG_GROUPS) {
+        if (flags & FRP_FLAG_NO_MATCH) return fail(h, FRP_ERR_INVALID, "FRP_FLAG_GROUPS has no meaning together with FRP_FLAG_NO_MATCH");
+        if (h->m.frame_groups.empty()) return fail(h, FRP_ERR_INVALID, "FRP_FLAG_GROUPS: call frp_set_frame_groups first");
+        if ((int)h->m.frame_groups.size() != B) return fail(h, FRP_ERR_INVALID, "FRP_FLAG_GROUPS: frp_set_frame_groups was called for another B");
+    }
     return FRP_OK;
 }
 
 int run_pipeline(frp_handle* h, int K, float det_thresh, float nms_iou, uint32_t flags) {
     const Switches sw = read_switches();
-    FRPCHK(check_within_flag(h, flags));
+    FRPCHK(check_match_flags(h, flags, h->rB));
     if (h->det_scaled) FRPCHK(select_det_source(h, h->rH, h->rW));     // the fused path always detects at full size
     FRPCHK(run_detect(h, sw, K, det_thresh, nms_iou, flags));
     const long A = (long)h->det.dims[h->hdr.det_head_buf[0]].h * h->det.dims[h->hdr.det_head_buf[0]].w * 2;
@@ -549,11 +556,12 @@ void frp_destroy(frp_handle* h) {
     for (DevBuf& b : h->det.bufs) release(b);
     for (DevBuf& b : h->emb.bufs) release(b);
     DevBuf* all[] = {&h->wdata, &h->frames, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
-                     &h->pyr_boxes, &h->pyr_kps, &h->pyr_scores, &h->pyr_counts, &h->m.q16, &h->m.part_cos, &h->m.part_idx, &h->m.best_cos, &h->m.best_idx, &h->m.hit_cnt, &h->m.hit_idx, &h->m.hit_cos, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
+                     &h->pyr_boxes, &h->pyr_kps, &h->pyr_scores, &h->pyr_counts, &h->m.q16, &h->m.part_cos, &h->m.part_idx, &h->m.best_cos, &h->m.best_idx, &h->m.hit_cnt, &h->m.hit_idx, &h->m.hit_cos, &h->m.q_groups, &h->m.frame_groups_dev, &h->g_groups_dev, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
                      &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->det_hashes, &h->quality_in, &h->quality_out,
                      &h->jenc_in, &h->jenc_coef, &h->jenc_work, &h->jenc_bits, &h->jenc_out};
     for (DevBuf* b : all) release(*b);
     for (int i = 0; i < EV_COUNT; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
+    if (h->m.frame_groups_ev) (void)hipEventDestroy(h->m.frame_groups_ev);
     if (h->h_nfaces) (void)hipHostFree(h->h_nfaces);
     if (h->pin_stage) (void)hipHostFree(h->pin_stage);
     release_ingest(h);
@@ -608,7 +616,7 @@ int frp_process_pyramid(frp_handle* h, int32_t n_scales, const int32_t* det_hw, 
                         float nms_iou, uint32_t flags) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
-    FRPCHK(check_within_flag(h, flags));
+    FRPCHK(check_match_flags(h, flags, h->rB));
     if (!h->have_weights) return fail(h, FRP_ERR_INVALID, "process_pyramid: no weights loaded");
     if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "process_pyramid: no resident frames (call frp_upload_frames)");
     if (n_scales < 1 || n_scales > FRP_PYRAMID_MAX_SCALES || !det_hw) return fail(h, FRP_ERR_INVALID, "process_pyramid: 1 to 4 scales");
@@ -652,6 +660,7 @@ int frp_process_frames(frp_handle* h, const uint8_t* bgr, int32_t B, int32_t H, 
                        float* scores, int32_t* counts, float* emb, int32_t* match_idx, float* match_cos) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    FRPCHK(check_match_flags(h, flags, B));          // (ahead of the upload: a refused call leaves the resident frames alone too)
     FRPCHK(upload_frames(h, bgr, B, H, W, row_stride));
     FRPCHK(run_pipeline(h, max_faces, det_thresh, nms_iou, flags));
     FRPCHK(fetch_results(h, boxes, kps, scores, counts, emb, match_idx, match_cos));
@@ -705,7 +714,7 @@ int frp_finish_faces(frp_handle* h, int32_t B_in, const float* boxes, const floa
     if (B_in != h->rB) return fail(h, FRP_ERR_INVALID, "finish_faces: face list sized for another resident batch");
     int n;
     FRPCHK(validate_face_list(h, kps, counts, max_faces, n));
-    FRPCHK(check_within_flag(h, flags));
+    FRPCHK(check_match_flags(h, flags, h->rB));
     FRPCHK(upload_face_list(h, max_faces, boxes, kps, scores, counts));
     rec(h, EV_DEC);
     FRPCHK(run_faces(h, read_switches(), max_faces, n, flags));

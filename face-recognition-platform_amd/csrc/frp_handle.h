@@ -60,6 +60,15 @@ struct Matcher {
     float within_min_cos = 0.f;
     int within_cap = 0;                                  // 0: frp_set_within has not been called
     frp::DevBuf hit_cnt, hit_idx, hit_cos;               // [n], [n x cap], [n x cap] per compact face of the last flagged pass
+    // gallery groups (frp_match_groups, FRP_FLAG_GROUPS): the query masks of the last grouped launch, [round_up(n, 32)] - of a pass:
+    // one per compact face (launch_face_groups), alive as long as q16 holds the pass's queries (a rebuilt list needs both)
+    frp::DevBuf q_groups;
+    // frp_set_frame_groups: the frame masks for the flagged passes to come (empty: not set) and their device copy, uploaded by the
+    // first pass after a change; frame_groups_ev: that copy has read the host vector (waited for before the vector changes again)
+    std::vector<uint32_t> frame_groups;
+    frp::DevBuf frame_groups_dev;
+    bool frame_groups_dirty = false, frame_groups_copying = false;
+    hipEvent_t frame_groups_ev = nullptr;
 };
 
 // Everything that describes the last pass, i.e. what the handle's result buffers hold.  Started as a whole where a pass begins
@@ -72,6 +81,7 @@ struct Pass {
     int within_cap = 0;          // list size of the pass, 0: it ran without FRP_FLAG_WITHIN
     bool within_lists = false;   // ... and it matched (faces and a gallery): hit_* hold its lists
     bool q16_of_pass = false;    // q16 still holds its queries (a list that overflowed is rebuilt from them at fetch time)
+    bool groups = false;         // it matched with FRP_FLAG_GROUPS: q_groups holds its faces' masks
     // device-count pass: the embedder's FLOPs were charged for pend_cap faces, corrected once the count is known (settle_count)
     int pend_cap = 0;
     double pend_flops = 0.0, pend_f8flops = 0.0;
@@ -131,6 +141,12 @@ struct frp_handle {
     // exact compat rows (frp_gallery_exact): float64 [g_rows x 512] as enrolled, next to the unit fp16 snapshot
     bool g_exact = false;
     frp::DevBuf gx, gx_q, gx_out;
+    // gallery groups: one mask per row, ALL unless frp_gallery_set_groups said otherwise.  The host table is what the entry points
+    // edit and read; g_groups_dev is its device copy for the grouped kernels - [>= round_up(g_rows, 32)], rows >= g_rows hold 0 -
+    // built by the first grouped match behind a new snapshot (row_groups_device) and patched in place by the single-row updates
+    std::vector<uint32_t> g_groups;
+    frp::DevBuf g_groups_dev;
+    bool g_groups_dev_ok = false;
     // profiling
     hipEvent_t ev[EV_COUNT]{};
     frp_counters ctr{};
@@ -211,7 +227,10 @@ FRP_LOCAL int ensure_pinned(frp_handle* h, size_t bytes);           // frp_api.c
 FRP_LOCAL int stage_queries(frp_handle* h, int n, const float* rows = nullptr, const void* f16 = nullptr);
 // match_api.cpp: the match of a pass (run_faces) - top-1 of the n queries in q16 (n_dev: the count in device memory) and, `within`,
 // the hit lists of frp_set_within in the same launch; marks the pass as matched
-FRP_LOCAL int match_pass(frp_handle* h, const frp::Switches& sw, int n, const int32_t* n_dev, bool within);
+// `groups`: over the rows the frame mask of each face permits (frp_set_frame_groups; the caller has checked that B masks are set)
+FRP_LOCAL int match_pass(frp_handle* h, const frp::Switches& sw, int n, const int32_t* n_dev, bool within, bool groups);
+// gallery_api.cpp: the row masks in device memory, for a grouped match launch (built or brought up to date where they are not)
+FRP_LOCAL int row_groups_device(frp_handle* h, const uint32_t** out);
 inline void rec(frp_handle* h, int which) { if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream); }   // a stage event (timers on)
 FRP_LOCAL bool init_ingest(frp_handle* h);                          // ingest_api.cpp: the copy stream and its events (frp_create)
 FRP_LOCAL void release_ingest(frp_handle* h);                       // ... and everything `in` holds (frp_destroy)

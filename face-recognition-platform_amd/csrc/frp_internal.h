@@ -547,11 +547,23 @@ struct MatchParams {
     int32_t* hit_idx;         // [M, cap] ordered by (cosine desc, row asc), -1 beyond min(count, cap); a query with count > cap holds
     float* hit_cos;           // [M, cap] `cap` of its hits, which ones is a race: the caller rebuilds it (launch_topk_rows), -2.0 beyond
 };
+// Gallery groups of a match launch (both null: off - the kernels above, launched with MatchParams alone; both set: their GROUPS
+// instantiations): row r is permitted for query q iff row_groups[r] & q_groups[q] != 0, and top-1, the hit lists and their counts are
+// taken over the permitted rows only; all_scores then holds a quiet NaN where a row is not permitted.
+// (A kernel argument of its own, not two more fields of MatchParams: the ungrouped kernels' register allocation depends on the size
+// of their parameter block - match_top1_within_kernel goes from 2 spilled registers to 524 with 16 more bytes of it.)
+struct MatchGroups {
+    const uint32_t* row_groups;   // [>= round_up(N, 32)], rows >= N hold 0
+    const uint32_t* q_groups;     // [>= M]
+};
 #define FRP_WITHIN_MAX_CAP 64    // == FRP_MAX_TOPK (frp.h): one lane per list entry in the sort, and what launch_topk_rows rebuilds
 int match_num_workgroups(long N);
 #define FRP_MATCH_TOP1_MAX 512   // queries per launch the persistent top-1 kernel covers (the only one that takes n_dev)
 // per_tile_only: never the persistent top-1 kernel (A/B runs: Switches::match_v1); a launch with n_dev then fails
-hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t stream);
+hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t stream, MatchGroups groups = MatchGroups{nullptr, nullptr});
+// q_groups[f] = frame_groups[face_slot[f] / K] for the n faces of a compact face list (n_dev: the count in device memory, n the capacity)
+hipError_t launch_face_groups(const uint32_t* frame_groups, int B, const int32_t* face_slot, int K, int n, const int32_t* n_dev,
+                              uint32_t* q_groups, hipStream_t stream);
 // top-k of each row of a device score matrix [M x N] by (cosine desc, row asc); -1 / -2.0 beyond N entries
 hipError_t launch_topk_rows(const float* scores, int M, long N, int k, int32_t* idx_out, float* cos_out, hipStream_t stream);
 

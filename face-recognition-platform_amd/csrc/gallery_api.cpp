@@ -89,6 +89,22 @@ void install_gallery(frp_handle* h, DevBuf rows, DevBuf exact, int64_t n) {
     release(h->gx);
     h->gx = exact;
     h->g_rows = n;
+    h->g_groups.assign((size_t)n, FRP_GROUPS_ALL);      // rows that arrive without a mask are members of every group
+    h->g_groups_dev_ok = false;
+}
+
+// Rows [first, first + n) of the host mask table have changed (n may reach one past g_rows: the slot a removed last row left, which
+// holds 0 on the device): the device copy follows where it exists and has room, else the next grouped match rebuilds it.
+int push_groups(frp_handle* h, int64_t first, int64_t n) {
+    if (!h->g_groups_dev_ok || n <= 0) return FRP_OK;
+    if ((size_t)(first + n) * 4 > h->g_groups_dev.cap) { h->g_groups_dev_ok = false; return FRP_OK; }
+    std::vector<uint32_t> v((size_t)n, 0u);
+    for (int64_t i = 0; i < n && first + i < h->g_rows; ++i) v[(size_t)i] = h->g_groups[(size_t)(first + i)];
+    h->g_groups_dev_ok = false;                          // (a failed copy leaves no half-patched table in use)
+    HIPCHK(h, hipMemcpyAsync((uint32_t*)h->g_groups_dev.p + first, v.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->g_groups_dev_ok = true;
+    return FRP_OK;
 }
 
 // frp_gallery_update_row: `b` (the snapshot or its exact copy) moves to a fresh buffer of `cap_rows` rows that holds its live rows
@@ -123,6 +139,21 @@ int frp::upload_rows_normalized(frp_handle* h, const float* rows, int64_t n, _Fl
         if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("gallery_normalize: ") + hipGetErrorString(e));
         HIPCHK(h, hipStreamSynchronize(h->stream));   // scratch is reused by the next chunk
     }
+    return FRP_OK;
+}
+
+int frp::row_groups_device(frp_handle* h, const uint32_t** out) {
+    if (!h->g_groups_dev_ok) {
+        // room for the snapshot's row capacity (appends patch in place), a multiple of 32 rows: a wave's block of masks never leaves it
+        const size_t cap_rows = std::max<size_t>(h->gallery.cap / ((size_t)FRP_EMB_DIM * 2), (size_t)h->g_rows);
+        FRPCHK(ensure(h, h->g_groups_dev, (cap_rows + 31) / 32 * 32 * 4));
+        HIPCHK(h, hipMemsetAsync(h->g_groups_dev.p, 0, h->g_groups_dev.cap, h->stream));
+        if (h->g_rows > 0)
+            HIPCHK(h, hipMemcpyAsync(h->g_groups_dev.p, h->g_groups.data(), (size_t)h->g_rows * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));      // (the table may change as soon as this call returns)
+        h->g_groups_dev_ok = true;
+    }
+    *out = (const uint32_t*)h->g_groups_dev.p;
     return FRP_OK;
 }
 
@@ -306,7 +337,11 @@ int frp_gallery_update_row(frp_handle* h, int64_t row, const void* emb, int32_t 
         FRPCHK(grow_rows(h, h->gx, std::max<size_t>(h->gallery.cap / ((size_t)d * 2), (size_t)row + 1), (size_t)d * 8, "exact gallery grow: "));
     FRPCHK(upload_rows_normalized(h, unit, 1, (_Float16*)h->gallery.p + row * d));
     if (h->g_exact) FRPCHK(upload_rows_exact(h, emb, 1, dtype, (double*)h->gx.p + row * d));
-    if (row == h->g_rows) h->g_rows += 1;
+    if (row == h->g_rows) {          // an append is a member of every group; an overwrite keeps the row's mask
+        h->g_groups.push_back(FRP_GROUPS_ALL);
+        h->g_rows += 1;
+        FRPCHK(push_groups(h, row, 1));
+    }
     return FRP_OK;
 }
 
@@ -324,8 +359,11 @@ int frp_gallery_remove_row(frp_handle* h, int64_t row) {
                                      hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+    h->g_groups[(size_t)row] = h->g_groups[(size_t)last];      // the mask moves with the row
+    h->g_groups.pop_back();
     h->g_rows = last;
-    return FRP_OK;
+    FRPCHK(push_groups(h, row, 1));
+    return push_groups(h, last, 1);                            // (rows >= g_rows hold 0 on the device)
 }
 
 int64_t frp_gallery_size(const frp_handle* h) { return h ? h->g_rows : -1; }
@@ -338,6 +376,23 @@ int frp_gallery_get(frp_handle* h, void* out_f16, int64_t first_row, int64_t n_r
     HIPCHK(h, hipMemcpyAsync(out_f16, (_Float16*)h->gallery.p + first_row * FRP_EMB_DIM, (size_t)n_rows * FRP_EMB_DIM * 2,
                              hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return FRP_OK;
+}
+
+int frp_gallery_set_groups(frp_handle* h, const uint32_t* groups, int64_t first_row, int64_t n_rows) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    FRPCHK(refuse_while_reserved(h));
+    if (!groups || first_row < 0 || n_rows < 0 || first_row + n_rows > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery range");
+    std::copy(groups, groups + n_rows, h->g_groups.begin() + first_row);
+    return push_groups(h, first_row, n_rows);
+}
+
+int frp_gallery_get_groups(frp_handle* h, uint32_t* out, int64_t first_row, int64_t n_rows) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!out || first_row < 0 || n_rows < 0 || first_row + n_rows > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery range");
+    std::copy(h->g_groups.begin() + first_row, h->g_groups.begin() + first_row + n_rows, out);
     return FRP_OK;
 }
 

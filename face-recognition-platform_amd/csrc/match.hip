@@ -46,20 +46,44 @@ __device__ __forceinline__ void within_emit(const MatchParams& p, int q, int g, 
     }
 }
 
+// Gallery groups (frp.h: frp_match_groups, FRP_FLAG_GROUPS): row r is PERMITTED for query q iff row_groups[r] & q_groups[q] != 0, and
+// the GROUPS instantiations of both MFMA kernels select over the permitted rows only.  A wave keeps the masks of its 32 rows in LDS
+// (rows past N: 0) and, per query tile, reads the masks of its lane's 16 accumulator rows - rows g0 + (e&3) + 8*(e>>2) + 4*fh: four
+// aligned 16-byte reads, one per e>>2 - and sets the accumulator elements that are not permitted to -3.0, the value rows past N get:
+// below every bound (min_cos >= -2) and never greater than the -3.0 the search starts from.  Everything behind that is the ungrouped
+// code.  (In LDS and re-read per tile rather than resident: 16 more registers do not fit next to 128 fragment registers, the
+// accumulator and - in the persistent kernel - 32 running winners.)
+__device__ __forceinline__ void mask_tile(floatx16& acc, const uint32_t* wave_masks, int fh, uint32_t qg) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint4 m = *reinterpret_cast<const uint4*>(wave_masks + 8 * j + 4 * fh);
+        acc[4 * j + 0] = (m.x & qg) ? acc[4 * j + 0] : -3.0f;
+        acc[4 * j + 1] = (m.y & qg) ? acc[4 * j + 1] : -3.0f;
+        acc[4 * j + 2] = (m.z & qg) ? acc[4 * j + 2] : -3.0f;
+        acc[4 * j + 3] = (m.w & qg) ? acc[4 * j + 3] : -3.0f;
+    }
+}
+
 // WITHIN: the same tiles, the same top-1 partials, plus the "within" epilogue (hit lists; no score matrix) - see below
-template <bool WITHIN>
-__device__ __forceinline__ void match_tiles(MatchParams p) {
+// GROUPS: over the permitted rows only (above); its all_scores epilogue writes a quiet NaN for a row that is not permitted - what
+// topk_rows_kernel never selects - into the caller's scratch matrix (grouped top-k, the grouped rebuild of an overflowed list)
+template <bool WITHIN, bool GROUPS>
+__device__ __forceinline__ void match_tiles(MatchParams p, MatchGroups mg) {
     // two DISTINCT arrays: with one runtime-indexed array the compiler cannot tell the DMA target from the tile being
     // read and waits for the prefetch (vmcnt(0)) before the first fragment read of every tile
     __shared__ __attribute__((aligned(16))) unsigned char qs0[MT_Q * 1024];
     __shared__ __attribute__((aligned(16))) unsigned char qs1[MT_Q * 1024];
     __shared__ float red_cos[4][MT_Q];
     __shared__ int red_idx[4][MT_Q];
+    __shared__ __attribute__((aligned(16))) uint32_t row_masks[GROUPS ? MT_G : 4];
 
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int fr = lane & 31, fh = lane >> 5;
     const long g0 = (long)blockIdx.x * MT_G + wave * 32;
+    if constexpr (GROUPS) {          // this wave's 32 masks (read by this wave alone, behind the barrier below)
+        if (lane < 32) row_masks[wave * 32 + fr] = g0 + fr < p.N ? mg.row_groups[g0 + fr] : 0u;
+    }
 
     // ---- gallery rows -> registers (A fragments), rows past N clamped (masked in the epilogue)
     half8 gf[32];
@@ -88,9 +112,12 @@ __device__ __forceinline__ void match_tiles(MatchParams p) {
     q_dma(0, qs0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    if constexpr (GROUPS) __syncthreads();
 
     for (int qt = 0; qt < nqt; ++qt) {
         const bool odd = qt & 1;
+        uint32_t qg = 0;
+        if constexpr (GROUPS) qg = qt * MT_Q + fr < p.M ? mg.q_groups[qt * MT_Q + fr] : 0u;      // (ahead of the DMA: its wait is not the DMA's)
         if (qt + 1 < nqt) { if (odd) q_dma(qt + 1, qs0); else q_dma(qt + 1, qs1); }
         floatx16 acc;
 #pragma unroll
@@ -112,12 +139,21 @@ __device__ __forceinline__ void match_tiles(MatchParams p) {
         const int q = qt * MT_Q + fr;
         float best = -3.0f;
         int bidx = 0x7fffffff;
+        if constexpr (GROUPS) {      // (the mask address from an opaque copy of the lane index: not one more register held across the tiles)
+            int l = lane;
+            asm volatile("" : "+v"(l));
+            mask_tile(acc, row_masks + wave * 32, l >> 5, qg);
+        }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const long g = g0 + (e & 3) + 8 * (e >> 2) + 4 * fh;
             const float v = acc[e];
             if (g < p.N) {
-                if (!WITHIN && p.all_scores && q < p.M) p.all_scores[(long)q * p.N + g] = v;
+                if constexpr (GROUPS) {      // (a score is a cosine of unit rows or NaN: -3.0 is the mask's alone)
+                    if (!WITHIN && p.all_scores && q < p.M) p.all_scores[(long)q * p.N + g] = v == -3.0f ? __builtin_nanf("") : v;
+                } else {
+                    if (!WITHIN && p.all_scores && q < p.M) p.all_scores[(long)q * p.N + g] = v;
+                }
                 if (v > best) { best = v; bidx = (int)g; }   // rows visited in increasing g: ties keep the lower index
             }
         }
@@ -157,8 +193,10 @@ __device__ __forceinline__ void match_tiles(MatchParams p) {
         __builtin_amdgcn_s_barrier();
     }
 }
-__global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) { match_tiles<false>(p); }
-__global__ __launch_bounds__(256, 2) void match_within_kernel(MatchParams p) { match_tiles<true>(p); }
+__global__ __launch_bounds__(256, 2) void match_kernel(MatchParams p) { match_tiles<false, false>(p, MatchGroups{nullptr, nullptr}); }
+__global__ __launch_bounds__(256, 2) void match_within_kernel(MatchParams p) { match_tiles<true, false>(p, MatchGroups{nullptr, nullptr}); }
+__global__ __launch_bounds__(256, 2) void match_groups_kernel(MatchParams p, MatchGroups mg) { match_tiles<false, true>(p, mg); }
+__global__ __launch_bounds__(256, 2) void match_within_groups_kernel(MatchParams p, MatchGroups mg) { match_tiles<true, true>(p, mg); }
 
 // Top-1 only, M <= 512 queries (the streaming path: 320 faces per step): PERSISTENT workgroups of eight waves (one per CU;
 // a query tile in LDS serves 256 gallery rows) with the running winner of every query kept in REGISTERS across all the
@@ -176,10 +214,13 @@ __global__ __launch_bounds__(256, 2) void match_within_kernel(MatchParams p) { m
 #define MT_MAXQT 16
 #define MT_NW 8            // waves per workgroup: one query tile in LDS serves 256 gallery rows
 static_assert(MT_MAXQT * MT_Q == FRP_MATCH_TOP1_MAX, "frp_internal.h: FRP_MATCH_TOP1_MAX");
-template <bool WITHIN>
-__device__ __forceinline__ void match_top1_rounds(MatchParams p) {
+// GROUPS (see mask_tile): the query masks of the launch sit in LDS (one read per tile), a wave's 32 row masks are replaced per round.
+template <bool WITHIN, bool GROUPS>
+__device__ __forceinline__ void match_top1_rounds(MatchParams p, MatchGroups mg) {
     __shared__ __attribute__((aligned(16))) unsigned char qs0[MT_Q * 1024];
     __shared__ __attribute__((aligned(16))) unsigned char qs1[MT_Q * 1024];
+    __shared__ __attribute__((aligned(16))) uint32_t row_masks[GROUPS ? MT_NW * 32 : 4];
+    __shared__ uint32_t q_masks[GROUPS ? MT_MAXQT * MT_Q : 4];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int fr = lane & 31, fh = lane >> 5;
@@ -190,6 +231,10 @@ __device__ __forceinline__ void match_top1_rounds(MatchParams p) {
         n = n < 0 ? 0 : (n > p.M ? p.M : n);
         nqt = (n + MT_Q - 1) / MT_Q;
         n_real = n;
+    }
+    if constexpr (GROUPS) {
+        for (int i = t; i < MT_MAXQT * MT_Q; i += 64 * MT_NW) q_masks[i] = i < n_real ? mg.q_groups[i] : 0u;
+        __syncthreads();
     }
     const long nb = (p.N + 31) / 32;                                // 32-row gallery blocks
     const long wstride = (long)gridDim.x * MT_NW;
@@ -227,6 +272,9 @@ __device__ __forceinline__ void match_top1_rounds(MatchParams p) {
 #pragma unroll
             for (int s = 0; s < 32; ++s) gf[s] = *reinterpret_cast<const half8*>(gp + s * 16);
         }
+        if constexpr (GROUPS) {      // written and read by this wave alone (LDS accesses of a wave complete in order); rows past N: 0
+            if (lane < 32) row_masks[wave * 32 + fr] = g0 + fr < p.N ? mg.row_groups[g0 + fr] : 0u;
+        }
         q_dma(0, qs0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -253,6 +301,31 @@ __device__ __forceinline__ void match_top1_rounds(MatchParams p) {
                     if ((s & 7) == 7) __builtin_amdgcn_sched_barrier(0);
                 }
                 // acc[e]: gallery row (e&3) + 8*(e>>2) + 4*fh of this wave's 32 (increasing in e), query column fr
+                if constexpr (GROUPS) {
+                    // The grouped epilogue: the ungrouped one below behind mask_tile (rows past N hold mask 0: the ragged block needs
+                    // nothing else).  What depends on the lane alone - the two mask addresses, the query, the lane's first row - is
+                    // derived from an opaque copy of the lane index in every tile: left to the compiler, those values (16 row indices
+                    // among them) stay in registers across the unrolled tiles, and the kernel no longer fits its 256
+                    int l = lane;
+                    asm volatile("" : "+v"(l));
+                    const int q = qt * MT_Q + (l & 31), row0 = (int)((unsigned)g0 + 4u * (unsigned)(l >> 5));      // (rows < N fit an int)
+                    mask_tile(acc, row_masks + wave * 32, l >> 5, q_masks[q]);
+                    float tm = acc[0];
+#pragma unroll
+                    for (int e = 1; e < 16; ++e) tm = fmaxf(tm, acc[e]);
+                    if (tm > best[qt]) {
+#pragma unroll
+                        for (int e = 0; e < 16; ++e)
+                            if (acc[e] > best[qt]) { best[qt] = acc[e]; bidx[qt] = row0 + (e & 3) + 8 * (e >> 2); }
+                    }
+                    if constexpr (WITHIN) {
+                        if (tm >= p.min_cos && q < n_real) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e)
+                                if (acc[e] >= p.min_cos) within_emit(p, q, row0 + (e & 3) + 8 * (e >> 2), acc[e]);
+                        }
+                    }
+                } else {
                 if (ragged) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
@@ -274,6 +347,7 @@ __device__ __forceinline__ void match_top1_rounds(MatchParams p) {
                         for (int e = 0; e < 16; ++e)
                             if (acc[e] >= p.min_cos) within_emit(p, qt * MT_Q + fr, (int)(g0 + (e & 3) + 8 * (e >> 2) + 4 * fh), acc[e]);
                     }
+                }
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the next tile's DMA has had this tile to land
                 __builtin_amdgcn_s_barrier();
@@ -309,8 +383,10 @@ __device__ __forceinline__ void match_top1_rounds(MatchParams p) {
         p.part_idx[(long)blockIdx.x * p.Mpad + q] = bi;
     }
 }
-__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_kernel(MatchParams p) { match_top1_rounds<false>(p); }
-__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_within_kernel(MatchParams p) { match_top1_rounds<true>(p); }
+__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_kernel(MatchParams p) { match_top1_rounds<false, false>(p, MatchGroups{nullptr, nullptr}); }
+__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_within_kernel(MatchParams p) { match_top1_rounds<true, false>(p, MatchGroups{nullptr, nullptr}); }
+__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_groups_kernel(MatchParams p, MatchGroups mg) { match_top1_rounds<false, true>(p, mg); }
+__global__ __launch_bounds__(64 * MT_NW, 2) void match_top1_within_groups_kernel(MatchParams p, MatchGroups mg) { match_top1_rounds<true, true>(p, mg); }
 
 // one wave per query: reduce the per-workgroup partials
 __global__ __launch_bounds__(256) void match_reduce_kernel(MatchParams p) {
@@ -364,6 +440,24 @@ __global__ __launch_bounds__(256) void within_sort_kernel(MatchParams p) {
     else if (lane < p.cap) { idx[lane] = -1; cos[lane] = -2.0f; }
 }
 
+// the query masks of a grouped pass: q_groups[f] = frame_groups[frame of compact face f] (face_slot[f] = b * K + k), for the n faces of
+// the list or - n_dev - the count in device memory, the grid then sized for the capacity n
+__global__ __launch_bounds__(256) void face_groups_kernel(const uint32_t* __restrict__ frame_groups, int B, const int32_t* __restrict__ face_slot,
+                                                          int K, int n, const int32_t* __restrict__ n_dev, uint32_t* __restrict__ q_groups) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    int nn = n;
+    if (n_dev) { nn = *n_dev; nn = nn < 0 ? 0 : (nn > n ? n : nn); }
+    if (f >= nn) return;
+    const int b = face_slot[f] / K;
+    q_groups[f] = (b >= 0 && b < B) ? frame_groups[b] : 0u;
+}
+hipError_t launch_face_groups(const uint32_t* frame_groups, int B, const int32_t* face_slot, int K, int n, const int32_t* n_dev,
+                              uint32_t* q_groups, hipStream_t stream) {
+    if (!frame_groups || !face_slot || !q_groups || B <= 0 || K <= 0 || n <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(face_groups_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, frame_groups, B, face_slot, K, n, n_dev, q_groups);
+    return hipGetLastError();
+}
+
 static int match_cu_count(int dev) {
     static int cached[64] = {};
     if (dev < 0 || dev >= 64) return 0;
@@ -377,7 +471,7 @@ static int match_cu_count(int dev) {
 
 int match_num_workgroups(long N) { return (int)((N + MT_G - 1) / MT_G); }
 
-hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t stream) {
+hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t stream, MatchGroups mg) {
     if (p.N <= 0 || p.M <= 0 || !p.gallery || !p.q || !p.part_cos || !p.part_idx || !p.best_cos || !p.best_idx)
         return hipErrorInvalidValue;
     if (p.Mpad % MT_Q != 0 || p.Mpad < p.M || p.n_wg != match_num_workgroups(p.N) || p.N > 0x7fffff00L)
@@ -385,6 +479,8 @@ hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t st
     const bool within = p.hit_count != nullptr;
     if (within && (!p.hit_idx || !p.hit_cos || p.cap < 1 || p.cap > FRP_WITHIN_MAX_CAP || !(p.min_cos >= -2.0f) || p.all_scores))
         return hipErrorInvalidValue;
+    const bool groups = mg.row_groups != nullptr;          // the GROUPS instantiations: only when asked for
+    if (groups != (mg.q_groups != nullptr)) return hipErrorInvalidValue;
     MatchParams r = p;
     int dev = 0;
     if (p.n_dev && (p.all_scores || p.Mpad > MT_MAXQT * MT_Q || per_tile_only)) return hipErrorInvalidValue;   // top-1 kernel only
@@ -396,10 +492,12 @@ hipError_t launch_match(const MatchParams& p, bool per_tile_only, hipStream_t st
         const int grid = (int)(want < (long)ncu ? want : (long)ncu);          // 8 waves x ~220 registers: one workgroup per CU
         if (ncu <= 0 || grid <= 0 || grid > p.n_wg) return hipErrorInvalidValue;
         r.n_wg = grid;
-        if (within) hipLaunchKernelGGL(match_top1_within_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p);
+        if (groups) hipLaunchKernelGGL(within ? match_top1_within_groups_kernel : match_top1_groups_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p, mg);
+        else if (within) hipLaunchKernelGGL(match_top1_within_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p);
         else hipLaunchKernelGGL(match_top1_kernel, dim3(grid), dim3(64 * MT_NW), 0, stream, p);
     } else {
-        if (within) hipLaunchKernelGGL(match_within_kernel, dim3(p.n_wg), dim3(256), 0, stream, p);
+        if (groups) hipLaunchKernelGGL(within ? match_within_groups_kernel : match_groups_kernel, dim3(p.n_wg), dim3(256), 0, stream, p, mg);
+        else if (within) hipLaunchKernelGGL(match_within_kernel, dim3(p.n_wg), dim3(256), 0, stream, p);
         else hipLaunchKernelGGL(match_kernel, dim3(p.n_wg), dim3(256), 0, stream, p);
     }
     hipError_t e = hipGetLastError();

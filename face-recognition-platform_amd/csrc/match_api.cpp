@@ -66,16 +66,26 @@ int fill_match_params(frp_handle* h, const void* q, int n, Buf& part_cos, Buf& p
     return FRP_OK;
 }
 
-int launch_counted(frp_handle* h, const MatchParams& mp, bool per_tile_only, const char* what) {
-    FRPCHK(hip_rc(h, launch_match(mp, per_tile_only, h->stream), what));
-    h->ctr.match_bytes += (double)mp.N * FRP_EMB_DIM * 2;
+// the masks of a grouped launch: the row masks (brought to the device where they are not) and the n query masks in m.q_groups - copied
+// there from the host (`q_groups`), or, without, whatever the caller launches next (match_pass: launch_face_groups)
+int stage_groups(frp_handle* h, int n, const uint32_t* q_groups, MatchGroups& mg) {
+    FRPCHK(ensure(h, h->m.q_groups, (size_t)round_up(n, 32) * 4));
+    if (q_groups) HIPCHK(h, hipMemcpyAsync(h->m.q_groups.p, q_groups, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    mg.q_groups = (const uint32_t*)h->m.q_groups.p;
+    return row_groups_device(h, &mg.row_groups);
+}
+
+int launch_counted(frp_handle* h, const MatchParams& mp, bool per_tile_only, const char* what, const MatchGroups* mg = nullptr) {
+    FRPCHK(hip_rc(h, mg ? launch_match(mp, per_tile_only, h->stream, *mg) : launch_match(mp, per_tile_only, h->stream), what));
+    h->ctr.match_bytes += (double)mp.N * (FRP_EMB_DIM * 2 + (mg ? 4 : 0));
     h->ctr.match_launches += 1;
     return FRP_OK;
 }
 
 // q16 [mpad,512] holds n unit queries -> best_idx/best_cos [n] (+ the hit lists of `within`, in the same launch)
+// mg: the GROUPS form of the same launch (stage_groups)
 int run_match(frp_handle* h, const Switches& sw, int n, float* all_scores_dev, const int32_t* n_dev = nullptr,
-              const WithinArgs* within = nullptr) {
+              const WithinArgs* within = nullptr, const MatchGroups* mg = nullptr) {
     if (n <= 0) return FRP_OK;
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     Matcher& m = h->m;
@@ -88,19 +98,28 @@ int run_match(frp_handle* h, const Switches& sw, int n, float* all_scores_dev, c
         mp.min_cos = within->min_cos; mp.cap = within->cap;
         mp.hit_count = within->cnt; mp.hit_idx = within->idx; mp.hit_cos = within->cos;
     }
-    return launch_counted(h, mp, sw.match_v1 != 0, "match: ");
+    return launch_counted(h, mp, sw.match_v1 != 0, "match: ", mg);
 }
 
 // Queries `over` (indices into q16 and into the lists) have more than `cap` rows at or above the bound: which of them took the
 // slots was a race, so their lists are rebuilt as the first `cap` entries of the matcher's total order - the score rows of those
 // queries alone (the per-tile kernel's all_scores epilogue: the same bits), then launch_topk_rows.  All of those entries are hits.
-int rebuild_within_lists(frp_handle* h, const std::vector<int>& over, int cap, int32_t* hit_idx, float* hit_cos) {
+// q_groups (device, indexed like q16; null: an ungrouped match): the rebuild is grouped as well - the score rows hold a NaN where a
+// row is not permitted, which launch_topk_rows never selects.
+int rebuild_within_lists(frp_handle* h, const std::vector<int>& over, int cap, int32_t* hit_idx, float* hit_cos,
+                         const uint32_t* q_groups = nullptr) {
     const _Float16* q16 = (const _Float16*)h->m.q16.p;
     const long N = h->g_rows;
     const int total = (int)over.size();
     const int chunk = (int)std::max<long>(1, std::min<long>(total, (1L << 28) / N));      // <= 1 GiB of scores at a time
     const size_t qbytes = (size_t)round_up(chunk, 32) * FRP_EMB_DIM * 2;
-    ScopedBuf qt, all, pc, pi, bc, bi, tidx, tcos;
+    ScopedBuf qt, all, pc, pi, bc, bi, tidx, tcos, qg;
+    MatchGroups mg{nullptr, nullptr};
+    if (q_groups) {
+        FRPCHK(ensure(h, qg, (size_t)round_up(chunk, 32) * 4));
+        FRPCHK(row_groups_device(h, &mg.row_groups));
+        mg.q_groups = (const uint32_t*)qg->p;
+    }
     FRPCHK(ensure(h, qt, qbytes));
     FRPCHK(ensure(h, all, (size_t)chunk * N * 4));
     FRPCHK(ensure(h, tidx, (size_t)chunk * cap * 4));
@@ -111,10 +130,12 @@ int rebuild_within_lists(frp_handle* h, const std::vector<int>& over, int cap, i
         for (int i = 0; i < m; ++i)
             HIPCHK(h, hipMemcpyAsync((_Float16*)qt->p + (size_t)i * FRP_EMB_DIM, q16 + (size_t)over[m0 + i] * FRP_EMB_DIM, FRP_EMB_DIM * 2,
                                      hipMemcpyDeviceToDevice, h->stream));
+        for (int i = 0; q_groups && i < m; ++i)
+            HIPCHK(h, hipMemcpyAsync((uint32_t*)qg->p + i, q_groups + over[m0 + i], 4, hipMemcpyDeviceToDevice, h->stream));
         MatchParams mp;
         FRPCHK(fill_match_params(h, qt->p, m, pc, pi, bc, bi, mp));       // (the first chunk is the largest: it sizes the buffers)
         mp.all_scores = (float*)all->p;
-        FRPCHK(launch_counted(h, mp, true, "match within (overflow): "));
+        FRPCHK(launch_counted(h, mp, true, "match within (overflow): ", q_groups ? &mg : nullptr));
         FRPCHK(hip_rc(h, launch_topk_rows((const float*)all->p, m, N, cap, (int32_t*)tidx->p, (float*)tcos->p, h->stream),
                       "match within (overflow): "));
         for (int i = 0; i < m; ++i) {
@@ -141,13 +162,15 @@ int match_out(frp_handle* h, int rc, int M, int32_t* idx, float* cos, float* sco
     return FRP_OK;
 }
 
-int match_common(frp_handle* h, const float* q, int M, float* all_scores_host, int32_t* idx, float* cos) {
+int match_common(frp_handle* h, const float* q, int M, float* all_scores_host, int32_t* idx, float* cos, const uint32_t* q_groups = nullptr) {
     if (!queries_ok(q, M)) return fail(h, FRP_ERR_INVALID, "bad query arguments");
     if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
     FRPCHK(stage_queries(h, M, q));
+    MatchGroups mg{nullptr, nullptr};
+    if (q_groups) FRPCHK(stage_groups(h, M, q_groups, mg));
     ScopedBuf all;
     if (all_scores_host) FRPCHK(ensure(h, all, (size_t)M * h->g_rows * 4));
-    const int rc = run_match(h, read_switches(), M, (float*)all->p);
+    const int rc = run_match(h, read_switches(), M, (float*)all->p, nullptr, nullptr, q_groups ? &mg : nullptr);
     return match_out(h, rc, M, idx, cos, all_scores_host, all->p, "match result copy failed");
 }
 
@@ -163,6 +186,64 @@ int match_in_chunks(frp_handle* h, const float* q, int M, int chunk, Block block
     }
     (void)hipStreamSynchronize(h->stream);
     return rc;
+}
+
+// frp_match / frp_match_groups (q_groups: one mask per query, null: ungrouped)
+int match_topk(frp_handle* h, const float* q, int M, const uint32_t* q_groups, int topk, int32_t* idx, float* cos) {
+    if (topk < 1 || topk > FRP_MAX_TOPK) return fail(h, FRP_ERR_INVALID, "topk must be in 1..FRP_MAX_TOPK");
+    if (topk == 1) return match_common(h, q, M, nullptr, idx, cos, q_groups);
+    // k > 1: score matrix on the device (query chunks of <= 1 GiB of scores), then k selection passes per row
+    if (!queries_ok(q, M) || !idx || !cos) return fail(h, FRP_ERR_INVALID, "bad query arguments");
+    if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
+    const long N = h->g_rows;
+    const Switches sw = read_switches();
+    const int chunk = (int)std::max<long>(1, std::min<long>(M, (1L << 28) / N));
+    ScopedBuf all, didx, dcos;
+    FRPCHK(ensure(h, all, (size_t)chunk * N * 4));
+    FRPCHK(ensure(h, didx, (size_t)chunk * topk * 4));
+    FRPCHK(ensure(h, dcos, (size_t)chunk * topk * 4));
+    return match_in_chunks(h, q, M, chunk, [&](int m0, int m) -> int {
+        MatchGroups mg{nullptr, nullptr};
+        if (q_groups) FRPCHK(stage_groups(h, m, q_groups + m0, mg));
+        FRPCHK(run_match(h, sw, m, (float*)all->p, nullptr, nullptr, q_groups ? &mg : nullptr));
+        hipError_t e = launch_topk_rows((const float*)all->p, m, N, topk, (int32_t*)didx->p, (float*)dcos->p, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(idx + (size_t)m0 * topk, didx->p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * topk, dcos->p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        return hip_rc(h, e, "match top-k: ");
+    });
+}
+
+// frp_match_within / frp_match_within_groups
+int match_within(frp_handle* h, const float* q, int M, const uint32_t* q_groups, float min_cos, int cap, int32_t* idx, float* cos, int32_t* n_hits) {
+    if (!within_args_ok(min_cos, cap)) return fail(h, FRP_ERR_INVALID, "match_within: min_cos must be >= -2 and cap in 1..FRP_MAX_TOPK");
+    if (!queries_ok(q, M) || !idx || !cos || !n_hits) return fail(h, FRP_ERR_INVALID, "bad query arguments");
+    if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
+    const Switches sw = read_switches();
+    const int chunk = std::min<int>(M, 65536);
+    ScopedBuf dcnt, didx, dcos;
+    FRPCHK(ensure(h, dcnt, (size_t)chunk * 4));
+    FRPCHK(ensure(h, didx, (size_t)chunk * cap * 4));
+    FRPCHK(ensure(h, dcos, (size_t)chunk * cap * 4));
+    std::vector<int> over;
+    return match_in_chunks(h, q, M, chunk, [&](int m0, int m) -> int {
+        int32_t* nh = n_hits + m0;
+        const WithinArgs w{min_cos, cap, (int32_t*)dcnt->p, (int32_t*)didx->p, (float*)dcos->p};
+        MatchGroups mg{nullptr, nullptr};
+        if (q_groups) FRPCHK(stage_groups(h, m, q_groups + m0, mg));
+        FRPCHK(run_match(h, sw, m, nullptr, nullptr, &w, q_groups ? &mg : nullptr));
+        hipError_t e = hipMemcpyAsync(nh, dcnt->p, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        FRPCHK(hip_rc(h, e, "match within: "));
+        over.clear();                       // the counts are on the host: lists that overflowed are rebuilt from their score rows
+        for (int i = 0; i < m; ++i)
+            if (nh[i] > cap) over.push_back(i);
+        if (!over.empty()) FRPCHK(rebuild_within_lists(h, over, cap, (int32_t*)didx->p, (float*)dcos->p, mg.q_groups));
+        e = hipMemcpyAsync(idx + (size_t)m0 * cap, didx->p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * cap, dcos->p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        return hip_rc(h, e, "match within: ");
+    });
 }
 
 // the hit lists of the last flagged pass, compact face list -> [B][K] slots (frp.h: frp_fetch_within)
@@ -203,7 +284,8 @@ int fetch_within(frp_handle* h, int cap, int32_t* idx, float* cos, int32_t* n_hi
     if (!over.empty()) {
         if (!h->pass.q16_of_pass)
             return fail(h, FRP_ERR_INVALID, "fetch_within: a face has more hits than the list holds and a later call replaced the pass's embeddings");
-        int rc = rebuild_within_lists(h, over, cap, (int32_t*)m.hit_idx.p, (float*)m.hit_cos.p);
+        int rc = rebuild_within_lists(h, over, cap, (int32_t*)m.hit_idx.p, (float*)m.hit_cos.p,
+                                      h->pass.groups ? (const uint32_t*)m.q_groups.p : nullptr);      // (q_groups lives as long as q16_of_pass)
         if (rc == FRP_OK) rc = copy_lists();
         else (void)hipStreamSynchronize(h->stream);
         FRPCHK(rc);
@@ -225,21 +307,39 @@ int fetch_within(frp_handle* h, int cap, int32_t* idx, float* cos, int32_t* n_hi
 
 }  // namespace
 
-int frp::match_pass(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev, bool within) {
+int frp::match_pass(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev, bool within, bool groups) {
     Matcher& m = h->m;
+    MatchGroups mg{nullptr, nullptr};
+    if (groups) {          // the faces' masks from their frames' (the compact face list is on the device: so is the count, with n_dev)
+        const int B = h->pass.B;
+        if ((int)m.frame_groups.size() != B) return fail(h, FRP_ERR_INVALID, "FRP_FLAG_GROUPS: frame masks set for another batch size");
+        FRPCHK(ensure(h, m.frame_groups_dev, (size_t)B * 4));
+        if (m.frame_groups_dirty) {
+            HIPCHK(h, hipMemcpyAsync(m.frame_groups_dev.p, m.frame_groups.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+            if (!m.frame_groups_ev) HIPCHK(h, hipEventCreateWithFlags(&m.frame_groups_ev, hipEventDisableTiming));
+            HIPCHK(h, hipEventRecord(m.frame_groups_ev, h->stream));
+            m.frame_groups_copying = true;
+            m.frame_groups_dirty = false;
+        }
+        FRPCHK(stage_groups(h, n, nullptr, mg));
+        FRPCHK(hip_rc(h, launch_face_groups((const uint32_t*)m.frame_groups_dev.p, B, (const int32_t*)h->face_slot.p, h->pass.K, n, n_dev,
+                                            (uint32_t*)m.q_groups.p, h->stream), "face_groups: "));
+    }
+    const MatchGroups* pmg = groups ? &mg : nullptr;
     if (within) {          // the same kernel with the hit-list epilogue: one gallery pass for top-1 and the lists
         const int cap = m.within_cap;
         FRPCHK(ensure(h, m.hit_cnt, (size_t)n * 4));
         FRPCHK(ensure(h, m.hit_idx, (size_t)n * cap * 4));
         FRPCHK(ensure(h, m.hit_cos, (size_t)n * cap * 4));
         const WithinArgs w{m.within_min_cos, cap, (int32_t*)m.hit_cnt.p, (int32_t*)m.hit_idx.p, (float*)m.hit_cos.p};
-        FRPCHK(run_match(h, sw, n, nullptr, n_dev, &w));
+        FRPCHK(run_match(h, sw, n, nullptr, n_dev, &w, pmg));
         h->pass.within_lists = true;
         h->pass.q16_of_pass = true;
     } else {
-        FRPCHK(run_match(h, sw, n, nullptr, n_dev));
+        FRPCHK(run_match(h, sw, n, nullptr, n_dev, nullptr, pmg));
     }
     h->pass.matched = true;
+    h->pass.groups = groups;
     return FRP_OK;
 }
 
@@ -248,26 +348,14 @@ extern "C" {
 int frp_match(frp_handle* h, const float* q, int32_t M, int32_t topk, int32_t* idx, float* cos) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
-    if (topk < 1 || topk > FRP_MAX_TOPK) return fail(h, FRP_ERR_INVALID, "topk must be in 1..FRP_MAX_TOPK");
-    if (topk == 1) return match_common(h, q, M, nullptr, idx, cos);
-    // k > 1: score matrix on the device (query chunks of <= 1 GiB of scores), then k selection passes per row
-    if (!queries_ok(q, M) || !idx || !cos) return fail(h, FRP_ERR_INVALID, "bad query arguments");
-    if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
-    const long N = h->g_rows;
-    const Switches sw = read_switches();
-    const int chunk = (int)std::max<long>(1, std::min<long>(M, (1L << 28) / N));
-    ScopedBuf all, didx, dcos;
-    FRPCHK(ensure(h, all, (size_t)chunk * N * 4));
-    FRPCHK(ensure(h, didx, (size_t)chunk * topk * 4));
-    FRPCHK(ensure(h, dcos, (size_t)chunk * topk * 4));
-    return match_in_chunks(h, q, M, chunk, [&](int m0, int m) -> int {
-        FRPCHK(run_match(h, sw, m, (float*)all->p));
-        hipError_t e = launch_topk_rows((const float*)all->p, m, N, topk, (int32_t*)didx->p, (float*)dcos->p, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(idx + (size_t)m0 * topk, didx->p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * topk, dcos->p, (size_t)m * topk * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        return hip_rc(h, e, "match top-k: ");
-    });
+    return match_topk(h, q, M, nullptr, topk, idx, cos);
+}
+
+int frp_match_groups(frp_handle* h, const float* q, int32_t M, const uint32_t* q_groups, int32_t topk, int32_t* idx, float* cos) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!q_groups || !idx || !cos) return fail(h, FRP_ERR_INVALID, "match_groups: null argument");
+    return match_topk(h, q, M, q_groups, topk, idx, cos);
 }
 
 int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, int64_t n_cols) {
@@ -282,32 +370,15 @@ int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, i
 int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
-    if (!within_args_ok(min_cos, cap)) return fail(h, FRP_ERR_INVALID, "match_within: min_cos must be >= -2 and cap in 1..FRP_MAX_TOPK");
-    if (!queries_ok(q, M) || !idx || !cos || !n_hits) return fail(h, FRP_ERR_INVALID, "bad query arguments");
-    if (h->g_rows <= 0) return fail(h, FRP_ERR_NO_GALLERY, "gallery is empty");
-    const Switches sw = read_switches();
-    const int chunk = std::min<int>(M, 65536);
-    ScopedBuf dcnt, didx, dcos;
-    FRPCHK(ensure(h, dcnt, (size_t)chunk * 4));
-    FRPCHK(ensure(h, didx, (size_t)chunk * cap * 4));
-    FRPCHK(ensure(h, dcos, (size_t)chunk * cap * 4));
-    std::vector<int> over;
-    return match_in_chunks(h, q, M, chunk, [&](int m0, int m) -> int {
-        int32_t* nh = n_hits + m0;
-        const WithinArgs w{min_cos, cap, (int32_t*)dcnt->p, (int32_t*)didx->p, (float*)dcos->p};
-        FRPCHK(run_match(h, sw, m, nullptr, nullptr, &w));
-        hipError_t e = hipMemcpyAsync(nh, dcnt->p, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        FRPCHK(hip_rc(h, e, "match within: "));
-        over.clear();                       // the counts are on the host: lists that overflowed are rebuilt from their score rows
-        for (int i = 0; i < m; ++i)
-            if (nh[i] > cap) over.push_back(i);
-        if (!over.empty()) FRPCHK(rebuild_within_lists(h, over, cap, (int32_t*)didx->p, (float*)dcos->p));
-        e = hipMemcpyAsync(idx + (size_t)m0 * cap, didx->p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(cos + (size_t)m0 * cap, dcos->p, (size_t)m * cap * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        return hip_rc(h, e, "match within: ");
-    });
+    return match_within(h, q, M, nullptr, min_cos, cap, idx, cos, n_hits);
+}
+
+int frp_match_within_groups(frp_handle* h, const float* q, int32_t M, const uint32_t* q_groups, float min_cos, int32_t cap,
+                            int32_t* idx, float* cos, int32_t* n_hits) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h);
+    if (!q_groups) return fail(h, FRP_ERR_INVALID, "match_within_groups: null masks");
+    return match_within(h, q, M, q_groups, min_cos, cap, idx, cos, n_hits);
 }
 
 // Diagnostic (tests/test_gpu_match_exact.py): run_match on queries handed over as fp16 bits - no normalisation, so a test chooses both
@@ -350,6 +421,21 @@ int frp_set_within(frp_handle* h, float min_cos, int32_t cap) {
     if (!within_args_ok(min_cos, cap)) return fail(h, FRP_ERR_INVALID, "set_within: min_cos must be >= -2 and cap in 1..FRP_MAX_TOPK");
     h->m.within_min_cos = min_cos;
     h->m.within_cap = cap;
+    return FRP_OK;
+}
+
+int frp_set_frame_groups(frp_handle* h, const uint32_t* masks, int32_t B) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);
+    if (!masks || B <= 0 || B > 65536) return fail(h, FRP_ERR_INVALID, "set_frame_groups: B masks, B >= 1");
+    Matcher& m = h->m;
+    if ((int)m.frame_groups.size() == B && std::equal(masks, masks + B, m.frame_groups.begin())) return FRP_OK;      // the device copy stands
+    if (m.frame_groups_copying) {          // a pass's upload may still be reading the vector
+        HIPCHK(h, hipEventSynchronize(m.frame_groups_ev));
+        m.frame_groups_copying = false;
+    }
+    m.frame_groups.assign(masks, masks + B);
+    m.frame_groups_dirty = true;
     return FRP_OK;
 }
 

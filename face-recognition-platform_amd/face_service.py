@@ -55,6 +55,7 @@ _CAPS = {
     "face_quality": ("face_quality",),               # ... on the resident frames
     "match_within": ("match_within",),               # the stand-alone radius match (batch_compare_faces)
     "pass_within": ("fetch_within",),                # the radius match fused into a pass: set_within before it, fetch_within after it
+    "groups": ("gallery_set_groups", "set_frame_groups"),      # gallery groups: row masks, and a pass matched under per-frame masks
     "pyramid": ("process_pyramid_resident",),        # det_scales=
     "lane": ("upload_frames_async", "swap_frames", "process_resident", "fetch_results", "sequence"),    # process_stream's overlapped form
     "stage_jpeg": ("upload_jpeg_async",),            # process_frames stages a JpegBatch: upload, swap, pass, fetch under sequence()
@@ -221,6 +222,7 @@ class _Plan(NamedTuple):
     within: bool                             # the radius match is armed: set_within before the pass, fetch_within after it
     list_all: bool                           # all_matches on a gallery that has rows
     quality: bool
+    groups: Optional[Tuple[int, ...]] = None # one mask per frame (FLAG_GROUPS is in flags): set_frame_groups before the pass
 
 
 BLOCKING, STAGED, OVERLAPPED = "blocking", "staged", "overlapped"
@@ -253,6 +255,27 @@ def _check_det_scales(caps: EngineCaps, det_scales) -> Optional[Tuple[float, ...
     if not caps.pyramid:
         raise ValueError("det_scales needs an engine with process_pyramid_resident")
     return scales
+
+
+def _frame_groups(caps: EngineCaps, groups, n_frames: int) -> Optional[Tuple[int, ...]]:
+    """groups= of a frame pass as one mask per frame, or None; ValueError before anything reaches the engine"""
+    if groups is None:
+        return None
+    g = np.asarray(groups, dtype=np.uint64)
+    masks = (int(g),) * n_frames if g.ndim == 0 else tuple(int(m) for m in g.reshape(-1))
+    if len(masks) != n_frames:
+        raise ValueError(f"groups: one mask per frame ({n_frames}), not {len(masks)}")
+    if any(m > native.GROUPS_ALL for m in masks):
+        raise ValueError("groups: masks have 32 bits")
+    if not caps.groups:
+        raise ValueError("groups needs an engine with gallery groups (set_frame_groups)")
+    return masks
+
+
+def _n_frames(frames) -> int:
+    if isinstance(frames, _SOURCE_BATCHES):
+        return len(frames)
+    return 1 if frames.ndim == 3 else int(frames.shape[0])
 
 
 def _bring_in(eng, frames, staged: Optional[dict] = None) -> None:
@@ -667,8 +690,8 @@ class FaceService:
             return targets, cos_to_distance(cos[G.rows_of(targets)])
 
     # ------------------------------------------------------------------ store / delete (:344-390, :517-547)
-    def store_face(self, target_name: str, encoding: np.ndarray) -> Dict[str, Any]:
-        """:344-390.  The exclusive gallery lock (which stalls every streaming lane) is held for the duplicate scan and for
+    def store_face(self, target_name: str, encoding: np.ndarray, groups: Optional[int] = None) -> Dict[str, Any]:
+        """:344-390.  groups: the identity's group mask (Gallery.put).  The exclusive gallery lock (which stalls every streaming lane) is held for the duplicate scan and for
         the insert only; the storage write (DB round trip) and the on-disk backup run outside it, in the reference's order:
         scan -> store_embedding -> ENCODINGS[name] = ... -> backup."""
         try:
@@ -684,7 +707,7 @@ class FaceService:
                             break
             if not self._storage.store_embedding(target_name, enc.tolist()):
                 return {"success": False, "message": "Failed to store in database", "is_duplicate": is_dup}
-            already = self.ENCODINGS.put(target_name, enc)     # exclusive inside; reaches every lane's copy
+            already = self.ENCODINGS.put(target_name, enc, **({} if groups is None else {"groups": groups}))     # exclusive inside; reaches every lane's copy
             try:
                 self._backup_encoding_atomic(target_name, enc.tolist())
             except Exception as be:
@@ -869,7 +892,7 @@ class FaceService:
     # ------------------------------------------------------------------ streaming entry points (new)
     def process_frames(self, frames_bgr: np.ndarray, max_faces: int = 10, threshold: Optional[float] = None,
                        det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
-                       det_scales: Optional[Sequence[float]] = None) -> List[List[Dict[str, Any]]]:
+                       det_scales: Optional[Sequence[float]] = None, groups=None) -> List[List[Dict[str, Any]]]:
         """The live-loop body of routes/camera.py:225-259 for a batch of BGR frames, with the
         per-face compare + filter reduced to a fused device top-1: per frame a list of
         {bbox, kps, score, embedding, target, distance, cosine, confidence, match}.
@@ -880,17 +903,21 @@ class FaceService:
         frame at box_to_location(bbox), the pixel half from the batch's still-resident frames in one device call.
         det_scales=(1.0, 0.5, ...) detects at those scales of every frame (the `det_size` of an anchor-dense detector: a 4K camera
         detects at half size), merges the scales on the device and embeds from the full-resolution frames - one device pass
-        (Engine.process_pyramid_resident); 1 to 4 scales, each in (0, 2].  None: at native size only."""
+        (Engine.process_pyramid_resident); 1 to 4 scales, each in (0, 2].  None: at native size only.
+        groups=[mask per frame] (or one int for all): gallery groups - the faces of frame b are matched against the enrolled
+        identities whose mask shares a bit with groups[b] only (store_face(..., groups=), Gallery.set_groups): "target" is the best
+        PERMITTED identity and "matches" lists permitted ones, as if the gallery held nothing else; mask 0 matches nobody."""
         return self._process_frames_on(self._eng(), self.ENCODINGS.locked(), frames_bgr, max_faces, threshold, det_thresh, all_matches,
-                                       quality=quality, det_scales=det_scales)
+                                       quality=quality, det_scales=det_scales, groups=groups)
 
     def _process_frames_on(self, eng, guard, frames, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None,
-                           quality=False, det_scales=None):
+                           quality=False, det_scales=None, groups=None):
         """One frame pass on `eng`.  `take_next` / `staged` (process_stream on an engine with the lane calls): the overlapped form - this
         batch goes to the device through the engine's staging buffer (already there when the previous call staged it), the batch the
         lane will get next is claimed and its upload started on the copy stream while this batch's kernels run."""
         caps = engine_caps(eng)
         scales = _check_det_scales(caps, det_scales)
+        frame_groups = _frame_groups(caps, groups, _n_frames(frames)) if groups is not None else None
         if isinstance(frames, YuvBatch):
             frames.validate()                                          # (an odd size, mixed geometry: before anything reaches the engine)
         route = _route(caps, frames, take_next is not None and staged is not None)
@@ -902,9 +929,11 @@ class FaceService:
         # row -> name snapshot, so a concurrent delete can neither mis-attribute a face to the identity that was
         # moved into its row nor shrink the table under the lookup.
         with guard:
-            plan = self._plan(caps, len(G) > 0, max_faces, threshold, det_thresh, all_matches, quality, scales)
+            plan = self._plan(caps, len(G) > 0, max_faces, threshold, det_thresh, all_matches, quality, scales, frame_groups)
             if plan.within:
                 eng.set_within(within_min_cos(plan.tol), WITHIN_CAP)
+            if plan.groups is not None:
+                eng.set_frame_groups(plan.groups)
             if route == OVERLAPPED:
                 out, qual = self._overlapped_pass(eng, frames, plan, take_next, staged)
             elif route == STAGED:
@@ -929,13 +958,17 @@ class FaceService:
         # (lanes.Deferred); everything they need was taken above, under the guard.
         return lanes.Deferred(finish) if route == OVERLAPPED else finish()
 
-    def _plan(self, caps: EngineCaps, have_gallery: bool, max_faces, threshold, det_thresh, all_matches, quality, scales) -> "_Plan":
+    def _plan(self, caps: EngineCaps, have_gallery: bool, max_faces, threshold, det_thresh, all_matches, quality, scales,
+              frame_groups=None) -> "_Plan":
         tol = self.tolerance if threshold is None else min(self.tolerance, threshold)   # camera.py:250
         list_all = bool(all_matches) and have_gallery
         # all_matches on the device: the pass's own match kernel also lists every row within the bound (FLAG_WITHIN)
         within = bool(list_all and self.use_within and caps.pass_within)
         flags = (0 if have_gallery else native.FLAG_NO_MATCH) | (native.FLAG_WITHIN if within else 0)
-        return _Plan(max_faces, tol, DET_THRESH if det_thresh is None else det_thresh, flags, scales, within, list_all, bool(quality))
+        groups = frame_groups if have_gallery else None          # (an empty gallery: FLAG_NO_MATCH, which the grouped pass refuses)
+        if groups is not None:
+            flags |= native.FLAG_GROUPS
+        return _Plan(max_faces, tol, DET_THRESH if det_thresh is None else det_thresh, flags, scales, within, list_all, bool(quality), groups)
 
     def _overlapped_pass(self, eng, frames, plan: "_Plan", take_next, staged):
         """what only the lane form does, between the shared steps: stage the lane's next batch and build the PREVIOUS one's dicts (idle)"""
@@ -982,7 +1015,11 @@ class FaceService:
         if hits is not None:
             return {"names": names, "hits": hits}
         Q = np.concatenate([out["emb"][b, :int(c)] for b, c in enumerate(counts)])
-        return {"names": names, "dist_rows": cos_to_distance(eng.match_scores(Q)[:, G.rows_of(names)])}
+        dist = cos_to_distance(eng.match_scores(Q)[:, G.rows_of(names)])
+        if plan.groups is not None:            # the score rows ignore groups: identities the face's frame does not permit are beyond any tolerance
+            face_mask = np.repeat(np.asarray(plan.groups, np.uint32), np.minimum(counts, out["emb"].shape[1]).astype(np.int64))
+            dist = np.where((face_mask[:, None] & G.groups_table()[G.rows_of(names)][None, :]) != 0, dist, np.inf)
+        return {"names": names, "dist_rows": dist}
 
     def _stream_quality(self, eng, frames_bgr, out) -> List[Dict[str, Any]]:
         """quality dicts of a fetched batch's faces, frame by frame (the order of the face dicts), from the frames still resident on `eng`"""
@@ -994,12 +1031,13 @@ class FaceService:
 
     def process_stream(self, batches, max_faces: int = 10, threshold: Optional[float] = None,
                        det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
-                       det_scales: Optional[Sequence[float]] = None):
+                       det_scales: Optional[Sequence[float]] = None, groups=None):
         """process_frames for a stream of batches with TWO batches in flight on the GPU (lanes.py: a second handle and
         host thread; +7...13 % faces/s).  Yields one process_frames result per batch, in order.  Enrolment and deletion
         may run concurrently: they wait for the batches inside their device call and reach both gallery copies under
         the same lock, so every result is the one process_frames would have given for SOME gallery state between the
-        batch's submission and its delivery.  Falls back to one lane when the second one cannot join (see _eng2)."""
+        batch's submission and its delivery.  Falls back to one lane when the second one cannot join (see _eng2).
+        groups: as process_frames, for every batch - or a callable batch -> masks (mixer.run_mixed: the streams of each batch)."""
         engines = [self._eng()]
         e2 = self._eng2()
         if e2 is not None:
@@ -1010,7 +1048,8 @@ class FaceService:
         def on(eng):
             def run(frames, take_next=None, staged=None):
                 return self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold, det_thresh, all_matches,
-                                               take_next, staged, quality=quality, det_scales=det_scales)
+                                               take_next, staged, quality=quality, det_scales=det_scales,
+                                               groups=groups(frames) if callable(groups) else groups)
             if not engine_caps(eng).lane:
                 return lambda frames, take_next: run(frames)
             staged = {}                         # which batch sits in this lane's staging buffer

@@ -15,6 +15,8 @@ from typing import Dict, Iterator, List, Optional
 
 import numpy as np
 
+GROUPS_ALL = 0xFFFFFFFF        # include/frp.h: FRP_GROUPS_ALL - member of every group, the mask of a row that arrives without one
+
 
 class _RWLock:
     """Writers (gallery updates, and every reader that takes `Gallery.locked()`) are exclusive and re-entrant per thread;
@@ -93,6 +95,7 @@ class Gallery(Mapping):
         self._mirrors: List = []           # further engines holding a copy of the matrix (the second lane of a GPU)
         self._rows: Dict[str, int] = {}    # insertion-ordered: name -> device row
         self._names: List[Optional[str]] = []   # device row -> name
+        self._groups: List[int] = []       # device row -> group mask (frp.h: frp_gallery_set_groups); moves with _names
         self._lock = _RWLock()
         self.exact = False                 # the first engine keeps float64 rows as enrolled (enable_exact)
         self.dim = 0                       # width of the rows as enrolled (the reference's encodings are 128-d; device rows are padded to 512)
@@ -168,14 +171,43 @@ class Gallery(Mapping):
     def rows_of(self, names: List[str]) -> np.ndarray:
         return np.fromiter((self._rows[n] for n in names), dtype=np.int64, count=len(names))
 
-    def put(self, name: str, emb: np.ndarray) -> bool:
-        """insert or overwrite; returns True if the name already existed."""
+    # ---- group masks: "who is looked for where" on one gallery (a grouped match permits row r for a query iff mask[r] & query mask != 0)
+    def _push_groups(self, engines, first: int, masks) -> None:
+        """masks of the rows [first, first + len(masks)) to every copy.  The engines install ALL themselves for every row that
+        arrives, so a copy is only asked when the caller names masks - and one that cannot keep masks (no gallery_set_groups: the
+        partial engines of the tests, an older build) only then, by raising, when one of them is not ALL."""
+        masks = [int(m) & GROUPS_ALL for m in masks]
+        missing = [e for e in engines if not hasattr(e, "gallery_set_groups")]
+        if missing and any(m != GROUPS_ALL for m in masks):
+            raise ValueError("this engine keeps no group masks (gallery_set_groups)")
+        for e in engines:
+            if e not in missing:
+                e.gallery_set_groups(np.asarray(masks, np.uint32), first)
+
+    def groups_of(self, name: str) -> int:
+        return self._groups[self._rows[name]]
+
+    def groups_table(self) -> np.ndarray:
+        """device row -> mask, uint32 [len(self)]"""
+        return np.asarray(self._groups, dtype=np.uint32)
+
+    def set_groups(self, name: str, mask: int) -> None:
+        with self._lock:
+            row = self._rows[name]
+            self._push_groups(self._engines(), row, [mask])
+            self._groups[row] = int(mask) & GROUPS_ALL
+
+    def put(self, name: str, emb: np.ndarray, groups: Optional[int] = None) -> bool:
+        """insert or overwrite; returns True if the name already existed.  groups: the row's mask - None keeps the current one on an
+        overwrite and makes a new row a member of every group."""
         with self._lock:
             e = np.asarray(emb)
             e = e.astype(np.float64 if e.dtype == np.float64 else np.float32, copy=False).reshape(-1)   # (float64 stays: exact rows)
             if not self._names:
                 self.dim = int(e.shape[0])
             engines = self._engines()
+            if groups is not None and int(groups) & GROUPS_ALL != GROUPS_ALL and not all(hasattr(g, "gallery_set_groups") for g in engines):
+                raise ValueError("this engine keeps no group masks (gallery_set_groups)")      # (before any copy is touched)
             if name in self._rows:
                 row = self._rows[name]
                 old = None
@@ -188,6 +220,8 @@ class Gallery(Mapping):
                         for done in engines[:i]:            # a later copy failed: the copies must not differ by a row
                             done.gallery_update_row(row, old)
                         raise
+                if groups is not None:
+                    self.set_groups(name, groups)
                 return True
             row = len(self._names)
             for i, eng in enumerate(engines):
@@ -199,6 +233,9 @@ class Gallery(Mapping):
                     raise
             self._rows[name] = row
             self._names.append(name)
+            self._groups.append(GROUPS_ALL)                 # what every copy gave the appended row
+            if groups is not None and int(groups) & GROUPS_ALL != GROUPS_ALL:
+                self.set_groups(name, groups)
             return False
 
     def remove(self, name: str) -> bool:
@@ -221,7 +258,9 @@ class Gallery(Mapping):
                 moved = self._names[last]
                 self._names[row] = moved
                 self._rows[moved] = row                # dict position (insertion order) is unchanged
+                self._groups[row] = self._groups[last]  # (the device moved the mask with the row)
             self._names.pop()
+            self._groups.pop()
             return True
 
     def _resync_from(self, engines) -> None:
@@ -232,19 +271,36 @@ class Gallery(Mapping):
         if src is None:
             return
         rows = src.gallery_get(0, n).astype(np.float32) if n else np.zeros((0, 512), np.float32)
+        masks = self._groups[:n]
         for e in engines:
             if e is not src:
-                e.gallery_set(rows)
+                e.gallery_set(rows)                    # (every row ALL again)
+                if any(m != GROUPS_ALL for m in masks):
+                    self._push_groups([e], 0, masks)
 
-    def set_bulk(self, names: List[str], emb: np.ndarray):
-        """replace the whole gallery (startup load / all-gathered watchlist)."""
+    def set_bulk(self, names: List[str], emb: np.ndarray, groups=None):
+        """replace the whole gallery (startup load / all-gathered watchlist).  groups: one mask for every row or one per row;
+        None: every row a member of every group."""
         with self._lock:
             if len(set(names)) != len(names) or len(names) != len(emb):
                 raise ValueError("names must be unique and match the rows")
-            for eng in self._engines():
+            masks = [GROUPS_ALL] * len(names)
+            if groups is not None:
+                g = np.asarray(groups, dtype=np.uint64)
+                masks = [int(g) & GROUPS_ALL] * len(names) if g.ndim == 0 else [int(m) & GROUPS_ALL for m in g.reshape(-1)]
+                if len(masks) != len(names):
+                    raise ValueError("one group mask per row")
+            engines = self._engines()
+            plain = all(m == GROUPS_ALL for m in masks)
+            if not plain and not all(hasattr(e, "gallery_set_groups") for e in engines):
+                raise ValueError("this engine keeps no group masks (gallery_set_groups)")      # (before any copy is touched)
+            for eng in engines:
                 eng.gallery_set(np.asarray(emb))
+            if not plain:
+                self._push_groups(engines, 0, masks)
             self._rows = {n: i for i, n in enumerate(names)}
             self._names = list(names)
+            self._groups = masks
             self.dim = int(np.asarray(emb).shape[1]) if len(names) else 0
 
     def adopt_device(self, names: List[str]):
@@ -254,6 +310,7 @@ class Gallery(Mapping):
                 raise ValueError("name table does not match the device gallery")
             self._rows = {n: i for i, n in enumerate(names)}
             self._names = list(names)
+            self._groups = [GROUPS_ALL] * len(names)        # (frp_gallery_set_device / _commit / _allgather install ALL)
 
     def clear(self):
         with self._lock:
@@ -261,3 +318,4 @@ class Gallery(Mapping):
                 eng.gallery_set(np.zeros((0, 512), np.float32))
             self._rows.clear()
             self._names.clear()
+            self._groups.clear()

@@ -212,14 +212,29 @@ def demix(meta: List[Optional[Tuple[Any, int]]], per_frame_results: List[Any]) -
     return out
 
 
-def run_mixed(service, mixer: StreamMixer, **kw) -> Iterator[Dict[Any, List[Tuple[int, Any]]]]:
-    """mixer -> FaceService.process_stream (two batches in flight) -> per batch {stream id: [(frame index, faces), ...]}"""
+def frame_groups(meta: List[Optional[Tuple[Any, int]]], groups_of_stream) -> List[int]:
+    """one gallery-group mask per slot of a mixed batch (FaceService.process_frames(groups=)): the mask of the slot's stream -
+    groups_of_stream is {stream id: mask} (a stream it does not list looks for everyone: ALL) or a callable stream id -> mask -
+    and 0, which matches nobody, for a slot left empty"""
+    look = groups_of_stream if callable(groups_of_stream) else (lambda sid: groups_of_stream.get(sid, 0xFFFFFFFF))
+    return [0 if m is None else int(look(m[0])) for m in meta]
+
+
+def run_mixed(service, mixer: StreamMixer, groups_of_stream=None, **kw) -> Iterator[Dict[Any, List[Tuple[int, Any]]]]:
+    """mixer -> FaceService.process_stream (two batches in flight) -> per batch {stream id: [(frame index, faces), ...]}.
+    groups_of_stream ("camera 3 looks for list A, camera 7 for lists A and C"): every frame is matched against the identities its
+    stream's mask permits (frame_groups above), in the same one pass per batch."""
     import collections
     metas = collections.deque()
+    masks = {}                              # id(batch) -> its frames' masks, from the batch's hand-over to its pass
 
     def batches():
         for buf, meta in mixer:
             metas.append(meta)
+            if groups_of_stream is not None:
+                masks[id(buf)] = frame_groups(meta, groups_of_stream)
             yield buf
+    if groups_of_stream is not None:
+        kw = dict(kw, groups=lambda batch: masks.pop(id(batch)))
     for res in service.process_stream(batches(), **kw):
         yield demix(metas.popleft(), res)

@@ -24,7 +24,8 @@ EMB_DIM = 512
 CHIP = 112
 MAX_FACES_CAP = 128
 MAX_TOPK = 64
-FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN = 1, 2, 4, 8
+FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN, FLAG_GROUPS = 1, 2, 4, 8, 16
+GROUPS_ALL = 0xFFFFFFFF                      # include/frp.h: FRP_GROUPS_ALL - the mask of a gallery row that arrived without one
 F32, F16, F64 = 0, 1, 2
 JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}      # include/frp.h: FRP_JPEG_420, FRP_JPEG_444
 YUV_LAYOUTS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3}      # include/frp.h: FRP_YUV_NV12 ... (plane order: frp_upload_yuv)
@@ -38,12 +39,12 @@ ABI_SYMBOLS = [
     "frp_jpeg_info_get", "frp_jpeg_coefficients", "frp_upload_jpeg_async", "frp_debug_jpeg_device_batches", "frp_debug_graph_replays",
     "frp_set_jpeg_selfsync", "frp_debug_jpeg_selfsync_batches", "frp_jpeg_selfsync_coefficients",
     "frp_dist_unique_id", "frp_dist_init", "frp_dist_destroy", "frp_gallery_allgather",
-    "frp_gallery_size", "frp_gallery_get", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact",
+    "frp_gallery_size", "frp_gallery_get", "frp_gallery_set_groups", "frp_gallery_get_groups", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact",
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_debug_fc_l2norm", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_match_groups", "frp_match_within_groups", "frp_set_frame_groups", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -248,6 +249,12 @@ def load_library() -> C.CDLL:
         lib.frp_match_within.argtypes = [vp, vp, i32, f32, i32, vp, vp, vp]
         lib.frp_set_within.argtypes = [vp, f32, i32]
         lib.frp_fetch_within.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    if hasattr(lib, "frp_match_groups"):     # (as frp_match_within above)
+        lib.frp_gallery_set_groups.argtypes = [vp, vp, i64, i64]
+        lib.frp_gallery_get_groups.argtypes = [vp, vp, i64, i64]
+        lib.frp_set_frame_groups.argtypes = [vp, vp, i32]
+        lib.frp_match_groups.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+        lib.frp_match_within_groups.argtypes = [vp, vp, i32, vp, f32, i32, vp, vp, vp]
     if hasattr(lib, "frp_face_quality"):     # (as above: an older A/B partner build has none)
         lib.frp_face_quality.argtypes = [vp, vp, i32, u32, vp]
     if hasattr(lib, "frp_encode_jpeg"):      # (as above)
@@ -515,6 +522,33 @@ class Engine:
         out = np.empty((n, EMB_DIM), dtype=np.float16)
         self._chk(self._lib.frp_gallery_get(self._h, _ptr(out), first, n))
         return out
+
+    # -- gallery groups (frp.h: frp_gallery_set_groups): one uint32 mask per row, bit g = member of group g
+    @staticmethod
+    def _masks(groups, n: int) -> np.ndarray:
+        """n uint32 masks from one int (the same for all) or a sequence of n"""
+        g = np.asarray(groups, dtype=np.uint32)
+        g = np.full(n, g, np.uint32) if g.ndim == 0 else np.ascontiguousarray(g).reshape(-1)
+        if g.shape[0] != n:
+            raise ValueError(f"{n} masks expected, got {g.shape[0]}")
+        return g
+
+    def gallery_set_groups(self, groups, first: int = 0):
+        """masks of the rows [first, first + len(groups)); rows that arrive without one have GROUPS_ALL"""
+        g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32)).reshape(-1)
+        self._chk(self._lib.frp_gallery_set_groups(self._h, _ptr(g), int(first), g.shape[0]))
+
+    def gallery_get_groups(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        n = self.gallery_size() - first if n is None else n
+        out = np.empty((max(n, 0),), np.uint32)
+        self._chk(self._lib.frp_gallery_get_groups(self._h, _ptr(out), int(first), int(n)))
+        return out
+
+    def set_frame_groups(self, masks):
+        """one mask per frame for the passes that run with FLAG_GROUPS from now on: the faces of frame b are matched against the
+        gallery rows masks[b] permits (row mask & frame mask != 0)"""
+        m = np.ascontiguousarray(np.asarray(masks, dtype=np.uint32)).reshape(-1)
+        self._chk(self._lib.frp_set_frame_groups(self._h, _ptr(m), m.shape[0]))
 
     # -- hot path
     @staticmethod
@@ -801,27 +835,36 @@ class Engine:
         self._chk(self._lib.frp_embed_faces(self._h, _ptr(frames), H, W, rs, _ptr(k), k.shape[0], flags, _ptr(out)))
         return out
 
-    def match(self, q: np.ndarray, topk: int = 1):
+    def match(self, q: np.ndarray, topk: int = 1, groups=None):
         """-> (row idx, cosine): [M] for topk == 1, else [M, topk] ordered by (cosine desc, row asc);
-        columns beyond the gallery size hold -1 / -2.0"""
+        columns beyond the gallery size hold -1 / -2.0.  groups (one mask per query, or one int for all): over the rows each query's
+        mask permits only (frp.h: frp_match_groups); entries beyond the permitted rows hold -1 / -2.0"""
         q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, EMB_DIM)
         shape = (q.shape[0],) if topk == 1 else (q.shape[0], topk)
         idx = np.empty(shape, np.int32)
         cos = np.empty(shape, np.float32)
-        self._chk(self._lib.frp_match(self._h, _ptr(q), q.shape[0], int(topk), _ptr(idx), _ptr(cos)))
+        if groups is None:
+            self._chk(self._lib.frp_match(self._h, _ptr(q), q.shape[0], int(topk), _ptr(idx), _ptr(cos)))
+        else:
+            g = self._masks(groups, q.shape[0])
+            self._chk(self._lib.frp_match_groups(self._h, _ptr(q), q.shape[0], _ptr(g), int(topk), _ptr(idx), _ptr(cos)))
         return idx, cos
 
-    def match_within(self, q: np.ndarray, min_cos: float, cap: int = 64):
+    def match_within(self, q: np.ndarray, min_cos: float, cap: int = 64, groups=None):
         """radius match -> (idx [M, cap], cos [M, cap], n_hits [M]): every gallery row whose cosine is >= min_cos, ordered by
         (cosine desc, row asc); n_hits is the true count and may exceed cap (the list then holds the first cap of that order);
-        entries beyond min(n_hits, cap) hold -1 / -2.0"""
+        entries beyond min(n_hits, cap) hold -1 / -2.0.  groups: as in match() - lists and counts over the permitted rows only"""
         q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, EMB_DIM)
         M, cap = q.shape[0], int(cap)
         ok = 1 <= cap <= 64                     # (the library refuses the others: size the buffers for something harmless)
         idx = np.empty((M, cap if ok else 1), np.int32)
         cos = np.empty((M, cap if ok else 1), np.float32)
         n_hits = np.empty((M,), np.int32)
-        self._chk(self._lib.frp_match_within(self._h, _ptr(q), M, float(min_cos), cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
+        if groups is None:
+            self._chk(self._lib.frp_match_within(self._h, _ptr(q), M, float(min_cos), cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
+        else:
+            g = self._masks(groups, M)
+            self._chk(self._lib.frp_match_within_groups(self._h, _ptr(q), M, _ptr(g), float(min_cos), cap, _ptr(idx), _ptr(cos), _ptr(n_hits)))
         return idx, cos, n_hits
 
     def match_f16(self, q16: np.ndarray, n_device: Optional[int] = None, scores: bool = False):

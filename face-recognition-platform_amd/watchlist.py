@@ -217,11 +217,12 @@ def load_backup_dir(path, dim: int = 512) -> Tuple[List[str], np.ndarray]:
     return names, (np.stack(rows) if rows else np.zeros((0, dim), np.float32))
 
 
-def install_watchlist(service, records: Iterable[Dict], fernet: Optional[Fernet]) -> Dict[str, int]:
+def install_watchlist(service, records: Iterable[Dict], fernet: Optional[Fernet], groups: Optional[int] = None) -> Dict[str, int]:
     """The start-up load the reference lacks: decrypt every stored identity and install the
-    matrix in the device gallery of `service` (a FaceService) in one upload."""
+    matrix in the device gallery of `service` (a FaceService) in one upload.  groups: one gallery-group mask for the whole
+    installed list (Gallery.set_bulk: which frames look for it - FaceService.process_frames(groups=)); None: every frame does."""
     names, mat, skipped = load_records(records, fernet)
-    service.ENCODINGS.set_bulk(names, mat)
+    service.ENCODINGS.set_bulk(names, mat, **({} if groups is None else {"groups": groups}))
     return {"loaded": len(names), "skipped": len(skipped)}
 
 

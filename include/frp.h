@@ -55,6 +55,8 @@ typedef enum frp_dtype { FRP_F32 = 0, FRP_F16 = 1, FRP_F64 = 2 } frp_dtype;
 #define FRP_FLAG_WITHIN 8u     /* besides the top-1: per face the list of ALL gallery rows whose cosine is at or above the bound of
                                   frp_set_within, from the same gallery pass (frp_fetch_within; the caller's filter loop over every
                                   target, camera.py:246-256) */
+#define FRP_FLAG_GROUPS 16u    /* the pass matches every face against the rows its FRAME's mask permits (frp_set_frame_groups) */
+#define FRP_GROUPS_ALL 0xFFFFFFFFu   /* member of every group: the mask of a row that arrived without one */
 
 typedef struct frp_handle frp_handle;
 
@@ -127,6 +129,22 @@ int frp_gallery_remove_row(frp_handle* h, int64_t row); /* last row moves into `
 int64_t frp_gallery_size(const frp_handle* h);
 /* copy the normalised fp16 gallery back to the host (n_rows x 512 uint16) */
 int frp_gallery_get(frp_handle* h, void* out_f16, int64_t first_row, int64_t n_rows);
+/* Gallery groups: "who is looked for where" on ONE gallery (the reference's watchlist subset of the enrolled targets,
+ * utils/db.py:493-510, alert_service.py; the mixed-camera batches of mixer.py / dist.py) instead of one gallery copy or one pass per
+ * list, or a host filter behind an unrestricted match (wrong for top-1: the best row overall hides the best permitted one).
+ * Every row carries a uint32 mask - bit g: member of group g - and every query one; row r is PERMITTED for query q iff
+ * (row_groups[r] & q_groups[q]) != 0.  The grouped matches (frp_match_groups, frp_match_within_groups, a pass with FRP_FLAG_GROUPS)
+ * are the ungrouped ones taken over the permitted rows only: same total order (cosine descending, row ascending), a NaN score never
+ * selected, n_hits the true number of permitted rows at or above the bound, -1 / -2.0 for a query with nothing selectable (mask 0,
+ * no permitted row, every score NaN) and for ranks past the number of permitted rows.  The cosine of a permitted row is the
+ * frp_match_scores entry bit for bit; frp_match_scores and frp_gallery_distances ignore groups.
+ * Rows that arrive without a mask have FRP_GROUPS_ALL: every row of frp_gallery_set / _set_device / _commit / _allgather (mask
+ * changes are not replicated across ranks), a row appended by frp_gallery_update_row.  An overwrite keeps the row's mask and
+ * frp_gallery_remove_row moves the last row's mask with the row.  Mask 0 is legal: the row is enrolled but matches nobody.
+ * frp_gallery_set_groups / _get_groups: masks of rows [first_row, first_row + n_rows) within [0, frp_gallery_size);
+ * FRP_ERR_INVALID for a null pointer or a range outside it, and - set_groups - while a reservation is pending. */
+int frp_gallery_set_groups(frp_handle* h, const uint32_t* groups, int64_t first_row, int64_t n_rows);
+int frp_gallery_get_groups(frp_handle* h, uint32_t* out, int64_t first_row, int64_t n_rows);
 
 /* ---- exact rows for the REST-style compat path ---------------------------------------
  * replaces: the float64 arithmetic of face_recognition.face_distance on the rows AS ENROLLED
@@ -188,6 +206,14 @@ int frp_synchronize(frp_handle* h);
  * bit.  The list of a face with n_hits > cap is rebuilt here, from the embeddings the pass left on the device (one score row per
  * such face + the top-k selection); FRP_ERR_INVALID if a later match / embed call on the handle has replaced them. */
 int frp_set_within(frp_handle* h, float min_cos, int32_t cap);
+/* Grouped passes (FRP_FLAG_GROUPS of frp_process_frames / frp_process_resident / frp_finish_faces / frp_process_pyramid): masks [B],
+ * one per FRAME, for the flagged passes that follow - every face of frame b is matched against the rows masks[b] permits (frame mask
+ * 0: its faces match nothing, -1).  The pass launches the GROUPS form of the match kernel it would have launched, once; detections,
+ * embeddings and everything else are unchanged, and without the flag nothing is.  With FRP_FLAG_WITHIN the lists of frp_fetch_within
+ * are the grouped ones, a rebuilt list included.  A flagged pass fails with FRP_ERR_INVALID, nothing launched and the last pass's
+ * results still fetchable, without a preceding frp_set_frame_groups, with a B other than the pass's, or together with
+ * FRP_FLAG_NO_MATCH.  frp_counters.match_bytes of a grouped launch counts N * (1024 + 4). */
+int frp_set_frame_groups(frp_handle* h, const uint32_t* masks, int32_t B);
 int frp_fetch_within(frp_handle* h, int32_t B, int32_t max_faces, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits);
 
 /* Overlapped ingest for streaming callers (the camera loop keeps producing frames while the previous
@@ -432,6 +458,13 @@ int frp_match_scores(frp_handle* h, const float* q, int32_t M, float* cos_all, i
  * queries): no M x N matrix exists unless a query has more than cap hits - its list, and only its, is rebuilt from its score row.
  * -> compare_faces' `d <= tolerance` over all targets, batch_compare_faces (face_service.py:409-432,448-481) */
 int frp_match_within(frp_handle* h, const float* q, int32_t M, float min_cos, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits);
+/* frp_match / frp_match_within over the rows each query's mask permits (q_groups [M]; semantics: frp_gallery_set_groups above).  The
+ * same kernels in their GROUPS form: an accumulator element whose row is not permitted is set to the value rows past the gallery's
+ * end get, ahead of the selection; topk > 1 and a list with n_hits > cap select from score rows that hold a NaN where a row is
+ * not permitted.  Arguments are checked as in the ungrouped calls (null pointers, topk, cap, min_cos) before anything is launched. */
+int frp_match_groups(frp_handle* h, const float* q, int32_t M, const uint32_t* q_groups, int32_t topk, int32_t* idx, float* cos);
+int frp_match_within_groups(frp_handle* h, const float* q, int32_t M, const uint32_t* q_groups, float min_cos, int32_t cap,
+                            int32_t* idx, float* cos, int32_t* n_hits);
 
 /* Face quality: the blur and lighting sums of rectangles of the RESIDENT frames (those of the last frp_upload_frames / frp_swap_frames /
  * frp_process_frames), as uploaded.

@@ -4,7 +4,11 @@
     tools/match_probe.py within [N ...]
 the radius match instead: wall ms per call, copies included, of frp_match_within (cap 64, the bound of tolerance 0.6; every query
 is a noisy copy of a gallery row, so it has about one hit) against frp_match(topk=64), frp_match_scores and the plain top-1, M = 320,
-N = 100k / 1M; under `rocprofv3 --kernel-trace --stats` the same run gives match_top1_kernel against match_top1_within_kernel."""
+N = 100k / 1M; under `rocprofv3 --kernel-trace --stats` the same run gives match_top1_kernel against match_top1_within_kernel.
+    tools/match_probe.py --groups [N ...]
+gallery groups: wall ms per call of the grouped top-1 (frp_match_groups, the mask patterns of tests/groups_cases.py) against the plain
+top-1 on the same gallery and queries, M = 320, N = 100k / 1M, in one process, alternating round by round; per size the median of the
+rounds, the plain kernel's run-to-run spread (max - min of its rounds over their median) and the ratio grouped / plain."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -44,6 +48,38 @@ def within_mode(sizes):
               f" | hits per query {n.mean():.2f} (max {n.max()}) | lists equal top-k cut at the bound: {same}")
 
 
+def groups_mode(sizes):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import groups_cases as gc
+    M, rounds, reps = 320, 7, 20
+    for N in sizes:
+        G = rng.standard_normal((N, 512)).astype(np.float32)
+        eng.gallery_set(G)
+        q = G[rng.integers(0, N, size=M)] + 0.3 * rng.standard_normal((M, 512)).astype(np.float32)
+        del G
+        eng.gallery_set_groups(gc.row_groups(N))
+        qg = gc.query_groups(M)
+        ig, cg = eng.match(q, groups=qg)
+        i1, c1 = eng.match(q)
+        P = (qg & gc.row_groups(N)[np.maximum(ig, 0)]) != 0
+        consistent = bool(np.all(P[ig >= 0]) and np.all(cg[ig >= 0] <= c1[ig >= 0]) and np.array_equal(ig[qg == gc.ALL], i1[qg == gc.ALL]))
+        t = {"plain": [], "grouped": []}
+        for _ in range(rounds):
+            for name, fn in (("plain", lambda: eng.match(q)), ("grouped", lambda: eng.match(q, groups=qg))):
+                fn()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    fn()
+                t[name].append((time.perf_counter() - t0) / reps * 1e3)
+        mp, mg = float(np.median(t["plain"])), float(np.median(t["grouped"]))
+        spread = (max(t["plain"]) - min(t["plain"])) / mp
+        print(f"N={N:8d} M={M}: plain top-1 {mp:7.3f} ms | grouped top-1 {mg:7.3f} ms | ratio {mg / mp:6.3f} | plain spread over {rounds} rounds "
+              f"{100 * spread:5.1f} % | winners permitted, never above the plain winner's score, equal for ALL queries: {consistent}")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--groups":
+    groups_mode([int(a) for a in sys.argv[2:]] or [100_000, 1_000_000])
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "within":
     within_mode([int(a) for a in sys.argv[2:]] or [100_000, 1_000_000])
     sys.exit(0)

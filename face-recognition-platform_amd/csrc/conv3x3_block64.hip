@@ -35,9 +35,9 @@
 //               a 16-row ring, disjoint; the slots conv1 writes held rows m - 16, last read in step k - 2.  conv2 reads them from
 //               step k + 1 on, behind the barrier that follows conv1's retired writes.
 //     Between two items one more barrier: the next item's first groups go into slots the last step may still be reading.
-//   * Same bits as the two launches: accumulation order (kh, kw, 16-channel slice) in fp32, epilogue arithmetic of the other direct
-//     kernels (bias - the nine border classes by the intermediate pixel's true image position -, residual, ReLU / PReLU, one RNE
-//     conversion to fp16).  tests/test_gpu_block64.py compares with np.array_equal.
+//   * Same bits as the two launches: accumulation order (kh, kw, 16-channel slice) in fp32, epilogue arithmetic from its one
+//     definition (conv_common.h: epi_*; the nine border classes go by the intermediate pixel's true image position).
+//     tests/test_gpu_block64.py compares with np.array_equal.
 //
 // Replaces the same reference calls as conv_mfma.hip (face_recognition.face_locations / face_encodings,
 // backend/app/routes/camera.py:232,237).
@@ -64,8 +64,6 @@ static_assert(B64_LDS == BLOCK64_LDS_BYTES && B64_LDS <= 160 * 1024, "LDS budget
 #ifndef B64_ABL
 #define B64_ABL 0                              // lab builds: timing ablations (1: no output stores, 2: no input DMA, 4: no MFMAs; wrong results)
 #endif
-
-typedef unsigned b64_u32x4 __attribute__((ext_vector_type(4)));
 
 template <int ACT1, bool BORDER1, int ACT2>
 __global__ __launch_bounds__(512, 2) void conv3x3_block64_kernel(Block64Params p_in) {
@@ -192,36 +190,22 @@ __global__ __launch_bounds__(512, 2) void conv3x3_block64_kernel(Block64Params p
                     const int my = ys - 1 + 4 * k + 2 * wp + b, mx = x0 - 1 + fr;
                     const bool inimg = (unsigned)my < (unsigned)H && (unsigned)mx < (unsigned)W;
                     int cls = 0;
-                    if (BORDER1) cls = ((my == 0) ? 0 : (my == H - 1) ? 2 : 1) * 3 + ((mx == 0) ? 0 : (mx == W - 1) ? 2 : 1);
+                    if (BORDER1) cls = epi_border_class(my, mx, H, W);
                     if (!inimg) cls = 0;
-                    union { half4 h; unsigned u[2]; } pk[4];
+                    half4 pk[4];
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const int cl = wc * 32 + 8 * g + 4 * fh;
-                        const floatx4 b4 = *reinterpret_cast<const floatx4*>(lds_bias1 + cls * 64 + cl);
                         floatx4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[b][4 * g + e] + b4[e];
-                        if (ACT1 == FRP_ACT_RELU) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                        } else if (ACT1 == FRP_ACT_PRELU) {
-                            const floatx4 s4 = *reinterpret_cast<const floatx4*>(lds_slope1 + cl);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * s4[e];
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) pk[g].h[e] = (_Float16)v[e];
+                        epi_value<ACT1, 0>(v, 0, acc[b], g, lds_bias1 + cls * 64, lds_slope1, wc * 32 + 8 * g + 4 * fh);
+                        pk[g] = epi_half4(v);
                     }
                     const int ms = (6 + 4 * k + 2 * wp + b) & (B64_MID_ROWS - 1);
                     unsigned char* mrow = smem + B64_OFF_MID + ms * B64_MID_ROW + lbase + wc * 64;
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                        swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
-                        b64_u32x4 o = {pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]};   // couts 32 wc + 16 q + 8 fh .. + 7
-                        if (!inimg) o = b64_u32x4{0u, 0u, 0u, 0u};                   // conv2's zero padding
-                        *reinterpret_cast<b64_u32x4*>(mrow + q * 32) = o;
+                        u32x4 o = epi_chunk(pk[2 * q], pk[2 * q + 1]);              // couts 32 wc + 16 q + 8 fh .. + 7
+                        if (!inimg) o = u32x4{0u, 0u, 0u, 0u};                   // conv2's zero padding
+                        *reinterpret_cast<u32x4*>(mrow + q * 32) = o;
                     }
                 }
             }
@@ -237,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_block64_kernel(Block64Params p
                 for (int j = 0; j < 4; ++j) rp[j] = smem + B64_OFF_MID + ((ib + j) & (B64_MID_ROWS - 1)) * B64_MID_ROW + lbase;
                 multiply(rp);
                 // epilogue: lane = output pixel (row oy, column x0 + fr; lanes 30, 31 belong to the next strip)
-                b64_u32x4 rr[2][2];
+                u32x4 rr[2][2];
                 unsigned ooff[2];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
@@ -247,48 +231,23 @@ __global__ __launch_bounds__(512, 2) void conv3x3_block64_kernel(Block64Params p
                     const int i = ib + b;
                     const unsigned char* xr = smem + (((i >> 2) & 3) * B64_IN_GRP + (i & 3) * B64_IN_ROW) + lbase + 2 * B64_PITCH + wc * 64;
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) rr[b][q] = *reinterpret_cast<const b64_u32x4*>(xr + q * 32);
+                    for (int q = 0; q < 2; ++q) rr[b][q] = *reinterpret_cast<const u32x4*>(xr + q * 32);
                 }
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     half4 r4[4];
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        b64_u32x4 v = rr[b][q];
-                        unsigned x_ = v.x, y_ = v.y, z_ = v.z, w_ = v.w;
-                        swap_halves(x_, z_);
-                        swap_halves(y_, w_);
-                        union { unsigned u[2]; half4 h; } lo, hi;
-                        lo.u[0] = x_; lo.u[1] = y_; hi.u[0] = z_; hi.u[1] = w_;
-                        r4[2 * q] = lo.h;
-                        r4[2 * q + 1] = hi.h;
-                    }
-                    union { half4 h; unsigned u[2]; } pk[4];
+                    for (int q = 0; q < 2; ++q) epi_residual(rr[b][q], r4[2 * q], r4[2 * q + 1]);
+                    half4 pk[4];
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const int cl = wc * 32 + 8 * g + 4 * fh;
-                        const floatx4 b4 = *reinterpret_cast<const floatx4*>(lds_bias2 + cl);
                         floatx4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[b][4 * g + e] + b4[e];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] += (float)r4[g][e];
-                        if (ACT2 == FRP_ACT_RELU) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                        } else if (ACT2 == FRP_ACT_PRELU) {
-                            const floatx4 s4 = *reinterpret_cast<const floatx4*>(lds_slope2 + cl);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * s4[e];
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) pk[g].h[e] = (_Float16)v[e];
+                        epi_value<ACT2, 1>(v, 0, acc[b], g, lds_bias2, lds_slope2, wc * 32 + 8 * g + 4 * fh, r4[g]);
+                        pk[g] = epi_half4(v);
                     }
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                        swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
-                        const b64_u32x4 o = {pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]};
+                        const u32x4 o = epi_chunk(pk[2 * q], pk[2 * q + 1]);
                         if (B64_ABL & 1) asm volatile("" ::"v"(o)); else
                         __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, ooff[b] + 32 * q, 0, 0);   // couts 32 wc + 16 q + 8 fh .. + 7
                     }

@@ -13,8 +13,9 @@
 //     ds_read_b128 per MFMA, every one of them at the block's base register + an immediate (144-byte pixel pitch: C64_PITCH);
 //   * stores are unconditional buffer stores (pixels that do not exist get an out-of-range offset), so the in-order memory
 //     counter is exact and the wait in front of a tile's barrier admits the next tile's DMA and the last epilogue's stores.
-// Eight waves = 4 pixel groups (tile rows 2g, 2g + 1) x 2 cout groups; accumulation order (kh, kw, 16-channel slice) and
-// epilogue arithmetic are those of the other direct kernels: bit-identical results (tests: test_conv_c64_equals_generic_kernel).
+// Eight waves = 4 pixel groups (tile rows 2g, 2g + 1) x 2 cout groups; accumulation order (kh, kw, 16-channel slice) as in the
+// other direct kernels, epilogue arithmetic from its one definition (conv_common.h: epi_*): bit-identical results (tests:
+// test_conv_c64_equals_generic_kernel).
 //
 // Replaces the same reference calls as conv_mfma.hip (face_recognition.face_locations / face_encodings,
 // backend/app/routes/camera.py:232,237).
@@ -41,8 +42,6 @@ static_assert(C64_ROWS_MAX * 9 <= C64_PIECES * 64, "patch slots");
 #define C64_NBUF 3
 #define C64_OFF_PAR (C64_NBUF * C64_BUF)
 #define C64_LDS (C64_OFF_PAR + 10 * 64 * 4)
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Specialised at compile time on (activation, residual, border-class bias): with the flags as run-time values the epilogue was a
 // chain of ~90 uniform branches and the register allocator spilled eleven registers, each reload a vmcnt(0) in the tile loop.
@@ -232,22 +231,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(ConvParams p_in) {
                 unsigned char* prow = smem + pbuf * C64_BUF + R * C64_PITCH + fh * 16;
 #pragma unroll
                 for (int cg = 0; cg < 2; ++cg) {
-                    union { half4 hv; unsigned u[2]; } pk[4];
+                    half4 pk[4];
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const floatx4 b4 = *reinterpret_cast<const floatx4*>(sb + 32 * cg + 8 * g + 4 * fh);
-                        const floatx4 s4 = *reinterpret_cast<const floatx4*>(sb + 64 + 32 * cg + 8 * g + 4 * fh);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float v = sacc[cg][4 * g + e] + b4[e];
-                            pk[g].hv[e] = (_Float16)(v > 0.f ? v : v * s4[e]);
-                        }
+                        const float* sbg = sb + 32 * cg + 8 * g + 4 * fh;
+                        floatx4 v;
+                        epi_value<FRP_ACT_PRELU, 0>(v, 0, sacc[cg], g, sbg, sbg + 64, 0);
+                        pk[g] = epi_half4(v);
                     }
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                        swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
-                        u32x4 o = {pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]};     // couts 32 cg + 16 q + 8 fh .. + 7
+                        u32x4 o = epi_chunk(pk[2 * q], pk[2 * q + 1]);                // couts 32 cg + 16 q + 8 fh .. + 7
                         if (C64S_ABL & 2) asm volatile("" ::"v"(o)); else
                         __builtin_amdgcn_raw_buffer_store_b128(o, srsrc, goff + cg * 64 + q * 32, 0, 0);
                         if (!inimg) o = u32x4{0u, 0u, 0u, 0u};                  // the conv's zero padding, not the stem of padded chips
@@ -293,49 +287,22 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(ConvParams p_in) {
         for (int b = 0; b < 2; ++b) {
             const int oy = oy0 + b * C64_RB;
             int cls = 0;
-            if (border) cls = ((oy == 0) ? 0 : (oy == p.H - 1) ? 2 : 1) * 3 + ((ox == 0) ? 0 : (ox == p.W - 1) ? 2 : 1);
+            if (border) cls = epi_border_class(oy, ox, p.H, p.W);
             half4 r4[4];
             if (has_res) {
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    u32x4 v = rr[b][q];
-                    unsigned x_ = v.x, y_ = v.y, z_ = v.z, w_ = v.w;
-                    swap_halves(x_, z_);
-                    swap_halves(y_, w_);
-                    union { unsigned u[2]; half4 h; } lo, hi;
-                    lo.u[0] = x_; lo.u[1] = y_; hi.u[0] = z_; hi.u[1] = w_;
-                    r4[2 * q] = lo.h;
-                    r4[2 * q + 1] = hi.h;
-                }
+                for (int q = 0; q < 2; ++q) epi_residual(rr[b][q], r4[2 * q], r4[2 * q + 1]);
             }
-            union { half4 h; unsigned u[2]; } pk[4];
+            half4 pk[4];                       // (each group converted as it is finished: all four values first cost ten registers)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int cl = wave_c * 32 + 8 * g + 4 * fh;
-                const floatx4 b4 = *reinterpret_cast<const floatx4*>(lds_bias + cls * 64 + cl);
                 floatx4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = acc[b][4 * g + e] + b4[e];
-                if (has_res) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)r4[g][e];
-                }
-                if (ACT == FRP_ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                } else if (ACT == FRP_ACT_PRELU) {
-                    const floatx4 s4 = *reinterpret_cast<const floatx4*>(lds_slope + cl);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * s4[e];
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pk[g].h[e] = (_Float16)v[e];
+                epi_value<ACT, RES>(v, 0, acc[b], g, lds_bias + cls * 64, lds_slope, wave_c * 32 + 8 * g + 4 * fh, r4[g]);
+                pk[g] = epi_half4(v);
             }
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
-                const u32x4 o = {pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]};
+                const u32x4 o = epi_chunk(pk[2 * q], pk[2 * q + 1]);
                 if (STEM && (C64S_ABL & 8)) asm volatile("" ::"v"(o)); else
                 __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, ooff[b] + 32 * q, 0, 0);   // couts 32 wave_c + 16 q + 8 fh .. + 7
             }

@@ -43,8 +43,6 @@ namespace frp {
 #define S2_OFF_DUMMY (S2_OFF_BIAS + S2_MAX_COUT * 4)
 #define S2_LDS (S2_OFF_DUMMY + 1024)             // 159,744 B
 
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-
 // lab builds only (tools/s2_ablate.sh): timing ablations - 1: no patch DMA, 2: no MFMAs, 4: no weight DMA, 8: no fragment reads,
 // 16: no stores (1, 4, 16: every wait drains the counter).  Wrong results, of course.
 #ifndef S2_ABL
@@ -309,33 +307,23 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_kernel(ConvParams p_in) {
             wslot = nws;
         }
 
-        // ---------------- epilogue: lane = pixel, registers 4g .. 4g+3 of block j = couts c0 + 64 wave_c + 32 j + 8g + 4 fh .. + 3
+        // ---------------- epilogue (arithmetic: conv_common.h, epi_*): lane = pixel, registers 4g .. 4g+3 of block j = couts c0 + 64 wave_c + 32 j + 8g + 4 fh .. + 3
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int m = m0 + (wave_p * 2 + b) * 32 + fr;
             const unsigned ooff = m < M ? (unsigned)(m * pCout * 2 + (c0 + wave_c * 64) * 2 + fh * 16) : CONV_OOB;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                union { half4 h; unsigned u[2]; } pk[4];
+                half4 pk[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int cl = c0 + wave_c * 64 + j * 32 + 8 * g + 4 * fh;
-                    const floatx4 b4 = *reinterpret_cast<const floatx4*>(lds_bias + cl);
                     floatx4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[b][j][4 * g + e] + b4[e];
-                    if (ACT == FRP_ACT_RELU) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pk[g].h[e] = (_Float16)v[e];
+                    epi_value<ACT, 0>(v, 0, acc[b][j], g, lds_bias, nullptr, c0 + wave_c * 64 + j * 32 + 8 * g + 4 * fh);   // (ACT: none or ReLU, no slope)
+                    pk[g] = epi_half4(v);
                 }
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                    swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
-                    const u32x4s o = {pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]};
+                    const u32x4 o = epi_chunk(pk[2 * q], pk[2 * q + 1]);
                     if (S2_ABL & 16) asm volatile("" ::"v"(o)); else
                     __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, ooff + j * 64 + q * 32, 0, 0);   // couts 32 j + 16 q + 8 fh .. + 7 of the wave's 64
                 }

@@ -537,7 +537,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv3x3_wino_kernel(ConvParam
 // the barrier of sub-step T (lgkmcnt(0): they are the operands of T, requested during T - 1 from slot T & 3), so no read of
 // that slot is in flight anywhere when the DMA behind the barrier restages it; a patch slot is restaged one to five
 // sub-steps after the last read of it was consumed.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // ZERO: the first MFMA into an accumulator of a tile - C is the inline constant 0, the accumulator is only written (no 128 v_mov
 // per wave and tile to clear it first; early-clobber: the destination may not overlap the sources)

@@ -145,10 +145,102 @@ __device__ __forceinline__ void fast_divmod(int m, int d, float inv_d, int& q, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Tile epilogue shared by the conv kernels (accumulator layout of v_mfma_f32_32x32x16: lane = one pixel (fr) of a
-// 32-pixel row block, registers 4g..4g+3 = couts 8g + 4*fh .. +3 of a 32-cout block): bias / 9-class border bias
-// from the LDS parameter cache, residual, activation in fp32, then fp16 (16-byte stores after a half-wave
-// exchange) or fp32 output.
+// THE epilogue arithmetic of every conv / stem kernel: one lane's share of one 32-pixel x 32-cout accumulator block
+// (layout of v_mfma_f32_32x32x16: lane = pixel fr of the block, registers 4g..4g+3 = couts 8g + 4*fh .. +3).  Bit-identity
+// between the kernel families rests on these being the only definition: accumulator (x weight scale) + bias, + residual,
+// ReLU / PReLU in fp32, ONE conversion to fp16 (or fp8), then the half-wave exchange into store chunks.  Stores, addresses,
+// range checks and ablation switches stay with the kernels; so does the ORDER in which a kernel calls the pieces (all four
+// groups' values before any conversion, or group by group): the register allocation follows it.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// border class 0..8 of output pixel (oy, ox): row of the 9-class bias table (FRP_FLAG_BORDER_BIAS)
+__device__ __forceinline__ int epi_border_class(int oy, int ox, int Ho, int Wo) {
+    return ((oy == 0) ? 0 : (oy == Ho - 1) ? 2 : 1) * 3 + ((ox == 0) ? 0 : (ox == Wo - 1) ? 2 : 1);
+}
+
+// residual: one 16-byte chunk in the STORE layout (couts 16q + 8*fh .. +7 of this lane's pixel; from a global load, a buffer
+// load or LDS) -> groups 2q, 2q + 1 in the accumulator layout: the same half-wave exchange as for the stores (it is its own inverse)
+__device__ __forceinline__ void epi_residual(u32x4 c, half4& g0, half4& g1) {
+    unsigned x = c.x, y = c.y, z = c.z, w = c.w;
+    swap_halves(x, z);
+    swap_halves(y, w);
+    union { unsigned u[2]; half4 h; } lo, hi;
+    lo.u[0] = x; lo.u[1] = y; hi.u[0] = z; hi.u[1] = w;
+    g0 = lo.h;
+    g1 = hi.h;
+}
+__device__ __forceinline__ void epi_residual(const uint4& c, half4& g0, half4& g1) { epi_residual(u32x4{c.x, c.y, c.z, c.w}, g0, g1); }
+
+// value of group g, written to v[o .. o+3].  V = floatx4 (o = 0) where a kernel converts group by group; V = floatx16 (o = 4g: the
+// accumulator layout) where it finishes a block's four groups first - the other choice costs either kind of kernel registers
+// (tests/test_kernel_resources_host.py).  bias / slope / wscale: rows of the LDS parameter cache (or registers of the caller), read
+// at [cl .. cl+3], the group's couts - the slope only under PReLU.
+//   ACT: FRP_ACT_* or -1 = run-time `act`;  RES: 0 / 1 or -1 = run-time `has_res`;  WS: the accumulator is first multiplied by wscale
+template <int ACT, int RES, bool WS = false, typename V>
+__device__ __forceinline__ void epi_value(V& v, int o, const floatx16& acc, int g, const float* bias, const float* slope, int cl,
+                                          half4 res = half4{}, int act_rt = FRP_ACT_NONE, bool res_rt = false, const float* wscale = nullptr) {
+    const int act = ACT < 0 ? act_rt : ACT;
+    const bool has_res = RES < 0 ? res_rt : RES != 0;
+    const floatx4 b4 = *reinterpret_cast<const floatx4*>(bias + cl);
+    if constexpr (WS) {
+        const floatx4 w4 = *reinterpret_cast<const floatx4*>(wscale + cl);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[o + e] = acc[4 * g + e] * w4[e] + b4[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[o + e] = acc[4 * g + e] + b4[e];
+    }
+    if (has_res) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[o + e] += (float)res[e];
+    }
+    if (act == FRP_ACT_RELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[o + e] = fmaxf(v[o + e], 0.f);
+    } else if (act == FRP_ACT_PRELU) {
+        const floatx4 s4 = *reinterpret_cast<const floatx4*>(slope + cl);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[o + e] = v[o + e] > 0.f ? v[o + e] : v[o + e] * s4[e];
+    }
+}
+__device__ __forceinline__ floatx4 epi_group(const floatx16& v, int g) { return floatx4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]}; }
+
+// pack: the one conversion to fp16 (of v[o .. o+3]) ...
+template <typename V>
+__device__ __forceinline__ half4 epi_half4(const V& v, int o = 0) {
+    half4 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) h[e] = (_Float16)v[o + e];
+    return h;
+}
+// ... and the half-wave exchange of groups 2q, 2q + 1 (as packed dwords) into the lane's store chunk q: couts 16q + 8*fh .. +7
+__device__ __forceinline__ u32x4 epi_chunk(const unsigned (&a)[2], const unsigned (&b)[2]) {
+    unsigned a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
+    swap_halves(a0, b0);
+    swap_halves(a1, b1);
+    return u32x4{a0, a1, b0, b1};
+}
+__device__ __forceinline__ u32x4 epi_chunk(half4 a, half4 b) {
+    union { half4 h; unsigned u[2]; } x, y;
+    x.h = a;
+    y.h = b;
+    return epi_chunk(x.u, y.u);
+}
+// the fp8 sibling (OCP E4M3: value / out_scale, clamped to +-448): a lane packs its 4-cout runs into dwords, exchanges half-waves
+// like the fp16 path and stores 8 consecutive couts (8 bytes) per (32-cout block, half)
+__device__ __forceinline__ int pack_fp8x4(const floatx16& v, int o, float inv_scale) {
+    float a[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = fminf(fmaxf(v[o + e] * inv_scale, -448.f), 448.f);
+    int d = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
+    return __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], d, true);
+}
+// (in place: afterwards (a, b) is the lane's chunk q)
+__device__ __forceinline__ void epi_chunk8(unsigned& a, unsigned& b) { swap_halves(a, b); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Tile epilogue of the tiled kernels (generic, row-patch, Winograd): the pixel loop around the pieces above - bias / 9-class
+// border bias from the LDS parameter cache, residual, activation, then fp16 (16-byte stores) or fp32 output.
 //
 // FULL tiles (the common case) run a copy specialised at compile time on (activation, residual): with the flags
 // as run-time values the compiler kept ~70 uniform branches and ~90 s_nops in every epilogue (it does not unswitch
@@ -165,7 +257,6 @@ __device__ __forceinline__ void conv_epilogue_body(const ConvParams& p, floatx16
     const bool border = p.flags & FRP_FLAG_BORDER_BIAS;
     const bool out32 = (ACT < 0) && (p.flags & FRP_FLAG_OUT_F32);
     const bool has_res = RES < 0 ? p.res != nullptr : RES != 0;
-    const int act = ACT < 0 ? p.act : ACT;
     half4 r4[MP][MC][4];
     bool mok[MP];
     long obase[MP];
@@ -180,71 +271,40 @@ __device__ __forceinline__ void conv_epilogue_body(const ConvParams& p, floatx16
             int n, rem, oy, ox;
             fast_divmod(m, HoWo, inv_howo, n, rem);
             fast_divmod(rem, p.Wo, inv_wo, oy, ox);
-            cls[i] = ((oy == 0) ? 0 : (oy == p.Ho - 1) ? 2 : 1) * 3 + ((ox == 0) ? 0 : (ox == p.Wo - 1) ? 2 : 1);
+            cls[i] = epi_border_class(oy, ox, p.Ho, p.Wo);
         }
         obase[i] = (long)m * p.Cout;
         if (has_res) {
-            // the residual arrived as 16-byte chunks in the STORE layout; the same half-wave exchange as for the
-            // stores (it is its own inverse) turns them into the accumulator layout
 #pragma unroll
             for (int j = 0; j < MC; ++j)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    uint4 rr = rres[i][j][q];
-                    swap_halves(rr.x, rr.z);
-                    swap_halves(rr.y, rr.w);
-                    union { unsigned u[2]; half4 h; } lo, hi;
-                    lo.u[0] = rr.x; lo.u[1] = rr.y; hi.u[0] = rr.z; hi.u[1] = rr.w;
-                    r4[i][j][2 * q] = lo.h;
-                    r4[i][j][2 * q + 1] = hi.h;
-                }
+                for (int q = 0; q < 2; ++q) epi_residual(rres[i][j][q], r4[i][j][2 * q], r4[i][j][2 * q + 1]);
         }
     }
 #pragma unroll
     for (int i = 0; i < MP; ++i) {
 #pragma unroll
         for (int j = 0; j < MC; ++j) {
-            floatx4 v[4];
+            floatx16 v;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = crow0 + j * 32 + 8 * g + 4 * fh;
-                const floatx4 b4 = *reinterpret_cast<const floatx4*>(lds_bias + cls[i] * TC + cl);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[g][e] = acc[i][j][4 * g + e] + b4[e];
-                if (has_res) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] += (float)r4[i][j][g][e];
-                }
-                if (act == FRP_ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] = fmaxf(v[g][e], 0.f);
-                } else if (act == FRP_ACT_PRELU) {
-                    const floatx4 s4 = *reinterpret_cast<const floatx4*>(lds_slope + cl);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] = v[g][e] > 0.f ? v[g][e] : v[g][e] * s4[e];
-                }
-            }
+            for (int g = 0; g < 4; ++g)
+                epi_value<ACT, RES>(v, 4 * g, acc[i][j], g, lds_bias + cls[i] * TC, lds_slope, crow0 + j * 32 + 8 * g + 4 * fh, r4[i][j][g], p.act, has_res);
             if (out32) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int co = c0 + crow0 + j * 32 + 8 * g + 4 * fh;
                     if (FULL || (mok[i] && co < p.Cout))
-                        *reinterpret_cast<floatx4*>(reinterpret_cast<float*>(p.out) + obase[i] + co) = v[g];
+                        *reinterpret_cast<floatx4*>(reinterpret_cast<float*>(p.out) + obase[i] + co) = epi_group(v, g);
                 }
             } else {
-                union { half4 h; unsigned u[2]; } pk[4];
+                half4 h[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pk[g].h[e] = (_Float16)v[g][e];
+                for (int g = 0; g < 4; ++g) h[g] = epi_half4(v, 4 * g);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                    swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
+                    const u32x4 o = epi_chunk(h[2 * q], h[2 * q + 1]);
                     const int co = c0 + crow0 + j * 32 + 16 * q + 8 * fh;   // 8 consecutive couts
-                    if (FULL || (mok[i] && co < p.Cout))
-                        *reinterpret_cast<uint4*>(reinterpret_cast<_Float16*>(p.out) + obase[i] + co) =
-                            make_uint4(pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]);
+                    if (FULL || (mok[i] && co < p.Cout)) *reinterpret_cast<u32x4*>(reinterpret_cast<_Float16*>(p.out) + obase[i] + co) = o;
                 }
             }
         }
@@ -271,17 +331,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, floatx16 (&ac
 // ---------------------------------------------------------------------------------------------------------------
 // Epilogue with fp8 outputs (BASELINE config 5).  WS: the accumulator is first multiplied by lds_wscale[cout] (fp8
 // weights x fp8 input: per-cout weight scale x input-tensor scale).  Outputs: fp16 to p.out unless FRP_FLAG_OUT_FP8;
-// OCP E4M3 bytes (value / out_scale, clamped to +-448) to p.out when FRP_FLAG_OUT_FP8, else to p.out2 when set.
-// fp8 store layout: a lane packs its 4-cout runs into dwords, exchanges half-waves like the fp16 path and stores
-// 8 consecutive couts (8 bytes) per (32-cout block, half).
-__device__ __forceinline__ int pack_fp8x4(floatx4 v, float inv_scale) {
-    float a[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] = fminf(fmaxf(v[e] * inv_scale, -448.f), 448.f);
-    int d = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], d, true);
-}
-
+// OCP E4M3 bytes to p.out when FRP_FLAG_OUT_FP8, else to p.out2 when set.
 template <int MP, int MC, int TC, bool FULL, int ACT, int RES, bool WS>
 __device__ __forceinline__ void conv_epilogue8_body(const ConvParams& p, floatx16 (&acc)[MP][MC], const uint4 (&rres)[MP][MC][2],
                                                     const float* lds_bias, const float* lds_slope, const float* lds_wscale, int m0,
@@ -291,7 +341,6 @@ __device__ __forceinline__ void conv_epilogue8_body(const ConvParams& p, floatx1
     unsigned char* dst8 = reinterpret_cast<unsigned char*>(out8 ? p.out : p.out2);
     const float inv_os = 1.0f / p.out_scale;
     const bool has_res = RES < 0 ? p.res != nullptr : RES != 0;
-    const int act = ACT < 0 ? p.act : ACT;
 #pragma unroll
     for (int i = 0; i < MP; ++i) {
         const int mraw = m0 + prow0 + i * 32 + fr;
@@ -302,7 +351,7 @@ __device__ __forceinline__ void conv_epilogue8_body(const ConvParams& p, floatx1
             int n, rem, oy, ox;
             fast_divmod(m, HoWo, inv_howo, n, rem);
             fast_divmod(rem, p.Wo, inv_wo, oy, ox);
-            cls = ((oy == 0) ? 0 : (oy == p.Ho - 1) ? 2 : 1) * 3 + ((ox == 0) ? 0 : (ox == p.Wo - 1) ? 2 : 1);
+            cls = epi_border_class(oy, ox, p.Ho, p.Wo);
         }
         const long obase = (long)m * p.Cout;
 #pragma unroll
@@ -310,68 +359,32 @@ __device__ __forceinline__ void conv_epilogue8_body(const ConvParams& p, floatx1
             half4 r4[4];
             if (has_res) {
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    uint4 rr = rres[i][j][q];
-                    swap_halves(rr.x, rr.z);
-                    swap_halves(rr.y, rr.w);
-                    union { unsigned u[2]; half4 h; } lo, hi;
-                    lo.u[0] = rr.x; lo.u[1] = rr.y; hi.u[0] = rr.z; hi.u[1] = rr.w;
-                    r4[2 * q] = lo.h;
-                    r4[2 * q + 1] = hi.h;
-                }
+                for (int q = 0; q < 2; ++q) epi_residual(rres[i][j][q], r4[2 * q], r4[2 * q + 1]);
             }
-            floatx4 v[4];
+            floatx16 v;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = crow0 + j * 32 + 8 * g + 4 * fh;
-                const floatx4 b4 = *reinterpret_cast<const floatx4*>(lds_bias + cls * TC + cl);
-                if constexpr (WS) {
-                    const floatx4 w4 = *reinterpret_cast<const floatx4*>(lds_wscale + cl);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] = acc[i][j][4 * g + e] * w4[e] + b4[e];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] = acc[i][j][4 * g + e] + b4[e];
-                }
-                if (has_res) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] += (float)r4[g][e];
-                }
-                if (act == FRP_ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] = fmaxf(v[g][e], 0.f);
-                } else if (act == FRP_ACT_PRELU) {
-                    const floatx4 s4 = *reinterpret_cast<const floatx4*>(lds_slope + cl);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[g][e] = v[g][e] > 0.f ? v[g][e] : v[g][e] * s4[e];
-                }
-            }
+            for (int g = 0; g < 4; ++g)
+                epi_value<ACT, RES, WS>(v, 4 * g, acc[i][j], g, lds_bias + cls * TC, lds_slope, crow0 + j * 32 + 8 * g + 4 * fh, r4[g], p.act, has_res, lds_wscale);
             if (!out8) {                      // fp16 primary output
-                union { half4 h; unsigned u[2]; } pk[4];
+                half4 h[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pk[g].h[e] = (_Float16)v[g][e];
+                for (int g = 0; g < 4; ++g) h[g] = epi_half4(v, 4 * g);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-                    swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
+                    const u32x4 o = epi_chunk(h[2 * q], h[2 * q + 1]);
                     const int co = c0 + crow0 + j * 32 + 16 * q + 8 * fh;
-                    if (FULL || (mok && co < p.Cout))
-                        *reinterpret_cast<uint4*>(reinterpret_cast<_Float16*>(p.out) + obase + co) =
-                            make_uint4(pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]);
+                    if (FULL || (mok && co < p.Cout)) *reinterpret_cast<u32x4*>(reinterpret_cast<_Float16*>(p.out) + obase + co) = o;
                 }
             }
             if (dst8) {                       // fp8 output (primary or copy)
                 unsigned d[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) d[g] = (unsigned)pack_fp8x4(v[g], inv_os);
+                for (int g = 0; g < 4; ++g) d[g] = (unsigned)pack_fp8x4(v, 4 * g, inv_os);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    swap_halves(d[2 * q], d[2 * q + 1]);        // -> couts 16q + 8fh .. +7 of this pixel
+                    epi_chunk8(d[2 * q], d[2 * q + 1]);         // -> couts 16q + 8fh .. +7 of this pixel
                     const int co = c0 + crow0 + j * 32 + 16 * q + 8 * fh;
-                    if (FULL || (mok && co < p.Cout))
-                        *reinterpret_cast<uint2*>(dst8 + obase + co) = make_uint2(d[2 * q], d[2 * q + 1]);
+                    if (FULL || (mok && co < p.Cout)) *reinterpret_cast<uint2*>(dst8 + obase + co) = make_uint2(d[2 * q], d[2 * q + 1]);
                 }
             }
         }

@@ -21,7 +21,7 @@
 
 namespace frp {
 
-// (vector typedefs and the half-wave exchange `swap_halves` come from conv_common.h)
+// (vector typedefs and the epilogue pieces - value, fp16 conversion, half-wave exchange into store chunks: epi_* - come from conv_common.h)
 
 #define ST_ROWS 4
 #define ST_COLS 64
@@ -30,7 +30,8 @@ namespace frp {
 #define ST_PITCH 392                     // halfs per patch row
 
 // bias + ReLU + fp16 pack of one accumulator quad, two elements per instruction (v_pk_add_f32, v_cvt_pk_f16_f32,
-// v_pk_max_f16; relu(round16(y)) == round16(relu(y))): -> two dwords of packed halfwords
+// v_pk_max_f16; relu(round16(y)) == round16(relu(y)): the bits of epi_value<FRP_ACT_RELU, 0> + epi_half4, in half the
+// instructions): -> two dwords of packed halfwords
 __device__ __forceinline__ void bias_relu_pack(const floatx16& acc, int g, floatx4 b, unsigned (&out)[2]) {
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2) {
@@ -129,21 +130,20 @@ __global__ __launch_bounds__(256) void stem_u8_kernel(StemParams p) {
         }
         const int ox = ox0 + oxl;
         // (all 64 lanes take part in the half-wave exchange; only the stores are predicated)
-        union { half4 v; unsigned u[2]; } pk[4];
+        half4 pk[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pk[g].v[e] = (_Float16)fmaxf(acc[4 * g + e] + bias4[g][e], 0.f);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            swap_halves(pk[2 * q].u[0], pk[2 * q + 1].u[0]);
-            swap_halves(pk[2 * q].u[1], pk[2 * q + 1].u[1]);
+        for (int g = 0; g < 4; ++g) {
+            floatx4 v;
+            epi_value<FRP_ACT_RELU, 0>(v, 0, acc, g, reinterpret_cast<const float*>(&bias4[g]), nullptr, 0);
+            pk[g] = epi_half4(v);
         }
+        u32x4 o4[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) o4[q] = epi_chunk(pk[2 * q], pk[2 * q + 1]);
         if (oy < p.Ho && ox < p.Wo) {
             _Float16* o = p.out + (((long)b * p.Ho + oy) * p.Wo + ox) * 32;
 #pragma unroll
-            for (int q = 0; q < 2; ++q)
-                *reinterpret_cast<uint4*>(o + 16 * q + 8 * h) = make_uint4(pk[2 * q].u[0], pk[2 * q].u[1], pk[2 * q + 1].u[0], pk[2 * q + 1].u[1]);
+            for (int q = 0; q < 2; ++q) *reinterpret_cast<u32x4*>(o + 16 * q + 8 * h) = o4[q];
         }
     }
 }
@@ -391,19 +391,15 @@ __global__ __launch_bounds__(256, 2) void stem12_u8_kernel(Stem12Params p) {
                 pk[g].u[0] = inside ? pk[g].u[0] : 0u;
                 pk[g].u[1] = inside ? pk[g].u[1] : 0u;
             }
+            u32x4 o4[2];
 #pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                swap_halves(pk[2 * qq].u[0], pk[2 * qq + 1].u[0]);
-                swap_halves(pk[2 * qq].u[1], pk[2 * qq + 1].u[1]);
-            }
+            for (int qq = 0; qq < 2; ++qq) o4[qq] = epi_chunk(pk[2 * qq].u, pk[2 * qq + 1].u);
             // after the exchange lane (pixel r, half h) holds couts 16*qq + 8*h .. +7 of its pixel.  But the
             // exchange pairs lane l with l+32: `inside` of both lanes is the same pixel, so the zeros agree.
             if (!extra || r < S12_S1R) {
                 unsigned char* dst = s1 + ((row * 2 + (col & 1)) * 33 + (col >> 1)) * S12_PIX;
 #pragma unroll
-                for (int qq = 0; qq < 2; ++qq)
-                    *reinterpret_cast<uint4*>(dst + (2 * qq + h) * 16) =
-                        make_uint4(pk[2 * qq].u[0], pk[2 * qq].u[1], pk[2 * qq + 1].u[0], pk[2 * qq + 1].u[1]);
+                for (int qq = 0; qq < 2; ++qq) *reinterpret_cast<u32x4*>(dst + (2 * qq + h) * 16) = o4[qq];
             }
         }
         __syncthreads();
@@ -425,17 +421,13 @@ __global__ __launch_bounds__(256, 2) void stem12_u8_kernel(Stem12Params p) {
             struct { unsigned u[2]; } pk[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) bias_relu_pack(acc, g, b2[g], pk[g].u);
+            u32x4 o4[2];
 #pragma unroll
-            for (int qq = 0; qq < 2; ++qq) {
-                swap_halves(pk[2 * qq].u[0], pk[2 * qq + 1].u[0]);
-                swap_halves(pk[2 * qq].u[1], pk[2 * qq + 1].u[1]);
-            }
+            for (int qq = 0; qq < 2; ++qq) o4[qq] = epi_chunk(pk[2 * qq].u, pk[2 * qq + 1].u);
             if (oy < p.Ho2 && ox < p.Wo2) {
                 _Float16* o = p.out + (((long)b * p.Ho2 + oy) * p.Wo2 + ox) * 64 + 32 * g2;
 #pragma unroll
-                for (int qq = 0; qq < 2; ++qq)
-                    *reinterpret_cast<uint4*>(o + 16 * qq + 8 * h) =
-                        make_uint4(pk[2 * qq].u[0], pk[2 * qq].u[1], pk[2 * qq + 1].u[0], pk[2 * qq + 1].u[1]);
+                for (int qq = 0; qq < 2; ++qq) *reinterpret_cast<u32x4*>(o + 16 * qq + 8 * h) = o4[qq];
             }
         }
         // (no barrier here: the next tile's phase A only writes `patch`, which phase C does not read, and
@@ -537,25 +529,20 @@ __global__ __launch_bounds__(256) void emb_stem_kernel(EmbStemParams p) {
             }
 #pragma unroll
             for (int cg = 0; cg < 2; ++cg) {
-                union { half4 v; unsigned u[2]; } pk[4];
+                half4 pk[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = acc[cg][4 * g + e] + bias[cg][g][e];
-                        pk[g].v[e] = (_Float16)(v > 0.f ? v : v * slope[cg][g][e]);
-                    }
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    swap_halves(pk[2 * qq].u[0], pk[2 * qq + 1].u[0]);
-                    swap_halves(pk[2 * qq].u[1], pk[2 * qq + 1].u[1]);
+                for (int g = 0; g < 4; ++g) {
+                    floatx4 v;
+                    epi_value<FRP_ACT_PRELU, 0>(v, 0, acc[cg], g, reinterpret_cast<const float*>(&bias[cg][g]), reinterpret_cast<const float*>(&slope[cg][g]), 0);
+                    pk[g] = epi_half4(v);
                 }
+                u32x4 o4[2];
+#pragma unroll
+                for (int qq = 0; qq < 2; ++qq) o4[qq] = epi_chunk(pk[2 * qq], pk[2 * qq + 1]);
                 if (oy < p.H && ox < p.W) {
                     _Float16* o = p.out + (((long)img * p.H + oy) * p.W + ox) * 64 + 32 * cg;
 #pragma unroll
-                    for (int qq = 0; qq < 2; ++qq)
-                        *reinterpret_cast<uint4*>(o + 16 * qq + 8 * h) =
-                            make_uint4(pk[2 * qq].u[0], pk[2 * qq].u[1], pk[2 * qq + 1].u[0], pk[2 * qq + 1].u[1]);
+                    for (int qq = 0; qq < 2; ++qq) *reinterpret_cast<u32x4*>(o + 16 * qq + 8 * h) = o4[qq];
                 }
             }
         }

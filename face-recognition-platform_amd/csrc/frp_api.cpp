@@ -178,7 +178,7 @@ int run_detect(frp_handle* h, const Switches& sw, int K, float det_thresh, float
         if (h->det.dims[bi].c != 32) return fail(h, FRP_ERR_BLOB, "detector head must have 32 channels");
     }
     FRPCHK(run_decode(h, head, dims, B, K, det_thresh, nms_iou, flags, out));
-    if (!out) FRPCHK(compact_faces(h, B, K));
+    if (!out && !(flags & FRP_FLAG_TRACK)) FRPCHK(compact_faces(h, B, K));          // (a tracked pass: track_begin lists the faces, run_faces)
     rec(h, EV_DEC);
     return FRP_OK;
 }
@@ -233,13 +233,18 @@ int run_align(frp_handle* h, int K, int n, const int32_t* n_dev, uint32_t flags,
 
 // align + embed + match for the faces listed in h->kps / h->counts / h->face_slot (device), always from
 // the full-resolution resident frames.  n_known >= 0: face count known on the host.  This is where a pass begins.
+// FRP_FLAG_TRACK (checked by the caller: track_check): the face list is the tracker's - the detections that continue no identified
+// track - so the count is known on the device only, whatever the caller knew; behind the matcher every live slot gets its result
 int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t flags) {
     const int B = h->rB;
+    const bool tracked = (flags & FRP_FLAG_TRACK) != 0;
+    if (tracked) n_known = -1;
     const bool want_within = (flags & FRP_FLAG_WITHIN) && !(flags & FRP_FLAG_NO_MATCH);
     const bool want_groups = (flags & FRP_FLAG_GROUPS) != 0;          // (checked by the caller: check_match_flags)
     // a device-count pass that nobody fetched or synchronised yet (two process calls queued back to back): its count and its
     // counter corrections live in single slots (h_nfaces, Pass) this pass is about to reuse - settle it first
     FRPCHK(settle_count(h, false));
+    if (tracked) FRPCHK(track_begin(h, B, K));
     // Threshold mode (the reference's loop, routes/camera.py:232-259): how many faces the detector kept is known on the
     // device only.  It STAYS there: align, the embedder's kernels, the l2norm and the matcher are launched for the capacity
     // B x K and read the count from device memory (grids sized for the capacity; workgroups beyond the real tiles leave at
@@ -255,6 +260,8 @@ int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t fl
     h->pass.within_cap = want_within ? h->m.within_cap : 0;
     h->pass.nfaces = n_known < 0 ? -1 : n_known;          // -1: pending
     h->pass.cap = n_known < 0 ? B * K : n_known;
+    h->pass.tracked = tracked;
+    h->pass.track_matched = tracked && !(flags & FRP_FLAG_NO_MATCH) && h->g_rows > 0;
     if (n_known < 0 && !dev_count) FRPCHK(settle_count(h, false));   // the former path waits now (and counts the faces ahead of the launches)
     const int n = dev_count ? B * K : h->pass.nfaces;          // the faces everything below is launched for
     const double flops0 = h->ctr.emb_conv_flops, f8flops0 = h->ctr.f8_conv_flops;
@@ -268,6 +275,7 @@ int run_faces(frp_handle* h, const Switches& sw, int K, int n_known, uint32_t fl
     } else {
         rec(h, EV_ALIGN); rec(h, EV_EMB); rec(h, EV_L2); rec(h, EV_MATCH);
     }
+    if (tracked) FRPCHK(track_finish(h, h->pass.matched));          // (also when nothing was embedded: the reused slots, the tables)
     h->ctr.frames += B;
     if (n_dev) {
         h->pass.pend_flops = h->ctr.emb_conv_flops - flops0;      // charged for the capacity: corrected once the count is known
@@ -290,6 +298,7 @@ int begin_detect_only_pass(frp_handle* h, int B, int K) {
 // a flagged pass needs frp_set_within / frp_set_frame_groups for its B frames; checked before a pass launches anything or overwrites
 // anything of the last one
 int check_match_flags(frp_handle* h, uint32_t flags, int B) {
+    FRPCHK(track_check(h, flags, B));
     if ((flags & FRP_FLAG_WITHIN) && !(flags & FRP_FLAG_NO_MATCH) && h->m.within_cap <= 0)
         return fail(h, FRP_ERR_INVALID, "FRP_FLAG_WITHIN: call frp_set_within first");
     if (flags & FRP_FLAG_GROUPS) {
@@ -368,13 +377,16 @@ int fetch_results(frp_handle* h, float* boxes, float* kps, float* scores, int32_
     FRPCHK(settle_count(h, false));          // device-count pass: one short wait for the count, then copy exactly n rows
     const int n = h->pass.nfaces;
     const size_t s = (size_t)B * K;
-    const bool want_emb = n > 0 && emb, want_match = n > 0 && h->pass.matched && (match_idx || match_cos);
+    const bool tracked = h->pass.tracked;      // every live slot has a result, embedded in this pass or not: the per-slot arrays
+    const bool want_emb = tracked ? emb != nullptr : n > 0 && emb;
+    const bool want_match = (tracked ? h->pass.track_matched : n > 0 && h->pass.matched) && (match_idx || match_cos);
+    const size_t rows = tracked ? s : (size_t)n;          // result rows copied: all slots, or the compact faces
     // staging layout: counts | boxes | kps | scores | emb (compact, n rows) | idx | cos
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_cnt = take((size_t)B * 4), o_box = take(boxes ? s * 16 : 0), o_kps = take(kps ? s * 40 : 0),
-                 o_sc = take(scores ? s * 4 : 0), o_emb = take(want_emb ? (size_t)n * FRP_EMB_DIM * 4 : 0),
-                 o_idx = take(want_match ? (size_t)n * 4 : 0), o_cos = take(want_match ? (size_t)n * 4 : 0);
+                 o_sc = take(scores ? s * 4 : 0), o_emb = take(want_emb ? rows * FRP_EMB_DIM * 4 : 0),
+                 o_idx = take(want_match ? rows * 4 : 0), o_cos = take(want_match ? rows * 4 : 0);
     FRPCHK(ensure_pinned(h, off));
     unsigned char* st = h->pin_stage;
     HIPCHK(h, hipMemcpyAsync(st + o_cnt, h->counts.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
@@ -382,10 +394,11 @@ int fetch_results(frp_handle* h, float* boxes, float* kps, float* scores, int32_
     if (kps) HIPCHK(h, hipMemcpyAsync(st + o_kps, h->kps.p, s * 40, hipMemcpyDeviceToHost, h->stream));
     if (scores) HIPCHK(h, hipMemcpyAsync(st + o_sc, h->scores.p, s * 4, hipMemcpyDeviceToHost, h->stream));
     if (want_emb)
-        HIPCHK(h, hipMemcpyAsync(st + o_emb, h->emb.bufs[h->hdr.emb_out_buf].p, (size_t)n * FRP_EMB_DIM * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + o_emb, tracked ? h->trk.slot_emb.p : h->emb.bufs[h->hdr.emb_out_buf].p, rows * FRP_EMB_DIM * 4,
+                                 hipMemcpyDeviceToHost, h->stream));
     if (want_match) {
-        HIPCHK(h, hipMemcpyAsync(st + o_idx, h->m.best_idx.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(st + o_cos, h->m.best_cos.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + o_idx, tracked ? h->trk.slot_idx.p : h->m.best_idx.p, rows * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(st + o_cos, tracked ? h->trk.slot_cos.p : h->m.best_cos.p, rows * 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     settle_events(h, true);
@@ -403,13 +416,14 @@ int fetch_results(frp_handle* h, float* boxes, float* kps, float* scores, int32_
         const int nb = std::max(0, std::min(cnt[b], K));
         for (int k = 0; k < K; ++k) {
             const size_t slot = (size_t)b * K + k;
-            const bool live = k < nb && f < n;
+            const bool live = tracked ? k < nb : k < nb && f < n;
+            const size_t r = tracked ? slot : (size_t)f;          // the slot's result row
             if (emb) {
-                if (live && want_emb) memcpy(emb + slot * FRP_EMB_DIM, cemb + (size_t)f * FRP_EMB_DIM, FRP_EMB_DIM * 4);
+                if (live && want_emb) memcpy(emb + slot * FRP_EMB_DIM, cemb + r * FRP_EMB_DIM, FRP_EMB_DIM * 4);
                 else memset(emb + slot * FRP_EMB_DIM, 0, FRP_EMB_DIM * 4);
             }
-            if (match_idx) match_idx[slot] = (live && want_match) ? cidx[f] : -1;
-            if (match_cos) match_cos[slot] = (live && want_match) ? ccos[f] : -1.f;
+            if (match_idx) match_idx[slot] = (live && want_match) ? cidx[r] : -1;
+            if (match_cos) match_cos[slot] = (live && want_match) ? ccos[r] : -1.f;
             if (live) ++f;
         }
     }
@@ -447,7 +461,7 @@ int validate_face_list(frp_handle* h, const float* kps, const int32_t* counts, i
 }
 
 // ... into the handle's result buffers (boxes and scores where the caller has them), compacted as the detector's own
-int upload_face_list(frp_handle* h, int K, const float* boxes, const float* kps, const float* scores, const int32_t* counts) {
+int upload_face_list(frp_handle* h, int K, const float* boxes, const float* kps, const float* scores, const int32_t* counts, bool compact = true) {
     const int B = h->rB;
     const size_t s = (size_t)B * K;
     FRPCHK(ensure_results(h, B, K));
@@ -455,7 +469,7 @@ int upload_face_list(frp_handle* h, int K, const float* boxes, const float* kps,
     HIPCHK(h, hipMemcpyAsync(h->counts.p, counts, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
     if (boxes) HIPCHK(h, hipMemcpyAsync(h->boxes.p, boxes, s * 16, hipMemcpyHostToDevice, h->stream));
     if (scores) HIPCHK(h, hipMemcpyAsync(h->scores.p, scores, s * 4, hipMemcpyHostToDevice, h->stream));
-    return compact_faces(h, B, K);
+    return compact ? compact_faces(h, B, K) : FRP_OK;
 }
 
 }  // namespace
@@ -562,6 +576,7 @@ void frp_destroy(frp_handle* h) {
     for (DevBuf* b : all) release(*b);
     for (int i = 0; i < EV_COUNT; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->m.frame_groups_ev) (void)hipEventDestroy(h->m.frame_groups_ev);
+    release_tracks(h);
     if (h->h_nfaces) (void)hipHostFree(h->h_nfaces);
     if (h->pin_stage) (void)hipHostFree(h->pin_stage);
     release_ingest(h);
@@ -616,6 +631,7 @@ int frp_process_pyramid(frp_handle* h, int32_t n_scales, const int32_t* det_hw, 
                         float nms_iou, uint32_t flags) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    if (flags & FRP_FLAG_TRACK) return fail(h, FRP_ERR_INVALID, "process_pyramid: FRP_FLAG_TRACK is not supported under a cross-scale merge");
     FRPCHK(check_match_flags(h, flags, h->rB));
     if (!h->have_weights) return fail(h, FRP_ERR_INVALID, "process_pyramid: no weights loaded");
     if (h->rB <= 0) return fail(h, FRP_ERR_INVALID, "process_pyramid: no resident frames (call frp_upload_frames)");
@@ -715,7 +731,8 @@ int frp_finish_faces(frp_handle* h, int32_t B_in, const float* boxes, const floa
     int n;
     FRPCHK(validate_face_list(h, kps, counts, max_faces, n));
     FRPCHK(check_match_flags(h, flags, h->rB));
-    FRPCHK(upload_face_list(h, max_faces, boxes, kps, scores, counts));
+    if ((flags & FRP_FLAG_TRACK) && !boxes) return fail(h, FRP_ERR_INVALID, "finish_faces: FRP_FLAG_TRACK needs the boxes");
+    FRPCHK(upload_face_list(h, max_faces, boxes, kps, scores, counts, !(flags & FRP_FLAG_TRACK)));
     rec(h, EV_DEC);
     FRPCHK(run_faces(h, read_switches(), max_faces, n, flags));
     FRPCHK(fetch_results(h, nullptr, nullptr, nullptr, nullptr, emb, match_idx, match_cos));

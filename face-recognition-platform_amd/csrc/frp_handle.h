@@ -71,6 +71,27 @@ struct Matcher {
     hipEvent_t frame_groups_ev = nullptr;
 };
 
+// Face tracks (track_api.cpp; kernels and table layout: track_kernels.hip).  Other readers: run_faces and fetch_results (frp_api.cpp)
+// through track_begin / track_finish / the per-slot arrays; the gallery entry points set `stale`; frp_destroy releases the buffers.
+struct Tracks {
+    int max_streams = 0;                 // 0: frp_track_config has not been called (or released everything)
+    float iou_min = 0.f;
+    int refresh = 0, max_missed = 0;
+    // the next tracked pass embeds every face: a cached match_idx must never outlive a row move (set by frp_track_config, every
+    // gallery mutation and frp_gallery_exact; cleared where a tracked pass is queued)
+    bool stale = false;
+    frp::DevBuf hdr, meta, tab_emb, plan, totals;      // TrackParams: per-stream headers, table halves, plans; the two totals
+    // frp_set_frame_streams: the stream of every frame for the flagged passes to come (empty: not set), the streams that occur, and
+    // their device copy [B + n_present], uploaded by the first pass after a change (life cycle of Matcher::frame_groups)
+    std::vector<int32_t> streams, present;
+    frp::DevBuf streams_dev;
+    bool streams_dirty = false, streams_copying = false;
+    hipEvent_t streams_ev = nullptr;
+    // the last tracked pass: its shape and its per-slot arrays - slot_i32 = track_id | reused | age | src | pos, [B x K] each
+    int B = 0, K = 0;
+    frp::DevBuf slot_i32, slot_emb, slot_idx, slot_cos;
+};
+
 // Everything that describes the last pass, i.e. what the handle's result buffers hold.  Started as a whole where a pass begins
 // (run_faces; the detect-only entry points), never field by field: a new pass cannot inherit a flag of the one before.
 struct Pass {
@@ -82,6 +103,10 @@ struct Pass {
     bool within_lists = false;   // ... and it matched (faces and a gallery): hit_* hold its lists
     bool q16_of_pass = false;    // q16 still holds its queries (a list that overflowed is rebuilt from them at fetch time)
     bool groups = false;         // it matched with FRP_FLAG_GROUPS: q_groups holds its faces' masks
+    // FRP_FLAG_TRACK: nfaces counts the EMBEDDED faces; every live slot's emb / idx / cos are in Tracks' per-slot arrays (fetch_results
+    // reads them instead of scattering the compact results).  track_matched: the pass wanted a match (flags and a gallery) - reused
+    // slots carry one also where nothing was embedded, so `matched` alone does not say it
+    bool tracked = false, track_matched = false;
     // device-count pass: the embedder's FLOPs were charged for pend_cap faces, corrected once the count is known (settle_count)
     int pend_cap = 0;
     double pend_flops = 0.0, pend_f8flops = 0.0;
@@ -126,6 +151,7 @@ struct frp_handle {
     frp::DevBuf pyr_boxes, pyr_kps, pyr_scores, pyr_counts;
     Matcher m;                 // queries, work buffers and hit lists of the matcher
     Pass pass;                 // what the buffers above hold: the last pass
+    Tracks trk;                // face tracks: configuration, per-stream tables, the last tracked pass's per-slot results
     bool ev_pending = false;   // frp_process_resident's stage events are recorded but not yet read (see settle_events)
     // frp_face_quality: rectangles + tile prefix in, per-tile partials + per-rectangle sums out (its own: the last pass's results stay)
     frp::DevBuf quality_in, quality_out;
@@ -232,6 +258,13 @@ FRP_LOCAL int match_pass(frp_handle* h, const frp::Switches& sw, int n, const in
 // gallery_api.cpp: the row masks in device memory, for a grouped match launch (built or brought up to date where they are not)
 FRP_LOCAL int row_groups_device(frp_handle* h, const uint32_t** out);
 inline void rec(frp_handle* h, int which) { if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream); }   // a stage event (timers on)
+// track_api.cpp: a pass with FRP_FLAG_TRACK over B frames can run (configured, streams set for B, no flag it does not combine with)
+FRP_LOCAL int track_check(frp_handle* h, uint32_t flags, int B);
+// ... its associate + compact launches on the detections in h->boxes / h->counts: face_slot / nfaces list the faces to embed
+FRP_LOCAL int track_begin(frp_handle* h, int B, int K);
+// ... its resolve + store launches behind the matcher (`matched`: best_idx / best_cos hold the embedded faces' top-1)
+FRP_LOCAL int track_finish(frp_handle* h, bool matched);
+FRP_LOCAL void release_tracks(frp_handle* h);                       // frp_destroy
 FRP_LOCAL bool init_ingest(frp_handle* h);                          // ingest_api.cpp: the copy stream and its events (frp_create)
 FRP_LOCAL void release_ingest(frp_handle* h);                       // ... and everything `in` holds (frp_destroy)
 FRP_LOCAL int upload_frames(frp_handle* h, const uint8_t* bgr, int B, int H, int W, int64_t row_stride);   // into the resident buffer, stream-ordered

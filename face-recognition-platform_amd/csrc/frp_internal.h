@@ -413,6 +413,55 @@ hipError_t launch_chips_to_blob(const uint8_t* chips, int M, _Float16* out, hipS
 hipError_t launch_compact_faces(const int32_t* counts, int B, int max_faces, int32_t* face_slot, int32_t* n_faces,
                                 hipStream_t stream);
 
+// Face tracks (track_kernels.hip; frp.h: frp_track_config): which detections of a pass belong to a face identified before, the embed
+// list of the others, and the cached results of the rest.  Per stream two table halves of FRP_TRACK_SLOTS entries: a pass reads the
+// half `cur` of the stream's header and writes the other one.
+#define FRP_TRACK_SLOTS 128
+struct alignas(16) TrackEntry {            // one row of a table half (48 bytes)
+    float box[4];
+    int32_t id, age, missed;
+    int32_t match_idx;
+    float match_cos;
+    int32_t src;               // of the pass that wrote the row: where its emb / match_idx / match_cos come from (a slot's `src` below)
+    int32_t pad[2];
+};
+static_assert(sizeof(TrackEntry) == 48, "three 16-byte words");
+struct TrackHeader { int32_t next_id, n, cur, pad; };      // per stream: the next new id, rows of the current half, which half that is
+struct TrackPlan { int32_t old_half, n_new; };             // per stream, written by the associate launch of a pass for its store launch
+struct TrackParams {
+    // configuration and state
+    int max_streams;
+    float iou_min;
+    int refresh, max_missed, stale;
+    TrackHeader* hdr;          // [max_streams]
+    TrackEntry* meta;          // [max_streams][2][FRP_TRACK_SLOTS]
+    float* tab_emb;            // [max_streams][2][FRP_TRACK_SLOTS][512]
+    TrackPlan* plan;           // [max_streams]
+    int64_t* totals;           // [2]: embedded, reused
+    // the pass: B frames of K slots, stream per frame, the streams that occur (each once)
+    int B, K;
+    const int32_t* streams;    // [B], -1: an untracked frame
+    const int32_t* present;    // [n_present]
+    int n_present;
+    const float* boxes;        // [B][K][4]
+    const int32_t* counts;     // [B]
+    // per slot [B][K].  src >= 0: the slot of this batch whose embedding it carries (its own: an embedded slot); src < 0, not
+    // FRP_TRACK_DEAD: row -1 - src of the stream's old half; FRP_TRACK_DEAD: a slot at or beyond counts[b]
+    int32_t *track_id, *reused, *age, *src;
+    int32_t* pos;              // compact position of an embedded slot, -1 otherwise
+    int32_t *face_slot, *nfaces;
+    // compact results of the embedded faces (best_idx / best_cos null: the pass did not match) and the per-slot results
+    const float* emb;          // [n][512]
+    const int32_t* best_idx;
+    const float* best_cos;
+    float* slot_emb;           // [B][K][512]
+    int32_t* slot_idx;
+    float* slot_cos;
+};
+#define FRP_TRACK_DEAD INT32_MIN
+hipError_t launch_track_associate(const TrackParams& p, hipStream_t stream);      // + the compact launch behind it
+hipError_t launch_track_resolve(const TrackParams& p, hipStream_t stream);        // + the table store behind it
+
 // K5 tail: row-wise L2 normalisation of [M,512] fp32 (in place) + fp16 copy for the matcher.
 // With `partials` (split-K FC): emb[m][c] = sum_s partials[s][m][c] + bias[c] first.
 // `n_dev` (optional): the real row count lives in device memory (M is then the capacity); with ksplit == -1 the split

@@ -170,6 +170,7 @@ extern "C" {
 int frp_gallery_set(frp_handle* h, const void* emb, int64_t n, int32_t d, int32_t dtype) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     FRPCHK(refuse_while_reserved(h));
     if (n < 0 || (n > 0 && !emb) || d != FRP_EMB_DIM) return fail(h, FRP_ERR_INVALID, "gallery must be [n x 512]");
     ScopedBuf fresh, fresh_x;   // new snapshot(s), swapped in when complete
@@ -192,6 +193,7 @@ int frp_gallery_set(frp_handle* h, const void* emb, int64_t n, int32_t d, int32_
 int frp_gallery_set_device(frp_handle* h, const void* dev_f16, int64_t n, int32_t d) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     FRPCHK(refuse_while_reserved(h));
     if (n <= 0 || !dev_f16 || d != FRP_EMB_DIM) return fail(h, FRP_ERR_INVALID, "gallery must be [n x 512] fp16 on the device");
     ScopedBuf fresh, fresh_x;
@@ -227,6 +229,7 @@ int frp_gallery_cancel(frp_handle* h) {
 int frp_gallery_commit(frp_handle* h, int64_t n_rows) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     if (!h->g_reserved.p || n_rows < 0 || (size_t)n_rows * FRP_EMB_DIM * 2 > h->g_reserved.cap)
         return fail(h, FRP_ERR_INVALID, "gallery commit without a matching reservation");
     HIPCHK(h, hipStreamSynchronize(h->stream));      // nothing of this handle still reads the old snapshot
@@ -286,6 +289,7 @@ int frp_dist_destroy(frp_handle* h) {
 int frp_gallery_allgather(frp_handle* h, const void* shard, int64_t shard_rows, int32_t dtype, int64_t n_total) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     if (!h->comm) return fail(h, FRP_ERR_INVALID, "no communicator (frp_dist_init)");
     FRPCHK(refuse_while_reserved(h));
     const int world = h->dist_world, rank = h->dist_rank;
@@ -326,6 +330,7 @@ const void* frp_gallery_device_ptr(frp_handle* h) {
 int frp_gallery_update_row(frp_handle* h, int64_t row, const void* emb, int32_t d, int32_t dtype) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     FRPCHK(refuse_while_reserved(h));
     if (!emb || d != FRP_EMB_DIM || row < 0 || row > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery row");
     std::vector<float> f;
@@ -348,6 +353,7 @@ int frp_gallery_update_row(frp_handle* h, int64_t row, const void* emb, int32_t 
 int frp_gallery_remove_row(frp_handle* h, int64_t row) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     FRPCHK(refuse_while_reserved(h));
     if (row < 0 || row >= h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery row");
     const int64_t last = h->g_rows - 1;
@@ -382,6 +388,7 @@ int frp_gallery_get(frp_handle* h, void* out_f16, int64_t first_row, int64_t n_r
 int frp_gallery_set_groups(frp_handle* h, const uint32_t* groups, int64_t first_row, int64_t n_rows) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     FRPCHK(refuse_while_reserved(h));
     if (!groups || first_row < 0 || n_rows < 0 || first_row + n_rows > h->g_rows) return fail(h, FRP_ERR_INVALID, "bad gallery range");
     std::copy(groups, groups + n_rows, h->g_groups.begin() + first_row);
@@ -399,6 +406,7 @@ int frp_gallery_get_groups(frp_handle* h, uint32_t* out, int64_t first_row, int6
 int frp_gallery_exact(frp_handle* h, int32_t on) {
     if (!h) return FRP_ERR_INVALID;
     Guard g(h);
+    h->trk.stale = true;          // (frp.h, face tracks: a cached match must not outlive a change of the rows; set even where the call then fails)
     if (!on) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         release(h->gx); release(h->gx_q); release(h->gx_out);

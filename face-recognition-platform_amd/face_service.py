@@ -34,7 +34,7 @@ from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tu
 
 import numpy as np
 
-from . import ingest, lanes, native, pyramid
+from . import ingest, lanes, native, pyramid, tracks
 from .gallery import Gallery
 from .mjpeg import JpegBatch
 from .yuv import YuvBatch
@@ -60,6 +60,7 @@ _CAPS = {
     "lane": ("upload_frames_async", "swap_frames", "process_resident", "fetch_results", "sequence"),    # process_stream's overlapped form
     "stage_jpeg": ("upload_jpeg_async",),            # process_frames stages a JpegBatch: upload, swap, pass, fetch under sequence()
     "stage_yuv": ("upload_yuv_async", "swap_frames"),                                                    # ... a YuvBatch
+    "track": ("track_config", "set_frame_streams", "fetch_tracks"),      # face tracks: streams=
 }
 EngineCaps = namedtuple("EngineCaps", list(_CAPS))
 
@@ -133,10 +134,12 @@ def match_dicts(targets: Sequence[str], tol: float, hits=None, row=None, flag: b
 
 
 def face_dicts(out: Dict[str, np.ndarray], row_names: Dict[int, str], tol: float, all_matches: bool = False, names: Optional[List[str]] = None,
-               hits=None, dist_rows=None, qual=None) -> Tuple[List[List[Dict[str, Any]]], int]:
+               hits=None, dist_rows=None, qual=None, streams=None) -> Tuple[List[List[Dict[str, Any]]], int]:
     """The fetched arrays `out` of one pass -> (per frame its list of face dicts, the number of faces).  `row_names`: gallery row -> name
     as it was under the guard; all_matches: every face gets "matches" - match_dicts of `names` from `hits` or `dist_rows` (one entry per
-    face), [] when neither is given; `qual`: per face its quality dict.  Host arithmetic on its arguments: no device call, no lock.
+    face), [] when neither is given; `qual`: per face its quality dict; `streams`: the pass was tracked - one stream per frame, and `out`
+    holds "track_id" / "reused": every face gets "track_id", "stream" and "tracked" (True: the result is its track's, not embedded in this
+    pass).  Host arithmetic on its arguments: no device call, no lock.
     One pass of array arithmetic for the whole batch (distance, bucket, threshold), ONE tolist() per field; the per-face work left is
     building the dict (the reference builds N of them per face, camera.py:243-259)."""
     counts = np.asarray(out["counts"], dtype=np.int64)
@@ -151,9 +154,11 @@ def face_dicts(out: Dict[str, np.ndarray], row_names: Dict[int, str], tol: float
     boxes, kps, scores = out["boxes"][live].tolist(), out["kps"][live].tolist(), out["scores"][live].tolist()
     emb = out["emb"][live]                                            # [n, 512]: one gather, rows handed out as views
     rows_l, hit_l, cos_l, dist_l, conf_l, match_l = rows.tolist(), hit.tolist(), cos.tolist(), dist.tolist(), conf.tolist(), is_match.tolist()
+    if streams is not None:
+        tid_l, reu_l = out["track_id"][live].tolist(), out["reused"][live].tolist()
     result = []
     n = 0
-    for c in counts.tolist():
+    for b, c in enumerate(counts.tolist()):
         faces = []
         for i in range(n, n + c):
             h_ = hit_l[i]
@@ -166,6 +171,8 @@ def face_dicts(out: Dict[str, np.ndarray], row_names: Dict[int, str], tol: float
                                    match_dicts(names, tol, row=dist_rows[i]) if dist_rows is not None else [])
             if qual is not None:
                 face["quality"] = qual[i]
+            if streams is not None:
+                face["track_id"], face["stream"], face["tracked"] = tid_l[i], int(streams[b]), bool(reu_l[i])
             faces.append(face)
         n += c
         result.append(faces)
@@ -223,6 +230,7 @@ class _Plan(NamedTuple):
     list_all: bool                           # all_matches on a gallery that has rows
     quality: bool
     groups: Optional[Tuple[int, ...]] = None # one mask per frame (FLAG_GROUPS is in flags): set_frame_groups before the pass
+    streams: Optional[Tuple[int, ...]] = None  # one track stream per frame (FLAG_TRACK is in flags): set_frame_streams before, fetch_tracks after
 
 
 BLOCKING, STAGED, OVERLAPPED = "blocking", "staged", "overlapped"
@@ -270,6 +278,23 @@ def _frame_groups(caps: EngineCaps, groups, n_frames: int) -> Optional[Tuple[int
     if not caps.groups:
         raise ValueError("groups needs an engine with gallery groups (set_frame_groups)")
     return masks
+
+
+def _frame_streams(caps: EngineCaps, streams, n_frames: int, all_matches, groups, det_scales) -> Tuple[int, ...]:
+    """streams= of a frame pass as one stream per frame; ValueError before anything reaches the engine"""
+    if all_matches or groups is not None or det_scales is not None:
+        raise ValueError("streams does not combine with all_matches, groups or det_scales")
+    try:
+        ids = tuple(int(v) for v in streams)
+    except TypeError:
+        raise ValueError("streams: one stream index per frame") from None
+    if len(ids) != n_frames:
+        raise ValueError(f"streams: one stream per frame ({n_frames}), not {len(ids)}")
+    if any(v < -1 for v in ids):
+        raise ValueError("streams: indices are >= 0, or -1 for a frame that is not tracked")
+    if not caps.track:
+        raise ValueError("streams needs an engine with face tracks (track_config)")
+    return ids
 
 
 def _n_frames(frames) -> int:
@@ -892,7 +917,7 @@ class FaceService:
     # ------------------------------------------------------------------ streaming entry points (new)
     def process_frames(self, frames_bgr: np.ndarray, max_faces: int = 10, threshold: Optional[float] = None,
                        det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
-                       det_scales: Optional[Sequence[float]] = None, groups=None) -> List[List[Dict[str, Any]]]:
+                       det_scales: Optional[Sequence[float]] = None, groups=None, streams=None) -> List[List[Dict[str, Any]]]:
         """The live-loop body of routes/camera.py:225-259 for a batch of BGR frames, with the
         per-face compare + filter reduced to a fused device top-1: per frame a list of
         {bbox, kps, score, embedding, target, distance, cosine, confidence, match}.
@@ -906,16 +931,21 @@ class FaceService:
         (Engine.process_pyramid_resident); 1 to 4 scales, each in (0, 2].  None: at native size only.
         groups=[mask per frame] (or one int for all): gallery groups - the faces of frame b are matched against the enrolled
         identities whose mask shares a bit with groups[b] only (store_face(..., groups=), Gallery.set_groups): "target" is the best
-        PERMITTED identity and "matches" lists permitted ones, as if the gallery held nothing else; mask 0 matches nobody."""
+        PERMITTED identity and "matches" lists permitted ones, as if the gallery held nothing else; mask 0 matches nobody.
+        streams=[stream index per frame] (configure_tracks first): face tracks - the frames of a stream are consecutive frames of one
+        camera, in batch order; a face that continues a track identified before is not embedded again but carries its track's result
+        (tracks.TrackModel has the rules).  Every face dict gains "track_id", "stream" and "tracked" (True: a reused result); -1 marks
+        a frame that is not tracked.  Not together with all_matches, groups or det_scales (ValueError)."""
         return self._process_frames_on(self._eng(), self.ENCODINGS.locked(), frames_bgr, max_faces, threshold, det_thresh, all_matches,
-                                       quality=quality, det_scales=det_scales, groups=groups)
+                                       quality=quality, det_scales=det_scales, groups=groups, streams=streams)
 
     def _process_frames_on(self, eng, guard, frames, max_faces, threshold, det_thresh, all_matches, take_next=None, staged=None,
-                           quality=False, det_scales=None, groups=None):
+                           quality=False, det_scales=None, groups=None, streams=None):
         """One frame pass on `eng`.  `take_next` / `staged` (process_stream on an engine with the lane calls): the overlapped form - this
         batch goes to the device through the engine's staging buffer (already there when the previous call staged it), the batch the
         lane will get next is claimed and its upload started on the copy stream while this batch's kernels run."""
         caps = engine_caps(eng)
+        frame_streams = _frame_streams(caps, streams, _n_frames(frames), all_matches, groups, det_scales) if streams is not None else None
         scales = _check_det_scales(caps, det_scales)
         frame_groups = _frame_groups(caps, groups, _n_frames(frames)) if groups is not None else None
         if isinstance(frames, YuvBatch):
@@ -929,11 +959,13 @@ class FaceService:
         # row -> name snapshot, so a concurrent delete can neither mis-attribute a face to the identity that was
         # moved into its row nor shrink the table under the lookup.
         with guard:
-            plan = self._plan(caps, len(G) > 0, max_faces, threshold, det_thresh, all_matches, quality, scales, frame_groups)
+            plan = self._plan(caps, len(G) > 0, max_faces, threshold, det_thresh, all_matches, quality, scales, frame_groups, frame_streams)
             if plan.within:
                 eng.set_within(within_min_cos(plan.tol), WITHIN_CAP)
             if plan.groups is not None:
                 eng.set_frame_groups(plan.groups)
+            if plan.streams is not None:
+                eng.set_frame_streams(plan.streams)
             if route == OVERLAPPED:
                 out, qual = self._overlapped_pass(eng, frames, plan, take_next, staged)
             elif route == STAGED:
@@ -948,7 +980,7 @@ class FaceService:
             listed = self._all_matches_of(eng, out, plan) if plan.list_all and int(out["counts"].sum()) > 0 else {}
 
         def finish():
-            result, n = face_dicts(out, row_names, plan.tol, all_matches, qual=qual, **listed)
+            result, n = face_dicts(out, row_names, plan.tol, all_matches, qual=qual, streams=plan.streams, **listed)
             with self._metrics_lock:
                 self._metrics["total_encodings"] += n
                 self._metrics["total_comparisons"] += n * n_gallery
@@ -959,7 +991,7 @@ class FaceService:
         return lanes.Deferred(finish) if route == OVERLAPPED else finish()
 
     def _plan(self, caps: EngineCaps, have_gallery: bool, max_faces, threshold, det_thresh, all_matches, quality, scales,
-              frame_groups=None) -> "_Plan":
+              frame_groups=None, frame_streams=None) -> "_Plan":
         tol = self.tolerance if threshold is None else min(self.tolerance, threshold)   # camera.py:250
         list_all = bool(all_matches) and have_gallery
         # all_matches on the device: the pass's own match kernel also lists every row within the bound (FLAG_WITHIN)
@@ -968,7 +1000,10 @@ class FaceService:
         groups = frame_groups if have_gallery else None          # (an empty gallery: FLAG_NO_MATCH, which the grouped pass refuses)
         if groups is not None:
             flags |= native.FLAG_GROUPS
-        return _Plan(max_faces, tol, DET_THRESH if det_thresh is None else det_thresh, flags, scales, within, list_all, bool(quality), groups)
+        if frame_streams is not None:
+            flags |= native.FLAG_TRACK
+        return _Plan(max_faces, tol, DET_THRESH if det_thresh is None else det_thresh, flags, scales, within, list_all, bool(quality), groups,
+                     frame_streams)
 
     def _overlapped_pass(self, eng, frames, plan: "_Plan", take_next, staged):
         """what only the lane form does, between the shared steps: stage the lane's next batch and build the PREVIOUS one's dicts (idle)"""
@@ -985,6 +1020,8 @@ class FaceService:
     def _fetch(self, eng, frames, plan: "_Plan"):
         """-> (the results of the queued pass - waits for it -, the quality list of its faces while the frames are still resident, or None)"""
         out = eng.fetch_results()
+        if plan.streams is not None:
+            out.update(eng.fetch_tracks())
         return out, (self._stream_quality(eng, frames, out) if plan.quality else None)
 
     def _blocking_pass(self, eng, frames, plan: "_Plan"):
@@ -992,9 +1029,11 @@ class FaceService:
         if isinstance(frames, _SOURCE_BATCHES):
             frames = frames.decode()                                   # an engine without the device decoder / converter (tests' FakeEngine)
         kw = dict(max_faces=plan.max_faces, det_thresh=plan.det_thresh, nms_iou=NMS_IOU, flags=plan.flags)
-        with (self._sequence_of(eng) if plan.quality else contextlib.nullcontext()):
+        with (self._sequence_of(eng) if plan.quality or plan.streams is not None else contextlib.nullcontext()):
             if plan.scales is None:
                 out = eng.process_frames(frames, **kw)
+                if plan.streams is not None:
+                    out.update(eng.fetch_tracks())
             else:
                 out = eng.process_frames_pyramid(frames, scales=plan.scales, per_scale=PYRAMID_PER_SCALE, on_device=True, **kw)
             return out, (self._stream_quality(eng, frames, out) if plan.quality else None)
@@ -1031,17 +1070,22 @@ class FaceService:
 
     def process_stream(self, batches, max_faces: int = 10, threshold: Optional[float] = None,
                        det_thresh: Optional[float] = None, all_matches: bool = False, quality: bool = False,
-                       det_scales: Optional[Sequence[float]] = None, groups=None):
+                       det_scales: Optional[Sequence[float]] = None, groups=None, streams=None):
         """process_frames for a stream of batches with TWO batches in flight on the GPU (lanes.py: a second handle and
         host thread; +7...13 % faces/s).  Yields one process_frames result per batch, in order.  Enrolment and deletion
         may run concurrently: they wait for the batches inside their device call and reach both gallery copies under
         the same lock, so every result is the one process_frames would have given for SOME gallery state between the
         batch's submission and its delivery.  Falls back to one lane when the second one cannot join (see _eng2).
-        groups: as process_frames, for every batch - or a callable batch -> masks (mixer.run_mixed: the streams of each batch)."""
+        groups: as process_frames, for every batch - or a callable batch -> masks (mixer.run_mixed: the streams of each batch).
+        streams: as process_frames, for every batch - or a callable batch -> streams (mixer.run_mixed(track=True)).  A tracked stream runs
+        on ONE lane only: the track state lives in a handle, and alternate batches on a second handle would each see every other
+        frame of a camera - every track would age twice as fast and neither handle could reuse what the other embedded."""
         engines = [self._eng()]
-        e2 = self._eng2()
+        e2 = self._eng2() if streams is None else None
         if e2 is not None:
             engines.append(e2)
+        if streams is not None and not engine_caps(engines[0]).track:
+            raise ValueError("streams needs an engine with face tracks (track_config)")
         for e in engines:
             _check_det_scales(engine_caps(e), det_scales)  # (here, not at the first batch)
 
@@ -1049,7 +1093,8 @@ class FaceService:
             def run(frames, take_next=None, staged=None):
                 return self._process_frames_on(eng, self.ENCODINGS.reading(), frames, max_faces, threshold, det_thresh, all_matches,
                                                take_next, staged, quality=quality, det_scales=det_scales,
-                                               groups=groups(frames) if callable(groups) else groups)
+                                               groups=groups(frames) if callable(groups) else groups,
+                                               streams=streams(frames) if callable(streams) else streams)
             if not engine_caps(eng).lane:
                 return lambda frames, take_next: run(frames)
             staged = {}                         # which batch sits in this lane's staging buffer
@@ -1059,6 +1104,32 @@ class FaceService:
                     return run(frames, take_next, staged)
             return fn
         return lanes.run_ordered(batches, [on(e) for e in engines], prefetch=True)
+
+    # ------------------------------------------------------------------ face tracks (process_frames / process_stream with streams=)
+    def _track_engine(self):
+        eng = self._eng()
+        if not engine_caps(eng).track:
+            raise ValueError("face tracks need an engine with track_config")
+        return eng
+
+    def configure_tracks(self, max_streams: int, iou_min: float = tracks.DEFAULT_IOU_MIN, refresh: int = tracks.DEFAULT_REFRESH,
+                         max_missed: int = tracks.DEFAULT_MAX_MISSED) -> None:
+        """face tracks for the passes that get streams=: up to max_streams (1..64) cameras; a detection continues a track when its IoU with
+        the track's last box is at least iou_min, a track is embedded again every `refresh` frames and dropped after max_missed frames
+        without a detection (tracks.TrackModel; the defaults are ordinary ones, not measured optima).  Clears every track.
+        max_streams = 0 turns tracking off and frees its device memory.  The first lane's handle only: see process_stream."""
+        if max_streams:
+            tracks.check_config(iou_min, refresh, max_missed, max_streams)
+        self._track_engine().track_config(max_streams, iou_min, refresh, max_missed)
+
+    def reset_tracks(self, stream: Optional[int] = None) -> None:
+        """forget the tracks of one stream (a camera that reconnected), None: of all"""
+        self._track_engine().track_reset(-1 if stream is None else int(stream))
+
+    def track_statistics(self) -> Dict[str, int]:
+        """faces embedded and faces that reused their track's result, over the tracked passes since configure_tracks"""
+        embedded, reused = self._track_engine().track_stats()
+        return {"embedded": embedded, "reused": reused}
 
     def frame_buffer(self, batch: int, height: int, width: int) -> np.ndarray:
         """A page-locked u8 [batch, height, width, 3] array (owned by the engine, freed with it) for the capture / decode

@@ -220,21 +220,36 @@ def frame_groups(meta: List[Optional[Tuple[Any, int]]], groups_of_stream) -> Lis
     return [0 if m is None else int(look(m[0])) for m in meta]
 
 
-def run_mixed(service, mixer: StreamMixer, groups_of_stream=None, **kw) -> Iterator[Dict[Any, List[Tuple[int, Any]]]]:
+def frame_streams(meta: List[Optional[Tuple[Any, int]]], order: Sequence[Any]) -> List[int]:
+    """one track stream per slot of a mixed batch (FaceService.process_frames(streams=)): the dense index of the slot's stream in
+    `order` (StreamMixer.order) and -1, which is not tracked, for a slot left empty"""
+    index = {sid: i for i, sid in enumerate(order)}
+    return [-1 if m is None else index[m[0]] for m in meta]
+
+
+def run_mixed(service, mixer: StreamMixer, groups_of_stream=None, track: bool = False, **kw) -> Iterator[Dict[Any, List[Tuple[int, Any]]]]:
     """mixer -> FaceService.process_stream (two batches in flight) -> per batch {stream id: [(frame index, faces), ...]}.
     groups_of_stream ("camera 3 looks for list A, camera 7 for lists A and C"): every frame is matched against the identities its
-    stream's mask permits (frame_groups above), in the same one pass per batch."""
+    stream's mask permits (frame_groups above), in the same one pass per batch.
+    track: the faces are tracked per stream (frame_streams above; FaceService.configure_tracks first) - a face identified a frame
+    ago is not embedded again; process_stream then runs on one lane.  Not together with groups_of_stream."""
     import collections
+    if track and groups_of_stream is not None:
+        raise ValueError("run_mixed: track does not combine with groups_of_stream")
     metas = collections.deque()
-    masks = {}                              # id(batch) -> its frames' masks, from the batch's hand-over to its pass
+    masks = {}                              # id(batch) -> its frames' masks / streams, from the batch's hand-over to its pass
 
     def batches():
         for buf, meta in mixer:
             metas.append(meta)
             if groups_of_stream is not None:
                 masks[id(buf)] = frame_groups(meta, groups_of_stream)
+            elif track:
+                masks[id(buf)] = frame_streams(meta, mixer.order)
             yield buf
     if groups_of_stream is not None:
         kw = dict(kw, groups=lambda batch: masks.pop(id(batch)))
+    elif track:
+        kw = dict(kw, streams=lambda batch: masks.pop(id(batch)))
     for res in service.process_stream(batches(), **kw):
         yield demix(metas.popleft(), res)

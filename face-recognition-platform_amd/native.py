@@ -24,7 +24,7 @@ EMB_DIM = 512
 CHIP = 112
 MAX_FACES_CAP = 128
 MAX_TOPK = 64
-FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN, FLAG_GROUPS = 1, 2, 4, 8, 16
+FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN, FLAG_GROUPS, FLAG_TRACK = 1, 2, 4, 8, 16, 32
 GROUPS_ALL = 0xFFFFFFFF                      # include/frp.h: FRP_GROUPS_ALL - the mask of a gallery row that arrived without one
 F32, F16, F64 = 0, 1, 2
 JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}      # include/frp.h: FRP_JPEG_420, FRP_JPEG_444
@@ -44,7 +44,9 @@ ABI_SYMBOLS = [
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_debug_fc_l2norm", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
-    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_match_groups", "frp_match_within_groups", "frp_set_frame_groups", "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_match_groups", "frp_match_within_groups", "frp_set_frame_groups",
+    "frp_track_config", "frp_set_frame_streams", "frp_track_reset", "frp_fetch_tracks", "frp_track_stats", "frp_debug_track_step",
+    "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -255,6 +257,13 @@ def load_library() -> C.CDLL:
         lib.frp_set_frame_groups.argtypes = [vp, vp, i32]
         lib.frp_match_groups.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.frp_match_within_groups.argtypes = [vp, vp, i32, vp, f32, i32, vp, vp, vp]
+    if hasattr(lib, "frp_track_config"):     # (as above)
+        lib.frp_track_config.argtypes = [vp, i32, f32, i32, i32]
+        lib.frp_set_frame_streams.argtypes = [vp, vp, i32]
+        lib.frp_track_reset.argtypes = [vp, i32]
+        lib.frp_fetch_tracks.argtypes = [vp, i32, i32, vp, vp, vp]
+        lib.frp_track_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+        lib.frp_debug_track_step.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp, vp, vp]
     if hasattr(lib, "frp_face_quality"):     # (as above: an older A/B partner build has none)
         lib.frp_face_quality.argtypes = [vp, vp, i32, u32, vp]
     if hasattr(lib, "frp_encode_jpeg"):      # (as above)
@@ -310,6 +319,7 @@ class Engine:
         self._pass = (0, 0)              # (B, K) of the last pass that embeds faces: what fetch_results / fetch_within are sized for
         self._det_batch = 0              # frames of the detector run head_maps() reads back
         self._within_cap = 0             # set_within
+        self._track_pass = (0, 0)        # (B, K) of the last pass with FLAG_TRACK (or track_step): what fetch_tracks is sized for
         self._yuv_keep = ()              # host planes of the last two upload_yuv_async batches
 
     _h = None                            # (an object whose __init__ raised is still closed by __del__)
@@ -338,11 +348,13 @@ class Engine:
         """(B, H, W) of the resident frames; zeros before the first batch"""
         return self._resident
 
-    def _began(self, B: int, K: Optional[int] = None, heads: bool = False):
+    def _began(self, B: int, K: Optional[int] = None, heads: bool = False, flags: int = 0):
         """a pass over B frames has been taken by the library.  K: it embeds up to K faces per frame - the (B, K) fetch_results and
         fetch_within size their buffers for; heads: a detector run whose head maps head_maps() reads back, B frames of them"""
         if K is not None:
             self._pass = (B, K)
+            if flags & FLAG_TRACK:
+                self._track_pass = (B, K)
         if heads:
             self._det_batch = B
 
@@ -550,6 +562,56 @@ class Engine:
         m = np.ascontiguousarray(np.asarray(masks, dtype=np.uint32)).reshape(-1)
         self._chk(self._lib.frp_set_frame_groups(self._h, _ptr(m), m.shape[0]))
 
+    # -- face tracks (include/frp.h: frp_track_config; the semantics: tracks.TrackModel)
+    def track_config(self, max_streams: int, iou_min: float = 0.3, refresh: int = 8, max_missed: int = 2):
+        """tracking for the passes that run with FLAG_TRACK from now on: allocates the per-stream tables, clears every track, marks the
+        next pass stale; max_streams = 0 releases everything.  (0.3 / 8 / 2 are ordinary defaults, not measured optima.)"""
+        self._chk(self._lib.frp_track_config(self._h, int(max_streams), float(iou_min), int(refresh), int(max_missed)))
+
+    def set_frame_streams(self, streams):
+        """the stream of every frame, in [-1, max_streams), for the passes that run with FLAG_TRACK from now on (-1: the frame is not
+        tracked: every face embedded, track_id -1)"""
+        s = np.ascontiguousarray(np.asarray(streams, dtype=np.int32)).reshape(-1)
+        self._chk(self._lib.frp_set_frame_streams(self._h, _ptr(s), s.shape[0]))
+
+    def track_reset(self, stream: int = -1):
+        """forget the tracks of one stream (a camera reconnect), -1: of all"""
+        self._chk(self._lib.frp_track_reset(self._h, int(stream)))
+
+    def fetch_tracks(self) -> dict:
+        """track_id, reused, age [B, K] of the last pass that ran with FLAG_TRACK (slots without a face: -1 / 0 / 0)"""
+        B, K = self._track_pass
+        o = dict(track_id=np.full((B, K), -1, np.int32), reused=np.zeros((B, K), np.int32), age=np.zeros((B, K), np.int32))
+        self._chk(self._lib.frp_fetch_tracks(self._h, B, K, _ptr(o["track_id"]), _ptr(o["reused"]), _ptr(o["age"])))
+        return o
+
+    def track_stats(self) -> Tuple[int, int]:
+        """(faces embedded, faces reused) by the tracked passes since track_config"""
+        e, r = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.frp_track_stats(self._h, C.byref(e), C.byref(r)))
+        return int(e.value), int(r.value)
+
+    def track_step(self, streams, boxes, counts, K: int, emb, idx, cos) -> dict:
+        """the tracker's launches alone on host detections (frp.h: frp_debug_track_step; tracks.TrackModel.step's arguments and
+        return value): needs no weights, advances the handle's track state"""
+        streams = np.ascontiguousarray(np.asarray(streams, np.int32)).reshape(-1)
+        B, K = streams.shape[0], int(K)
+        boxes = np.ascontiguousarray(boxes, np.float32).reshape(B, K, 4)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(B)
+        emb = np.ascontiguousarray(emb, np.float32).reshape(B, K, EMB_DIM)
+        idx = np.ascontiguousarray(idx, np.int32).reshape(B, K)
+        cos = np.ascontiguousarray(cos, np.float32).reshape(B, K)
+        o = dict(track_id=np.zeros((B, K), np.int32), reused=np.zeros((B, K), np.int32), age=np.zeros((B, K), np.int32),
+                 face_slot=np.zeros((B * K,), np.int32), emb=np.zeros((B, K, EMB_DIM), np.float32), idx=np.zeros((B, K), np.int32),
+                 cos=np.zeros((B, K), np.float32))
+        n = C.c_int32(0)
+        self._chk(self._lib.frp_debug_track_step(self._h, _ptr(streams), _ptr(boxes), _ptr(counts), B, K, _ptr(emb), _ptr(idx), _ptr(cos),
+                                                 _ptr(o["track_id"]), _ptr(o["reused"]), _ptr(o["age"]), _ptr(o["face_slot"]), C.byref(n),
+                                                 _ptr(o["emb"]), _ptr(o["idx"]), _ptr(o["cos"])))
+        o["n_embed"] = int(n.value)
+        self._track_pass = (B, K)
+        return o
+
     # -- hot path
     @staticmethod
     def _frames(frames: np.ndarray) -> Tuple[np.ndarray, int, int, int, int]:
@@ -581,7 +643,7 @@ class Engine:
         self._chk(self._lib.frp_process_frames(self._h, _ptr(frames), B, H, W, rs, max_faces, det_thresh, nms_iou, flags,
                                                _ptr(o["boxes"]), _ptr(o["kps"]), _ptr(o["scores"]), _ptr(o["counts"]),
                                                _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
-        self._began(B, max_faces, heads=True)
+        self._began(B, max_faces, heads=True, flags=flags)
         return o
 
     def upload_frames(self, frames: np.ndarray):
@@ -645,7 +707,7 @@ class Engine:
 
     def process_resident(self, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4, flags: int = 0):
         self._chk(self._lib.frp_process_resident(self._h, max_faces, det_thresh, nms_iou, flags))
-        self._began(self._resident[0], max_faces)
+        self._began(self._resident[0], max_faces, flags=flags)
 
     def synchronize(self):
         self._chk(self._lib.frp_synchronize(self._h))
@@ -694,7 +756,7 @@ class Engine:
         self._chk(self._lib.frp_finish_faces(self._h, B, _ptr(boxes), _ptr(kps), _ptr(scores), _ptr(counts), max_faces, flags,
                                              _ptr(o["emb"]), _ptr(o["match_idx"]), _ptr(o["match_cos"])))
         o.update(boxes=boxes, kps=kps, scores=scores, counts=counts)
-        self._began(B, max_faces)
+        self._began(B, max_faces, flags=flags)
         return o
 
     def process_pyramid_resident(self, det_hws, per_scale: int = 64, max_faces: int = 10, det_thresh: float = 0.5, nms_iou: float = 0.4,

@@ -56,6 +56,8 @@ typedef enum frp_dtype { FRP_F32 = 0, FRP_F16 = 1, FRP_F64 = 2 } frp_dtype;
                                   frp_set_within, from the same gallery pass (frp_fetch_within; the caller's filter loop over every
                                   target, camera.py:246-256) */
 #define FRP_FLAG_GROUPS 16u    /* the pass matches every face against the rows its FRAME's mask permits (frp_set_frame_groups) */
+#define FRP_FLAG_TRACK 32u     /* face tracks: a detection that continues a track identified before gets the track's cached embedding
+                                  and match, only the others are embedded (frp_track_config, frp_set_frame_streams) */
 #define FRP_GROUPS_ALL 0xFFFFFFFFu   /* member of every group: the mask of a row that arrived without one */
 
 typedef struct frp_handle frp_handle;
@@ -215,6 +217,55 @@ int frp_set_within(frp_handle* h, float min_cos, int32_t cap);
  * FRP_FLAG_NO_MATCH.  frp_counters.match_bytes of a grouped launch counts N * (1024 + 4). */
 int frp_set_frame_groups(frp_handle* h, const uint32_t* masks, int32_t B);
 int frp_fetch_within(frp_handle* h, int32_t B, int32_t max_faces, int32_t cap, int32_t* idx, float* cos, int32_t* n_hits);
+
+/* Face tracks (FRP_FLAG_TRACK of frp_process_frames / frp_process_resident / frp_finish_faces): the workload is video, a stream's
+ * consecutive frames show the same faces in almost the same place, and the embedder is the dominant cost of a step - so a flagged
+ * pass decides ON THE DEVICE which detections continue a face identified before, embeds only the others (the embed list and its
+ * count stay in device memory, as in every threshold pass) and gives the rest the bits their track cached.
+ * State per stream: next_id and an ordered list of at most FRP_TRACK_SLOTS = 128 entries {box, id, age (frames of the stream since the
+ * embedding the entry carries was computed), missed, match_idx, match_cos, emb[512]}.  One frame of stream s (a stream's frames are
+ * taken in batch order), detections j = 0 .. n-1 in detector order, n = clamp(counts[b], 0, max_faces):
+ *   1. j ascending, over the entries no earlier j claimed: IoU as the NMS kernels compute it (+1-pixel areas, fp32, one rounding
+ *      per operation, inter / ((a + b) - inter)); candidates have iou >= iou_min (a NaN fails); the largest IoU wins, a tie goes to
+ *      the lowest entry.  Matched: the detection inherits the id, a = age + 1; a < refresh and the pass not stale: REUSED - it carries
+ *      the entry's emb / match_idx / match_cos, age = a; otherwise embedded, age 0.  Unmatched: id = next_id++, embedded, age 0.
+ *   2. the new list: the n detections in order (missed 0), then the unclaimed entries in their old order with missed + 1 and
+ *      age + 1 while missed <= max_missed, cut at 128.
+ * A frame of stream -1 embeds every detection, reports track_id -1 and touches no state; streams absent from a batch keep theirs.
+ * The source of a reused slot is an entry of the state before the pass or a face embedded EARLIER IN THE SAME BATCH (frame 2 of a
+ * stream reusing what frame 1 computes), resolved behind the matcher.  frp_fetch_results then gives every live slot its emb / idx /
+ * cos: embedded slots their own, reused slots the bits of their source.
+ * `stale`: set by frp_track_config, by every gallery mutation (set, set_device, commit, update_row, remove_row, allgather,
+ * set_groups) and by frp_gallery_exact; the next flagged pass then embeds every face (ids continue) and clears it - a cached
+ * match_idx never outlives a row move.
+ * Passes without the flag are unchanged whether or not tracking is configured, and leave the track state alone.
+ * frp_counters.faces and the embedder's FLOP count keep meaning EMBEDDED faces; frp_track_stats has both totals.
+ * Refused with FRP_ERR_INVALID before anything is launched, overwritten or advanced: the flag without frp_track_config, without
+ * frp_set_frame_streams for the pass's B, together with FRP_FLAG_WITHIN or FRP_FLAG_GROUPS, passed to frp_process_pyramid, or to
+ * frp_finish_faces without boxes.  Grouped / within passes and the pyramid pass under tracking are follow-ups.
+ *
+ * frp_track_config: iou_min in (0, 1], refresh >= 1, max_missed >= 0, max_streams 1..64: allocates the tables, clears every track,
+ * sets stale.  max_streams = 0 releases everything and turns tracking off.  (Callers' usual values 0.3 / 8 / 2 are ordinary
+ * defaults, not measured optima.) */
+#define FRP_TRACK_MAX_STREAMS 64
+int frp_track_config(frp_handle* h, int32_t max_streams, float iou_min, int32_t refresh, int32_t max_missed);
+/* the stream of every frame, entries in [-1, max_streams), for the flagged passes that follow (life cycle of frp_set_frame_groups) */
+int frp_set_frame_streams(frp_handle* h, const int32_t* stream_of_frame, int32_t B);
+/* forget the tracks of one stream (a camera reconnect), -1: of all; ids start at 0 again */
+int frp_track_reset(frp_handle* h, int32_t stream);
+/* [B x max_faces] of the last flagged pass: track id (-1: untracked frame or no face), 1 where the result was reused, age; the
+   shape check of frp_fetch_results */
+int frp_fetch_tracks(frp_handle* h, int32_t B, int32_t max_faces, int32_t* track_id, int32_t* reused, int32_t* age);
+/* faces embedded / reused by flagged passes since the last frp_track_config (device totals: waits for the stream) */
+int frp_track_stats(frp_handle* h, int64_t* embedded, int64_t* reused);
+/* the real associate / compact / resolve / store launches on host detections (parity tests; needs no weights, advances the handle's
+   track state, honours and clears stale): streams [B], boxes [B][K][4], counts [B]; emb_in [B][K][512], idx_in, cos_in [B][K] stand in
+   for what the embedder and matcher would produce for the slots that turn out embedded (compacted here in face_slot order).
+   Out: track_id, reused, age [B][K]; face_slot [B x K] (-1 behind n_embed); emb [B][K][512], idx, cos [B][K]; slots beyond the
+   counts are zero / -1 */
+int frp_debug_track_step(frp_handle* h, const int32_t* streams, const float* boxes, const int32_t* counts, int32_t B, int32_t K,
+                         const float* emb_in, const int32_t* idx_in, const float* cos_in, int32_t* track_id, int32_t* reused,
+                         int32_t* age, int32_t* face_slot, int32_t* n_embed, float* emb, int32_t* idx, float* cos);
 
 /* Overlapped ingest for streaming callers (the camera loop keeps producing frames while the previous
  * batch is on the GPU, camera.py:277-305): the NEXT batch is copied host -> device on a private copy

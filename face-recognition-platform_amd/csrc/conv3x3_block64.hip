@@ -69,11 +69,7 @@ template <int ACT1, bool BORDER1, int ACT2>
 __global__ __launch_bounds__(512, 2) void conv3x3_block64_kernel(Block64Params p_in) {
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     Block64Params p = p_in;
-    int N = p.N;
-    if (p.n_dev) {                             // image count known on the device only (threshold mode)
-        const int n = *p.n_dev;
-        N = n < 0 ? 0 : (n > p.N ? p.N : n);
-    }
+    const int N = p.n_dev ? conv_image_count(*p.n_dev, p.N) : p.N;      // image count known on the device only (threshold mode)
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -84,8 +80,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_block64_kernel(Block64Params p
     const int H = p.H, W = p.W;
 
     const unsigned io_bytes = (unsigned)((long)p.N * H * W * 128);                    // (< 2 GiB: launcher)
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, io_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, io_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, io_bytes);
+    const __amdgpu_buffer_rsrc_t orsrc = conv_rsrc(p.out, io_bytes);
 
     // ---------------- epilogue parameters: conv1 bias [9][64] (class-major) and slope, conv2 bias and slope
     float* lds_bias1 = reinterpret_cast<float*>(smem + B64_OFF_PAR);

@@ -70,35 +70,21 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(ConvParams p_in) {
     static_assert(C64_CW * C64_CH <= 512 && C64_NBLK <= 16 && C64_OFF_SPAR + 512 <= C64_OFF_PAR && !(STEM && RES), "stem fusion");
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     ConvParams p = p_in;
-    int N = p.N;
-    if (p.n_dev) {                             // image count known on the device only (threshold mode)
-        const int n = *p.n_dev;
-        N = n < 0 ? 0 : (n > p.N ? p.N : n);
-    }
+    const int N = p.n_dev ? conv_image_count(*p.n_dev, p.N) : p.N;      // image count known on the device only (threshold mode)
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int tx_n = (p.W + C64_TW - 1) / C64_TW, ty_n = (p.H + C64_TH - 1) / C64_TH;
     const int per = tx_n * ty_n;
     const int n_tiles = N * per;
-    int t0, t1, tstep;
-    if ((gridDim.x & 7) == 0) {                // XCD-interleaved tile walk (see conv3x3_lean.hip)
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, pr = gridDim.x >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = pr;
-    } else {
-        t0 = (int)((long)blockIdx.x * n_tiles / gridDim.x);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / gridDim.x);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, (int)gridDim.x, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, p.x_bytes);
     const unsigned o_bytes = (unsigned)((long)p.N * p.H * p.W * 64 * 2);             // (< 2 GiB: launcher)
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, o_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.res ? p.res : p.x), 0, p.res ? o_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t orsrc = conv_rsrc(p.out, o_bytes);
+    const __amdgpu_buffer_rsrc_t rrsrc = conv_rsrc(p.res ? (const void*)p.res : p.x, p.res ? o_bytes : 0u);
 
     // ---------------- epilogue parameters, once per workgroup (one cout tile): bias [9][64] (class-major), PReLU slope [64]
     float* lds_bias = reinterpret_cast<float*>(smem + C64_OFF_PAR);
@@ -179,8 +165,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(ConvParams p_in) {
 
     // ---------------- STEM: the chips under a tile's patch, one LDS-DMA piece per wave: slot pixel 64 wave + lane = (cy, cx) of the
     // (TH + 4) x (TW + 4) block whose origin lies two pixels up and left of the tile; outside the chip: zeros (the stem's padding)
-    const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(STEM ? p.stem_x : p.x), 0, STEM ? (unsigned)((long)p.N * p.H * p.W * 16) : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(STEM ? (void*)p.stem_out : p.out, 0, STEM ? o_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t crsrc = conv_rsrc(STEM ? (const void*)p.stem_x : p.x, STEM ? (unsigned)((long)p.N * p.H * p.W * 16) : 0u);
+    const __amdgpu_buffer_rsrc_t srsrc = conv_rsrc(STEM ? (const void*)p.stem_out : p.out, STEM ? o_bytes : 0u);
     auto issue_chips = [&](int tile, int cslot) {
         const Patch q = patch_of(tile);                          // (y0, x0: the patch origin = tile origin - 1)
         const int sl = wave * 64 + lane_e;

@@ -24,11 +24,6 @@
 
 namespace frp {
 
-// one LDS-DMA piece with a scalar byte offset added to the source address (not part of the range check)
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_base, unsigned voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
-}
-
 // F8 (BASELINE config 5, "fp8 ArcFace weights (CDNA4 fp8 MFMA)"): activations and weights are OCP FP8 E4M3 bytes, the
 // matrix instruction is the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales.  A 128-byte LDS row is
 // then 128 channels, a k-step one tap x 128 channels = 2 MFMAs of K = 64 per 32x32 block: the same DMA pieces, LDS reads
@@ -55,9 +50,7 @@ __global__ __launch_bounds__(512, TP == 128 ? 4 : 2) void conv3x3_lean_kernel(Co
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     ConvParams p = p_in;
     if (p.n_dev) {                             // image count known on the device only (threshold mode)
-        int n = *p.n_dev;
-        n = n < 0 ? 0 : (n > p.N ? p.N : n);
-        p.M = n * p.Ho * p.Wo;
+        p.M = conv_image_count(*p.n_dev, p.N) * p.Ho * p.Wo;
         p.n_ptiles = (p.M + TP - 1) / TP;
     }
     constexpr int NW = 8;
@@ -84,26 +77,15 @@ __global__ __launch_bounds__(512, TP == 128 ? 4 : 2) void conv3x3_lean_kernel(Co
     if constexpr (TP == 128) {
         if ((int)blockIdx.x >= G) { conv_prefetch_weights(p, (int)blockIdx.x - G, (int)gridDim.x - G, 512); return; }
     }
-    // XCD-interleaved tile walk (see conv3x3_rows.hip)
-    int t0, t1, tstep;
-    if ((G & 7) == 0) {
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, per = G >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = per;
-    } else {
-        t0 = (int)((long)blockIdx.x * n_tiles / G);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / G);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, G, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
     constexpr int ES = F8 ? 1 : 2;             // bytes per element
     const int cpt = (p.Cin * ES) >> 7;         // channel blocks of one 128-byte LDS row (64 fp16 / 128 fp8 channels)
     const int cin2 = p.Cin * ES;               // bytes per pixel = bytes per tap in a weight row
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = conv_rsrc(p.w, p.w_bytes);
 
     // ---------------- DMA lane geometry (as conv3x3_rows.hip): a piece fills 8 LDS rows x 128 B; lane -> row lane/8,
     // chunk position lane%8 holding logical chunk pos ^ ((row>>1)&7) (source-side swizzle)
@@ -220,34 +202,15 @@ __global__ __launch_bounds__(512, TP == 128 ? 4 : 2) void conv3x3_lean_kernel(Co
             for (int j = 0; j < MC; ++j) asm volatile("" : "+v"(acc[i][j]));
     };
 
-    // ---------------- per-tile epilogue parameters in LDS (see conv_mfma.hip)
+    // ---------------- per-tile epilogue parameters in LDS (EpiParamCache, conv_common.h; its steps are called through lambdas:
+    // called from the k-loop directly the compiler hoists their loads and the kernels spill more scalar registers)
     float* lds_bias = reinterpret_cast<float*>(smem + OFF_PAR);            // [9][TC]
     float* lds_slope = lds_bias + 9 * TC;                                   // [TC]
     float* lds_wscale = lds_slope + TC;                                     // [TC] (fp8: weight scale x input scale)
-    constexpr int PPT = (9 * TC + NW * 64 - 1) / (NW * 64);
-    float pb[PPT], ps = 0.f, pw = 0.f;
+    EpiParamCache<TC, NW * 64, F8> par;
     const bool border = p.flags & FRP_FLAG_BORDER_BIAS;
-    auto fetch_params = [&](int tile) {
-        const int c0p = (tile % p.n_ctiles) * TC;
-        const int nb = (border ? 9 : 1) * TC;
-#pragma unroll
-        for (int q = 0; q < PPT; ++q) {
-            const int idx = t + q * NW * 64;
-            const int cls = idx / TC, co = c0p + (idx - cls * TC);
-            pb[q] = (idx < nb && co < p.Cout) ? p.bias[(long)cls * p.Cout + co] : 0.f;
-        }
-        if (p.act == FRP_ACT_PRELU && t < TC) ps = (c0p + t < p.Cout) ? p.slope[c0p + t] : 0.f;
-        if (F8 && t < TC) pw = (c0p + t < p.Cout) ? p.wscale[c0p + t] * p.in_scale : 0.f;
-    };
-    auto store_params = [&]() {
-#pragma unroll
-        for (int q = 0; q < PPT; ++q) {
-            const int idx = t + q * NW * 64;
-            if (idx < 9 * TC) lds_bias[idx] = pb[q];
-        }
-        if (t < TC) lds_slope[t] = ps;
-        if (F8 && t < TC) lds_wscale[t] = pw;
-    };
+    auto fetch_params = [&](int tile) { par.fetch(p, (tile % p.n_ctiles) * TC, t, border); };
+    auto store_params = [&]() { par.store(lds_bias, lds_slope, lds_wscale, t); };
 
     // ---------------- prologue: zero block; row patches (0,0), (0,1) and weight stages tap 0, 1 of the first tile
     stamp(p.stamps, 0);
@@ -310,6 +273,9 @@ __global__ __launch_bounds__(512, TP == 128 ? 4 : 2) void conv3x3_lean_kernel(Co
                 int n, rem, oy, ox;
                 fast_divmod(m, HoWo, inv_howo, n, rem);
                 fast_divmod(rem, p.Wo, inv_wo, oy, ox);
+                // conv_tap_mask_s1 (conv_common.h), kept as this kernel's own copy: through the function - in every spelling
+                // tried - the two variants with one pixel block per wave (TP = 128; TC = 64 at TP = 256) spill 4 and 2 more
+                // scalar registers (tests/test_kernel_resources_host.py); tests/test_conv_frame_host.py holds the function, not this copy
                 const unsigned ym = (oy > 0 ? 1u : 0u) | 2u | (oy < p.H - 1 ? 4u : 0u);
                 const unsigned xm = (ox > 0 ? 1u : 0u) | 2u | (ox < p.W - 1 ? 4u : 0u);
 #pragma unroll

@@ -58,28 +58,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(ConvParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
 
     const int n_tiles = p.n_ptiles * p.n_ctiles;
-    // Tile walk.  Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  XCD x takes the
-    // contiguous chunk [x*T/8, (x+1)*T/8) of the tile list and its G/8 workgroups walk it INTERLEAVED (workgroup
-    // j: chunk + j, + j + G/8, ...): at any moment the workgroups of one L2 work on G/8 consecutive tiles, i.e. on
-    // a band of neighbouring image rows whose kh = 0/1/2 row patches (and both cout tiles of a pixel tile) are the
-    // same lines - fetched once per L2 instead of once per workgroup several tiles apart.
-    int t0, t1, tstep;
-    if ((gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, per = gridDim.x >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = per;
-    } else {                                        // small grids (fewer tiles than CUs): contiguous ranges
-        t0 = (int)((long)blockIdx.x * n_tiles / gridDim.x);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / gridDim.x);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, (int)gridDim.x, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
     const int cpt = p.Cin >> 6;                // 64-channel blocks
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = conv_rsrc(p.w, p.w_bytes);
 
     // ---------------- DMA lane geometry.  A piece fills 8 LDS rows x 128 B; lane -> row lane/8, chunk
     // position lane%8, which must hold logical chunk pos ^ ((row>>1)&7) (source-side swizzle).
@@ -233,31 +218,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(ConvParams p) {
         }
     }
 
-    // ---------------- per-tile epilogue parameters in LDS (see conv_mfma.hip)
+    // ---------------- per-tile epilogue parameters in LDS (EpiParamCache, conv_common.h; through lambdas as in conv3x3_lean.hip)
     float* lds_bias = reinterpret_cast<float*>(smem + OFF_PAR);            // [9][TC]
     float* lds_slope = lds_bias + 9 * TC;                                   // [TC]
-    constexpr int PPT = (9 * TC + NW * 64 - 1) / (NW * 64);
-    float pb[PPT], ps = 0.f;
+    EpiParamCache<TC, NW * 64, false> par;
     const bool border = p.flags & FRP_FLAG_BORDER_BIAS;
-    auto fetch_params = [&](int tile) {
-        const int c0p = (tile % p.n_ctiles) * TC;
-        const int nb = (border ? 9 : 1) * TC;
-#pragma unroll
-        for (int q = 0; q < PPT; ++q) {
-            const int idx = t + q * NW * 64;
-            const int cls = idx / TC, co = c0p + (idx - cls * TC);
-            pb[q] = (idx < nb && co < p.Cout) ? p.bias[(long)cls * p.Cout + co] : 0.f;
-        }
-        if (p.act == FRP_ACT_PRELU && t < TC) ps = (c0p + t < p.Cout) ? p.slope[c0p + t] : 0.f;
-    };
-    auto store_params = [&]() {
-#pragma unroll
-        for (int q = 0; q < PPT; ++q) {
-            const int idx = t + q * NW * 64;
-            if (idx < 9 * TC) lds_bias[idx] = pb[q];
-        }
-        if (t < TC) lds_slope[t] = ps;
-    };
+    auto fetch_params = [&](int tile) { par.fetch(p, (tile % p.n_ctiles) * TC, t, border); };
+    auto store_params = [&]() { par.store(lds_bias, lds_slope, nullptr, t); };
 
     // ---------------- prologue: zero block, row patches 0 and 1, weight stages 0 and 1 (a tile has at
     // least 3 row steps and 9 k-steps, so they always exist)
@@ -343,10 +310,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_rows_kernel(ConvParams p) {
                 int n, rem, oy, ox;
                 fast_divmod(m, HoWo, inv_howo, n, rem);
                 fast_divmod(rem, p.Wo, inv_wo, oy, ox);
-                const unsigned ym = (oy > 0 ? 1u : 0u) | 2u | (oy < p.H - 1 ? 4u : 0u);
-                const unsigned xm = (ox > 0 ? 1u : 0u) | 2u | (ox < p.W - 1 ? 4u : 0u);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) mask |= ((ym >> d) & 1u) ? (xm << (3 * d)) : 0u;
+                mask = conv_tap_mask_s1(oy, ox, p.H, p.W);
             }
             tapmask[i] = mask;
         }

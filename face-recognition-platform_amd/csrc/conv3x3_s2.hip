@@ -49,10 +49,6 @@ namespace frp {
 #define S2_ABL 0
 #endif
 
-__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_base, unsigned voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
-}
-
 template <int ACT>
 __global__ __launch_bounds__(512, 2) void conv3x3_s2_kernel(ConvParams p_in) {
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
@@ -60,10 +56,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_kernel(ConvParams p_in) {
     // (every field the loops use is copied into a local: a modified copy of the struct lives in scratch memory)
     int N_ = p.N, M_ = p.M, n_pt = p.n_ptiles;
     if (p.n_dev) {                             // image count known on the device only (threshold mode)
-        int n = *p.n_dev;
-        n = n < 0 ? 0 : (n > p.N ? p.N : n);
-        N_ = n;
-        M_ = n * p.Ho * p.Wo;
+        N_ = conv_image_count(*p.n_dev, p.N);
+        M_ = N_ * p.Ho * p.Wo;
         n_pt = (M_ + S2_TP - 1) / S2_TP;
     }
     const int M = M_, n_ct = p.n_ctiles, pW = p.W, pH = p.H, pCin = p.Cin, pCout = p.Cout;
@@ -71,25 +65,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_kernel(ConvParams p_in) {
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n_tiles = n_pt * n_ct;
-    int t0, t1, tstep;
-    if ((gridDim.x & 7) == 0) {                // XCD-interleaved tile walk (see conv3x3_lean.hip)
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, pr = gridDim.x >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = pr;
-    } else {
-        t0 = (int)((long)blockIdx.x * n_tiles / gridDim.x);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / gridDim.x);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, (int)gridDim.x, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x2rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x), 0, p.x2 ? p.x2_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = conv_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t x2rsrc = conv_rsrc(p.x2 ? p.x2 : p.x, p.x2 ? p.x2_bytes : 0u);
     const unsigned o_bytes = (unsigned)((long)M * pCout * 2);                         // (< 2 GiB: launcher)
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, o_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t orsrc = conv_rsrc(p.out, o_bytes);
 
     float* lds_bias = reinterpret_cast<float*>(smem + S2_OFF_BIAS);
     for (int i = t; i < pCout; i += 512) lds_bias[i] = p.bias[i];

@@ -168,27 +168,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv3x3_wino_kernel(ConvParam
     constexpr int PPT_STEP = ROWP ? PPS / 2 : PPS / 6;   // ... per sub-step (super-patch: sub-steps 0..5 of a channel block; row patches:
                                                          // sub-steps 0, 1 of every kernel row)
     if (p.n_dev) {                             // image count known on the device only (threshold mode)
-        int n = *p.n_dev;
-        n = n < 0 ? 0 : (n > p.N ? p.N : n);
-        p.M = n * p.Ho * p.Wo;
+        p.M = conv_image_count(*p.n_dev, p.N) * p.Ho * p.Wo;
         p.n_ptiles = (p.M + TP - 1) / TP;
     }
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n_tiles = p.n_ptiles * p.n_ctiles;
-    int t0, t1, tstep;
-    if ((gridDim.x & 7) == 0) {                // XCD-interleaved tile walk (see conv3x3_lean.hip)
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, per = gridDim.x >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = per;
-    } else {
-        t0 = (int)((long)blockIdx.x * n_tiles / gridDim.x);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / gridDim.x);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, (int)gridDim.x, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
     const int cpt = p.Cin >> 6;                // 64-channel blocks
     const int cin2 = p.Cin * 2;                // bytes per pixel
@@ -200,8 +188,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void conv3x3_wino_kernel(ConvParam
     const int OFF_DUMP = OFF_PAR + 11 * TC * 4;
     const int npw = (HALF >> 2) / NW;          // real patch pieces per wave and channel block (<= PPS)
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = conv_rsrc(p.w, p.w_bytes);
 
     // ---------------- DMA lane geometry.  A piece fills 8 LDS rows x 128 B: lane -> row lane/8, 16-byte position lane%8,
     // which must hold logical chunk pos ^ ((row>>1)&7) (source-side swizzle; pieces start at multiples of 8 rows).
@@ -614,27 +602,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wino2_kernel(ConvParams p_in) 
     constexpr int T2H = 8, T2W = 30;
     const int t2x = T2D ? (p.W + T2W - 1) / T2W : 1, t2y = T2D ? (p.H + T2H - 1) / T2H : 1;      // tiles per image row / column
     if (!T2D && p.n_dev) {                     // image count known on the device only (threshold mode)
-        int n = *p.n_dev;
-        n = n < 0 ? 0 : (n > p.N ? p.N : n);
-        p.M = n * p.Ho * p.Wo;
+        p.M = conv_image_count(*p.n_dev, p.N) * p.Ho * p.Wo;
         p.n_ptiles = (p.M + TP - 1) / TP;
     }
     const int t = threadIdx.x;
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int n_tiles = p.n_ptiles * p.n_ctiles;
-    int t0, t1, tstep;
-    if ((gridDim.x & 7) == 0) {                // XCD-interleaved tile walk (see conv3x3_lean.hip)
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, per = gridDim.x >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = per;
-    } else {
-        t0 = (int)((long)blockIdx.x * n_tiles / gridDim.x);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / gridDim.x);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, (int)gridDim.x, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
     const int cpt = p.Cin >> 6;                // 64-channel blocks
     const int cin2 = p.Cin * 2;                // bytes per pixel

@@ -27,6 +27,15 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, 0, 0, 0);
 }
 
+// ... with a scalar byte offset added to the source address (not part of the range check)
+__device__ __forceinline__ void dma16s(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_base, unsigned voffset, int soffset) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voffset, soffset, 0, 0);
+}
+// raw buffer descriptor of `bytes` bytes at ptr (stride 0; the flags word: 32-bit data format, offsets >= bytes read as zero)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_rsrc(const void* ptr, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, bytes, 0x00020000);
+}
+
 // (device-only constructs must live in __device__ functions: written directly in the __global__
 // template body they make the HOST pass drop the kernel stub without a diagnostic)
 __device__ __forceinline__ void keep_alive(floatx16 v) { asm volatile("" ::"v"(v)); }
@@ -143,6 +152,87 @@ __device__ __forceinline__ void fast_divmod(int m, int d, float inv_d, int& q, i
     if (r < 0) { --q; r += d; }
     if (r >= d) { ++q; r -= d; }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The frame of the persistent conv kernels: which tiles a workgroup computes, how many images exist, which taps of a pixel
+// lie inside the image, and the per-tile epilogue parameters in LDS.  tests/test_conv_frame_host.py holds the first three on the host.
+
+// Tile walk of workgroup b of the G that walk a list of n_tiles tiles: t0, t0 + tstep, ... < t1 (nothing when t0 >= t1).
+// Workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share an L2).  XCD x takes the contiguous chunk
+// [x*T/8, (x+1)*T/8) of the tile list and its G/8 workgroups walk it INTERLEAVED (workgroup j: chunk + j, + j + G/8, ...): at any
+// moment the workgroups of one L2 work on G/8 consecutive tiles - a band of neighbouring image rows whose row patches are the same
+// lines, both cout tiles of a pixel tile, the k-slices of one split-K tile - fetched once per L2 instead of once per workgroup
+// several tiles apart.  Grids that are no multiple of 8 (fewer tiles than CUs) take contiguous ranges.
+struct TileWalk { int t0, t1, tstep; };
+__host__ __device__ __forceinline__ TileWalk conv_tile_walk(int n_tiles, int G, unsigned b) {
+    if ((G & 7) == 0) {
+        const int x = b & 7, j = b >> 3, per = G >> 3;
+        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
+        return {cs + j, ce, per};
+    }
+    return {(int)((long)b * n_tiles / G), (int)((long)(b + 1) * n_tiles / G), 1};
+}
+
+// Images that really exist when the count is known on the device only (threshold mode): the value read from ConvParams::n_dev,
+// held inside the capacity N the buffers and the grid were sized for.
+__host__ __device__ __forceinline__ int conv_image_count(int n_dev, int N) { return n_dev < 0 ? 0 : (n_dev > N ? N : n_dev); }
+
+// 9-bit tap mask of output pixel (oy, ox): bit kh*3+kw set <=> tap (kh, kw) of its window lies inside the H x W input
+// (KS = 1: the one tap is bit 0).  The reference form, which no kernel calls: conv_mfma.hip spells it out itself (see there); the host
+// test checks this function and conv_tap_mask_s1, not the kernels' copies.
+__host__ __device__ __forceinline__ unsigned conv_tap_mask(int oy, int ox, int H, int W, int stride, int pad, int KS) {
+    const int y0 = oy * stride - pad, x0 = ox * stride - pad;
+    unsigned ym = 0, xm = 0, mask = 0;      // 3-bit validity of y0+{0,1,2}, x0+{0,1,2}
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        ym |= ((unsigned)(y0 + d) < (unsigned)H ? 1u : 0u) << d;
+        xm |= ((unsigned)(x0 + d) < (unsigned)W ? 1u : 0u) << d;
+    }
+    if (KS == 1) { ym &= 1u; xm &= 1u; }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) mask |= ((ym >> d) & 1u) ? (xm << (3 * d)) : 0u;
+    return mask;
+}
+// ... of a 3x3 stride-1 pad-1 window (the row-patch kernels): the centre row and column always exist
+__host__ __device__ __forceinline__ unsigned conv_tap_mask_s1(int oy, int ox, int H, int W) {
+    const unsigned ym = (oy > 0 ? 1u : 0u) | 2u | (oy < H - 1 ? 4u : 0u);
+    const unsigned xm = (ox > 0 ? 1u : 0u) | 2u | (ox < W - 1 ? 4u : 0u);
+    unsigned mask = 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) mask |= ((ym >> d) & 1u) ? (xm << (3 * d)) : 0u;
+    return mask;
+}
+
+// Per-tile epilogue parameters in LDS (behind the operand rings): bias (1 or 9 border classes, class-major [9][TC]), PReLU slope
+// [TC] and - F8 - weight scale x input scale [TC] of the tile's TC couts from c0.  A kernel fetches them into registers at the
+// start of the tile's first k-step and stores them at its end, so the epilogue reads them with short LDS latencies instead of
+// serialising on global loads.  t: the thread's index among the workgroup's THREADS; border: FRP_FLAG_BORDER_BIAS of the launch.
+// (conv_mfma.hip spells the same two steps out itself: tests/test_kernel_resources_host.py, see there.)
+template <int TC, int THREADS, bool F8>
+struct EpiParamCache {
+    static constexpr int PPT = (9 * TC + THREADS - 1) / THREADS;   // bias values per thread
+    float pb[PPT], ps = 0.f, pw = 0.f;
+    __device__ __forceinline__ void fetch(const ConvParams& p, int c0, int t, bool border) {
+        const int nb = (border ? 9 : 1) * TC;
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const int idx = t + q * THREADS;
+            const int cls = idx / TC, co = c0 + (idx - cls * TC);
+            pb[q] = (idx < nb && co < p.Cout) ? p.bias[(long)cls * p.Cout + co] : 0.f;
+        }
+        if (p.act == FRP_ACT_PRELU && t < TC) ps = (c0 + t < p.Cout) ? p.slope[c0 + t] : 0.f;
+        if (F8 && t < TC) pw = (c0 + t < p.Cout) ? p.wscale[c0 + t] * p.in_scale : 0.f;
+    }
+    __device__ __forceinline__ void store(float* lds_bias, float* lds_slope, float* lds_wscale, int t) const {
+#pragma unroll
+        for (int q = 0; q < PPT; ++q) {
+            const int idx = t + q * THREADS;
+            if (idx < 9 * TC) lds_bias[idx] = pb[q];
+        }
+        if (t < TC) lds_slope[t] = ps;
+        if (F8 && t < TC) lds_wscale[t] = pw;
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // THE epilogue arithmetic of every conv / stem kernel: one lane's share of one 32-pixel x 32-cout accumulator block

@@ -46,9 +46,7 @@ __global__ __launch_bounds__(NW * 64, TP == 128 ? 4 : 2) void conv_mfma_kernel(C
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     ConvParams p = p_in;
     if (p.n_dev) {                             // image count known on the device only (threshold mode)
-        int n = *p.n_dev;
-        n = n < 0 ? 0 : (n > p.N ? p.N : n);
-        p.M = n * p.Ho * p.Wo;
+        p.M = conv_image_count(*p.n_dev, p.N) * p.Ho * p.Wo;
         p.n_ptiles = (p.M + TP - 1) / TP;
         if (p.ksplit < 0) p.ksplit = conv_pick_ksplit(p.M, p.Cout, p.Ktot, p.flags, p.res != nullptr, p.n_cu);
     }
@@ -73,32 +71,19 @@ __global__ __launch_bounds__(NW * 64, TP == 128 ? 4 : 2) void conv_mfma_kernel(C
     // (tile, k-slice) pair: slice s covers k-steps [s*nk, (s+1)*nk) and writes raw fp32 partial
     // sums to a workspace slab that a finalize kernel reduces.
     const int n_tiles = p.n_ptiles * p.n_ctiles * p.ksplit;
-    // XCD-interleaved walk (see conv3x3_rows.hip): the workgroups of one L2 (b, b+8, ...) share a contiguous
-    // chunk of the tile list and walk it interleaved, so neighbouring tiles - same input rows, both cout tiles of
-    // a pixel tile, the k-slices of one split-K tile - are in flight on the same L2 at the same time.
     const int G = (TP == 128 && p.n_workers) ? p.n_workers : (int)gridDim.x;      // workgroups that walk tiles (the others: conv_prefetch_weights)
     if constexpr (TP == 128) {
         if ((int)blockIdx.x >= G) { conv_prefetch_weights(p, (int)blockIdx.x - G, (int)gridDim.x - G, NW * 64); return; }
     }
-    int t0, t1, tstep;
-    if ((G & 7) == 0) {
-        const int x = blockIdx.x & 7, j = blockIdx.x >> 3, per = G >> 3;
-        const int cs = (int)((long)x * n_tiles / 8), ce = (int)((long)(x + 1) * n_tiles / 8);
-        t0 = cs + j;
-        t1 = ce;
-        tstep = per;
-    } else {
-        t0 = (int)((long)blockIdx.x * n_tiles / G);
-        t1 = (int)((long)(blockIdx.x + 1) * n_tiles / G);
-        tstep = 1;
-    }
+    const TileWalk tw = conv_tile_walk(n_tiles, G, blockIdx.x);      // XCD-interleaved (conv_common.h)
+    const int t0 = tw.t0, t1 = tw.t1, tstep = tw.tstep;
     if (t0 >= t1) return;
     const int nk = p.nk / p.ksplit;            // k-steps per (tile, slice); launch_conv makes it exact
 
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrsrc = conv_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wrsrc = conv_rsrc(p.w, p.w_bytes);
     // K-concat: after the 9 * cpt (tap, channel block) stages of a tile come cpt2 stages of tensor x2 at the centre tap
-    const __amdgpu_buffer_rsrc_t x2rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x), 0, p.x2 ? p.x2_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x2rsrc = conv_rsrc(p.x2 ? p.x2 : p.x, p.x2 ? p.x2_bytes : 0u);
 
     // ---------------- DMA lane state of the ISSUE cursor (it runs PRE stages ahead of the MFMAs
     // and crosses into the next tile while the current one is still being multiplied).
@@ -133,6 +118,9 @@ __global__ __launch_bounds__(NW * 64, TP == 128 ? 4 : 2) void conv_mfma_kernel(C
                 fast_divmod(rem, p.Wo, inv_wo, oy, ox);
                 const int y0 = oy * p.stride - p.pad, x0 = ox * p.stride - p.pad;
                 off = (((n * p.H + y0) * p.W + x0) * p.Cin) * 2;
+                // conv_tap_mask (conv_common.h), kept as this kernel's own copy: through the function the 256 x 128 variant measured
+                // +0.65 % over four alternated kernel traces, outside the spread of the parent's own (profiles/frame/README.md);
+                // tests/test_conv_frame_host.py holds the function, not this copy
                 unsigned ym = 0, xm = 0;      // 3-bit validity of y0+{0,1,2}, x0+{0,1,2}
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
@@ -268,10 +256,10 @@ __global__ __launch_bounds__(NW * 64, TP == 128 ? 4 : 2) void conv_mfma_kernel(C
     // DMA pieces fired after MFMA group kk: an even split of LPS over the 4 sub-steps
     constexpr int Q1 = (LPS + 3) / 4, Q2 = (LPS + 1) / 2, Q3 = (3 * LPS + 3) / 4;
 
-    // ---------------- per-tile epilogue parameters in LDS (behind the ring): bias (1 or 9 classes) and
-    // PReLU slope of this tile's TC couts.  They are fetched at the start of the tile's first k-step and
-    // written at its end, so the epilogue reads them with short LDS latencies instead of serialising
-    // on global loads.
+    // ---------------- per-tile epilogue parameters in LDS, behind the ring: what EpiParamCache (conv_common.h) does for the
+    // row-patch kernels, kept as this kernel's own copy: on the shared template - called directly or through lambdas, as a
+    // struct or as free functions - the 256 x 64 variant spills one more scalar register (27 instead of 26;
+    // tests/test_kernel_resources_host.py), called directly the 256 x 128 variants go from 12 to 52 bytes of scratch.
     float* lds_bias = reinterpret_cast<float*>(smem + NS * STAGE);       // [9][TC] (class-major)
     float* lds_slope = lds_bias + 9 * TC;                                  // [TC]
     constexpr int PPT = (9 * TC + NW * 64 - 1) / (NW * 64);               // bias values per thread

@@ -173,6 +173,7 @@ S2_CASES = [
     (3, 30, 22, 128, 256, 1),       # odd output sizes (15 x 11), ragged last tile
     (2, 68, 120, 256, 256, 1),      # detector layer4.0.conv1
     (6, 14, 14, 512, 512, 0),       # 16 channel blocks, four cout tiles
+    (9, 128, 128, 64, 256, 1),      # 288 tiles on 256 workgroups (one per CU): the interleaved tile walk takes a second step
 ]
 
 
@@ -730,6 +731,7 @@ WINO_CASES = [
     (7, 6, 30, 192, 160, 2, True, 1),        # widest map the LDS holds (W = 30), ragged cout tile, 3 channel blocks
     (33, 4, 4, 128, 128, 1, True, 0),        # many tiny images per tile
     (1, 16, 16, 64, 64, 0, False, 0),        # exactly one tile
+    (169, 14, 14, 64, 256, 1, True, 0),      # 260 tiles on 256 workgroups (one per CU): the interleaved tile walk takes a second step
 ]
 
 

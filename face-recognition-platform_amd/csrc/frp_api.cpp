@@ -572,7 +572,7 @@ void frp_destroy(frp_handle* h) {
     DevBuf* all[] = {&h->wdata, &h->frames, &h->boxes, &h->kps, &h->scores, &h->counts, &h->anchor, &h->face_slot, &h->nfaces,
                      &h->pyr_boxes, &h->pyr_kps, &h->pyr_scores, &h->pyr_counts, &h->m.q16, &h->m.part_cos, &h->m.part_idx, &h->m.best_cos, &h->m.best_idx, &h->m.hit_cnt, &h->m.hit_idx, &h->m.hit_cos, &h->m.q_groups, &h->m.frame_groups_dev, &h->g_groups_dev, &h->scratch, &h->splitk_ws, &h->dense_logits, &h->scaled, &h->gallery,
                      &h->g_reserved, &h->gx, &h->gx_q, &h->gx_out, &h->det_hashes, &h->quality_in, &h->quality_out,
-                     &h->jenc_in, &h->jenc_coef, &h->jenc_work, &h->jenc_bits, &h->jenc_out};
+                     &h->jenc_in, &h->jenc_coef, &h->jenc_work, &h->jenc_bits, &h->jenc_out, &h->enh_in, &h->enh_out};
     for (DevBuf* b : all) release(*b);
     for (int i = 0; i < EV_COUNT; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->m.frame_groups_ev) (void)hipEventDestroy(h->m.frame_groups_ev);

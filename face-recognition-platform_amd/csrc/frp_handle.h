@@ -157,6 +157,8 @@ struct frp_handle {
     frp::DevBuf quality_in, quality_out;
     // frp_encode_jpeg: rectangles + tables in, quantised coefficients, the scans' work arrays, the unstuffed bit stream, the files (its own)
     frp::DevBuf jenc_in, jenc_coef, jenc_work, jenc_bits, jenc_out;
+    // frp_enhance_pixels / frp_encode_jpeg_enhanced: images + tap tables in, the enhanced pixels (the encoder's source in the second) (its own)
+    frp::DevBuf enh_in, enh_out;
     int32_t* h_nfaces = nullptr;   // pinned: the face count of a device-count pass, copied behind it (read by settle_count alone)
     unsigned char* pin_stage = nullptr;   // pinned staging of the result fetch
     size_t pin_cap = 0;
@@ -242,7 +244,7 @@ public:
 };
 
 // What the files of entry points share (frp_api.cpp, match_api.cpp, ingest_api.cpp, gallery_api.cpp, kernel_api.cpp, quality_api.cpp,
-// jpeg_encode_api.cpp)
+// jpeg_encode_api.cpp, enhance_api.cpp)
 FRP_LOCAL void settle_events(frp_handle* h, bool stream_is_idle);   // frp_api.cpp
 // frp_api.cpp: the pending face count of a device-count pass - waits for the stream unless it is idle, reads the count, corrects the
 // counters.  Called by whatever reuses or discards the pass's slots (h_nfaces, Pass) or needs its count; a no-op otherwise.
@@ -272,6 +274,16 @@ FRP_LOCAL void set_resident(frp_handle* h, int B, int H, int W);    // B frames 
 // host fp32 rows -> unit fp16 rows at dst (device), via the scratch buffer (gallery_api.cpp)
 FRP_LOCAL int upload_rows_normalized(frp_handle* h, const float* rows, int64_t n, _Float16* dst);
 FRP_LOCAL void dist_shutdown(frp_handle* h);                        // gallery_api.cpp: drops the handle's RCCL communicator, if any
+// jpeg_encode_api.cpp, shared with enhance_api.cpp.  The rectangle check of frp_encode_jpeg (FRP_ERR_INVALID and a message that names
+// rectangle i); then the encoder on n images that lie in a device buffer other than the resident frames: plan_buffer checks the
+// encoder's arguments and lays the images out (nothing launched), the caller sets p.frames / p.total_bytes and queues whatever
+// fills the buffer, files queues the encoder behind it and waits (offsets / out as in frp_encode_jpeg)
+struct JpegEncSource { long long pix0; int pitch, w, h; };          // first pixel (index into the buffer), pixels per row, size
+FRP_LOCAL int jpeg_enc_check_rect(frp_handle* h, const std::string& who, const int32_t* rects, int32_t i);
+FRP_LOCAL int jpeg_enc_plan_buffer(frp_handle* h, const std::string& who, const JpegEncSource* src, int32_t n, int quality, int subsampling,
+                                   int restart_mcus, uint32_t flags, std::vector<JpegEncImage>& img, JpegEncParams& p);
+FRP_LOCAL int jpeg_enc_files(frp_handle* h, const std::string& who, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality,
+                             uint8_t* out, int64_t out_cap, int64_t* offsets);
 
 // every entry point's first statement: the handle's mutex, its device, and - unless the call only touches the copy stream - the stage
 // events of a pass nobody has read yet

@@ -508,10 +508,14 @@ struct QualityParams {
 };
 hipError_t launch_face_quality(const QualityParams& p, hipStream_t stream);
 
-// JPEG encoder (jpeg_encode_kernels.hip; frp.h: frp_encode_jpeg): rectangles of the resident u8 frames -> baseline JPEG scans with libjpeg's
-// integer arithmetic.  One image per rectangle; blocks, restart intervals and bit-stream words are numbered over ALL images of a call.
+// JPEG encoder (jpeg_encode_kernels.hip; frp.h: frp_encode_jpeg): images in a u8 [.., 3] device buffer -> baseline JPEG scans with libjpeg's
+// integer arithmetic.  The buffer is the resident frames (one image per rectangle: pix0 = the rectangle's first pixel, pitch = W) or the
+// enhancer's tightly packed output (frp_encode_jpeg_enhanced: pix0 = the image's first pixel, pitch = its width).  Blocks, restart
+// intervals and bit-stream words are numbered over ALL images of a call.
 struct JpegEncImage {
-    int frame, top, left, h, w;   // the rectangle (validated by the caller: inside the frame, not empty)
+    long long pix0;               // pixel index of the image's first pixel in the source buffer
+    int pitch;                    // pixels from one row to the next
+    int h, w;                     // (validated by the caller: every pixel of the image lies inside the buffer, none is empty)
     int mx, my;                   // MCU grid
     int n_int;                    // restart intervals of the image (1 without restart markers)
     int int0;                     // intervals of the images before it
@@ -524,9 +528,8 @@ struct JpegEncTables {            // built on the host (jpeg_encode_api.cpp)
     uint16_t q[2][64];            // quantisation tables, natural order
 };
 struct JpegEncParams {
-    const uint8_t* frames;        // [B,H,W,3] u8, tightly packed
-    long long total_bytes;        // B*H*W*3: no byte at or beyond it is read
-    int B, H, W;
+    const uint8_t* frames;        // the source buffer: u8 pixels of 3 bytes
+    long long total_bytes;        // its size: no byte at or beyond it is read
     int rgb_in;
     const JpegEncImage* img;      // [n]
     const JpegEncTables* tab;
@@ -564,6 +567,44 @@ hipError_t launch_jpeg_enc_measure(const JpegEncParams& p, hipStream_t stream);
 hipError_t launch_jpeg_enc_pack(const JpegEncParams& p, hipStream_t stream);
 // stuffed bytes and restart markers into out
 hipError_t launch_jpeg_enc_emit(const JpegEncParams& p, hipStream_t stream);
+
+// Snapshot enhancer (enhance_kernels.hip; frp.h: frp_enhance_pixels): rectangles of the resident u8 frames -> Pillow's
+// resize(BICUBIC) + UnsharpMask of the crop, byte for byte, tightly packed in `out`.  All tables come from the host (enhance_api.cpp).
+#define ENH_TILE_W 64
+#define ENH_TILE_H 32
+#define ENH_MAX_BOX_R 1           // box radius of the blur's passes the kernel's LDS tile has halo for: UnsharpMask radius <= 2.0
+#define ENH_MAX_HALO (3 * (ENH_MAX_BOX_R + 1))
+#define ENH_MAX_TAPS 5            // bicubic, support 2, never downscaling
+struct EnhanceTap {               // one output column / row of the resample
+    int32_t first;                // first source column / row of the crop (Pillow's xmin)
+    int32_t count;                // taps, 1..ENH_MAX_TAPS; first + count <= the crop's width / height
+    int32_t k[ENH_MAX_TAPS];      // weights scaled by 2^22; an axis that keeps its size has the one tap 2^22: the identity
+    int32_t pad_;
+};
+struct EnhanceImage {
+    int frame, top, left, h, w;   // the rectangle (validated by the caller: inside the frame, not empty)
+    int ow, oh;                   // output size, >= w, h
+    int tiles_x;                  // ENH_TILE_W x ENH_TILE_H tiles of the OUTPUT per row of tiles
+    int tile0;                    // tiles of the images before it
+    int xtap, ytap;               // first entry of its ow column taps / oh row taps in `taps`
+    int pad_;
+    long long out0;               // byte offset of its first pixel in `out`
+};
+struct EnhanceParams {
+    const uint8_t* frames;        // [B,H,W,3] u8, tightly packed, 4-byte aligned base
+    long long total_bytes;        // B*H*W*3: no byte at or beyond it is read
+    int B, H, W;
+    const EnhanceImage* img;      // [n]
+    const EnhanceTap* taps;       // [n_taps]
+    int n, n_tiles, n_taps;
+    int sharpen;                  // 0: resample only
+    int box_r;                    // ImageFilter's box radius r (0..ENH_MAX_BOX_R) and its two weights
+    uint32_t ww, fw;
+    int percent, threshold;
+    uint8_t* out;                 // 4-byte aligned base
+    long long out_bytes;          // allocated bytes: no byte at or beyond it is written
+};
+hipError_t launch_enhance(const EnhanceParams& p, hipStream_t stream);
 
 #ifdef FRP_LAB
 hipError_t launch_mfma_peak(const _Float16* src, float* dst, int blocks, int iters, hipStream_t stream);

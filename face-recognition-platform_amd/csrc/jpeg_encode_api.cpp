@@ -122,32 +122,23 @@ std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs,
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-// validation + geometry shared by the two entry points; FRP_OK with n == 0 means: nothing to do
-int plan(frp_handle* h, const char* who, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags,
-         std::vector<JpegEncImage>& img, JpegEncParams& p) {
-    const std::string w(who);
-    if (h->rB <= 0 || !h->frames.p) return fail(h, FRP_ERR_INVALID, w + ": no resident frames");
-    if (n < 0) return fail(h, FRP_ERR_INVALID, w + ": n < 0");
-    if (flags & ~FRP_FLAG_RGB) return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB");
+// the checks of the encoder's own arguments, shared by every entry point
+int check_args(frp_handle* h, const std::string& w, int quality, int subsampling, int restart_mcus, int& hs, int& vs) {
     if (quality < 1 || quality > 100) return fail(h, FRP_ERR_INVALID, w + ": quality outside 1..100");
-    int hs = 0, vs = 0;
     if (!sampling_ok(subsampling, hs, vs)) return fail(h, FRP_ERR_INVALID, w + ": subsampling is neither FRP_JPEG_420 nor FRP_JPEG_444");
     if (restart_mcus < 0 || restart_mcus > 65535) return fail(h, FRP_ERR_INVALID, w + ": restart_mcus outside 0..65535");
-    if (n == 0) return FRP_OK;
-    if (!rects) return fail(h, FRP_ERR_INVALID, w + ": null rects");
+    return FRP_OK;
+}
+
+// the images' MCU grids and their places among the blocks and intervals of the call
+int layout(frp_handle* h, const std::string& w, const JpegEncSource* src, int32_t n, int hs, int vs, int restart_mcus, uint32_t flags,
+           std::vector<JpegEncImage>& img, JpegEncParams& p) {
     img.resize((size_t)n);
     long long blocks = 0, ints = 0;
     for (int32_t i = 0; i < n; ++i) {
-        const int32_t *r = rects + (size_t)i * 5, f = r[0], top = r[1], right = r[2], bottom = r[3], left = r[4];
-        if (!(f >= 0 && f < h->rB && top >= 0 && top < bottom && bottom <= h->rH && left >= 0 && left < right && right <= h->rW) ||
-            bottom - top > 65535 || right - left > 65535)
-            return fail(h, FRP_ERR_INVALID, w + ": rectangle " + std::to_string(i) + " (frame " + std::to_string(f) + ", top " +
-                        std::to_string(top) + ", right " + std::to_string(right) + ", bottom " + std::to_string(bottom) + ", left " +
-                        std::to_string(left) + ") is empty or outside the " + std::to_string(h->rB) + " resident frames of " +
-                        std::to_string(h->rH) + " x " + std::to_string(h->rW));
         JpegEncImage& I = img[(size_t)i];
         I = JpegEncImage{};
-        I.frame = f; I.top = top; I.left = left; I.h = bottom - top; I.w = right - left;
+        I.pix0 = src[i].pix0; I.pitch = src[i].pitch; I.h = src[i].h; I.w = src[i].w;
         I.mx = (I.w + 8 * hs - 1) / (8 * hs);
         I.my = (I.h + 8 * vs - 1) / (8 * vs);
         const long long mcus = (long long)I.mx * I.my;
@@ -159,15 +150,35 @@ int plan(frp_handle* h, const char* who, const int32_t* rects, int32_t n, int qu
         if (blocks >= (1LL << 26) || ints >= (1LL << 26)) return fail(h, FRP_ERR_INVALID, w + ": more than 2^26 blocks or restart intervals in one call");
     }
     p = JpegEncParams{};
-    p.frames = (const uint8_t*)h->frames.p;
-    p.B = h->rB; p.H = h->rH; p.W = h->rW;
-    p.total_bytes = (long long)h->rB * h->rH * h->rW * 3;
     p.rgb_in = (flags & FRP_FLAG_RGB) ? 1 : 0;
     p.n = n;
     p.hs = hs; p.vs = vs;
     p.ri = restart_mcus;
     p.n_blocks = blocks;
     p.n_int = ints;
+    return FRP_OK;
+}
+
+// validation + geometry of rectangles of the resident frames; FRP_OK with n == 0 means: nothing to do
+int plan(frp_handle* h, const char* who, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags,
+         std::vector<JpegEncImage>& img, JpegEncParams& p) {
+    const std::string w(who);
+    if (h->rB <= 0 || !h->frames.p) return fail(h, FRP_ERR_INVALID, w + ": no resident frames");
+    if (n < 0) return fail(h, FRP_ERR_INVALID, w + ": n < 0");
+    if (flags & ~FRP_FLAG_RGB) return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB");
+    int hs = 0, vs = 0;
+    FRPCHK(check_args(h, w, quality, subsampling, restart_mcus, hs, vs));
+    if (n == 0) return FRP_OK;
+    if (!rects) return fail(h, FRP_ERR_INVALID, w + ": null rects");
+    std::vector<JpegEncSource> src((size_t)n);
+    for (int32_t i = 0; i < n; ++i) {
+        FRPCHK(jpeg_enc_check_rect(h, w, rects, i));
+        const int32_t *r = rects + (size_t)i * 5;
+        src[(size_t)i] = JpegEncSource{((long long)r[0] * h->rH + r[1]) * h->rW + r[4], h->rW, r[2] - r[4], r[3] - r[1]};
+    }
+    FRPCHK(layout(h, w, src.data(), n, hs, vs, restart_mcus, flags, img, p));
+    p.frames = (const uint8_t*)h->frames.p;
+    p.total_bytes = (long long)h->rB * h->rH * h->rW * 3;
     return FRP_OK;
 }
 
@@ -198,18 +209,12 @@ int drain(frp_handle* h, int rc) {
     return rc;
 }
 
-int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags, uint8_t* out,
-           int64_t out_cap, int64_t* offsets) {
-    std::vector<JpegEncImage> img;
+// the planned images (p.frames / p.total_bytes: their buffer) -> the files in out; waits
+int files(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality, uint8_t* out, int64_t out_cap,
+          int64_t* offsets) {
     std::vector<uint8_t> up;
-    JpegEncParams p;
-    FRPCHK(plan(h, "encode_jpeg", rects, n, quality, subsampling, restart_mcus, flags, img, p));
-    if (out_cap < 0) return fail(h, FRP_ERR_INVALID, "encode_jpeg: out_cap < 0");
-    if (!offsets) return fail(h, FRP_ERR_INVALID, "encode_jpeg: null offsets");
-    if (n == 0) {
-        offsets[0] = 0;
-        return FRP_OK;
-    }
+    const int32_t n = p.n;
+    const int restart_mcus = p.ri;
     FRPCHK(forward(h, img, quality, p, up));
     // the work arrays of the entropy half, carved out of one allocation
     const size_t nb = (size_t)p.n_blocks, ni = (size_t)p.n_int;
@@ -234,13 +239,13 @@ int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subs
     hipError_t e = launch_jpeg_enc_measure(p, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&total_bits, p.bit_prefix + nb, sizeof(total_bits), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg measure: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, w + " measure: " + hipGetErrorString(e)));
     // a block codes at most 20 + 63 * 26 bits: anything beyond that is not a size
-    if (total_bits > (unsigned long long)nb * 1658ull) return drain(h, fail(h, FRP_ERR_HIP, "encode_jpeg: implausible bit count"));
+    if (total_bits > (unsigned long long)nb * 1658ull) return drain(h, fail(h, FRP_ERR_HIP, w + ": implausible bit count"));
     // 2. the stream in words (every interval starts on a word of its own), 0xFF counts per chunk, the intervals' places
     p.n_words = (total_bits >> 5) + ni + 1;
     p.n_chunks = (long long)((p.n_words + JE_CHUNK_WORDS - 1) / JE_CHUNK_WORDS);
-    if (jpeg_enc_scan_groups(p.n_chunks) > groups) return drain(h, fail(h, FRP_ERR_INVALID, "encode_jpeg: stream too long"));
+    if (jpeg_enc_scan_groups(p.n_chunks) > groups) return drain(h, fail(h, FRP_ERR_INVALID, w + ": stream too long"));
     const size_t words_bytes = align16((size_t)p.n_words * 4), chunk_bytes = align16((size_t)p.n_chunks * 4);
     int rc = ensure(h, h->jenc_bits, words_bytes + chunk_bytes + align16(((size_t)p.n_chunks + 1) * 8));
     if (rc != FRP_OK) return drain(h, rc);
@@ -253,7 +258,7 @@ int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subs
     if (e == hipSuccess) e = launch_jpeg_enc_pack(p, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(scan_off.data(), p.img_off, scan_off.size() * 8, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg pack: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, w + " pack: " + hipGetErrorString(e)));
     // 3. the files' places: headers + scan + EOI each
     std::vector<std::vector<uint8_t>> hdr((size_t)n);
     std::vector<unsigned long long> scan_base((size_t)n);
@@ -263,14 +268,14 @@ int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subs
         const unsigned long long scan = scan_off[(size_t)i + 1] - scan_off[(size_t)i];
         // stuffing at most doubles a stream, and every interval adds a marker: anything beyond that is not a size
         if (scan_off[(size_t)i + 1] < scan_off[(size_t)i] || scan > 2ull * ((total_bits >> 3) + 4ull * ni) + 16)
-            return drain(h, fail(h, FRP_ERR_HIP, "encode_jpeg: implausible scan size"));
+            return drain(h, fail(h, FRP_ERR_HIP, w + ": implausible scan size"));
         offsets[i] = at;
         scan_base[(size_t)i] = (unsigned long long)at + hdr[(size_t)i].size();
         at += (int64_t)(hdr[(size_t)i].size() + scan + 2);
     }
     offsets[n] = at;
-    if (at > out_cap) return drain(h, fail(h, FRP_ERR_INVALID, "encode_jpeg: the files take " + std::to_string(at) + " bytes, out_cap is " + std::to_string(out_cap)));
-    if (!out) return drain(h, fail(h, FRP_ERR_INVALID, "encode_jpeg: null out"));
+    if (at > out_cap) return drain(h, fail(h, FRP_ERR_INVALID, w + ": the files take " + std::to_string(at) + " bytes, out_cap is " + std::to_string(out_cap)));
+    if (!out) return drain(h, fail(h, FRP_ERR_INVALID, w + ": null out"));
     rc = ensure(h, h->jenc_out, (size_t)at);
     if (rc != FRP_OK) return drain(h, rc);
     p.out = (uint8_t*)h->jenc_out.p;
@@ -279,8 +284,8 @@ int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subs
     if (e == hipSuccess) e = launch_jpeg_enc_emit(p, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, p.out, (size_t)at, hipMemcpyDeviceToHost, h->stream);
     hipError_t e2 = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg emit: ") + hipGetErrorString(e)));
-    if (e2 != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, std::string("encode_jpeg sync: ") + hipGetErrorString(e2)));
+    if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, w + " emit: " + hipGetErrorString(e)));
+    if (e2 != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, w + " sync: " + hipGetErrorString(e2)));
     for (int32_t i = 0; i < n; ++i) {                        // the host's part of every file: what precedes the scan, and EOI
         std::memcpy(out + offsets[i], hdr[(size_t)i].data(), hdr[(size_t)i].size());
         out[offsets[i + 1] - 2] = 0xFF;
@@ -290,7 +295,48 @@ int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subs
     return FRP_OK;
 }
 
+int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags, uint8_t* out,
+           int64_t out_cap, int64_t* offsets) {
+    std::vector<JpegEncImage> img;
+    JpegEncParams p;
+    FRPCHK(plan(h, "encode_jpeg", rects, n, quality, subsampling, restart_mcus, flags, img, p));
+    if (out_cap < 0) return fail(h, FRP_ERR_INVALID, "encode_jpeg: out_cap < 0");
+    if (!offsets) return fail(h, FRP_ERR_INVALID, "encode_jpeg: null offsets");
+    if (n == 0) {
+        offsets[0] = 0;
+        return FRP_OK;
+    }
+    return files(h, "encode_jpeg", img, p, quality, out, out_cap, offsets);
+}
+
 }  // namespace
+
+namespace frp {
+
+int jpeg_enc_check_rect(frp_handle* h, const std::string& w, const int32_t* rects, int32_t i) {
+    const int32_t *r = rects + (size_t)i * 5, f = r[0], top = r[1], right = r[2], bottom = r[3], left = r[4];
+    if (!(f >= 0 && f < h->rB && top >= 0 && top < bottom && bottom <= h->rH && left >= 0 && left < right && right <= h->rW) ||
+        bottom - top > 65535 || right - left > 65535)
+        return fail(h, FRP_ERR_INVALID, w + ": rectangle " + std::to_string(i) + " (frame " + std::to_string(f) + ", top " +
+                    std::to_string(top) + ", right " + std::to_string(right) + ", bottom " + std::to_string(bottom) + ", left " +
+                    std::to_string(left) + ") is empty or outside the " + std::to_string(h->rB) + " resident frames of " +
+                    std::to_string(h->rH) + " x " + std::to_string(h->rW));
+    return FRP_OK;
+}
+
+int jpeg_enc_plan_buffer(frp_handle* h, const std::string& who, const JpegEncSource* src, int32_t n, int quality, int subsampling, int restart_mcus,
+                         uint32_t flags, std::vector<JpegEncImage>& img, JpegEncParams& p) {
+    int hs = 0, vs = 0;
+    FRPCHK(check_args(h, who, quality, subsampling, restart_mcus, hs, vs));
+    return layout(h, who, src, n, hs, vs, restart_mcus, flags, img, p);
+}
+
+int jpeg_enc_files(frp_handle* h, const std::string& who, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality, uint8_t* out,
+                   int64_t out_cap, int64_t* offsets) {
+    return files(h, who, img, p, quality, out, out_cap, offsets);
+}
+
+}  // namespace frp
 
 extern "C" {
 

@@ -1,4 +1,5 @@
-// Baseline JPEG encoder for rectangles of the resident frames (frp.h: frp_encode_jpeg; host side: jpeg_encode_api.cpp).
+// Baseline JPEG encoder for rectangles of the resident frames (frp.h: frp_encode_jpeg; host side: jpeg_encode_api.cpp) - or for images
+// in another device buffer of 3-byte pixels (frp_encode_jpeg_enhanced: the enhancer's output): an image is a first pixel and a row pitch.
 // All arithmetic is libjpeg's integer arithmetic at its defaults (jccolor / jcsample / jfdctint / jcdctmgr / jccoefct / jchuff), so the
 // files equal PIL's byte for byte (tests/test_gpu_jpeg_encode.py against tests/jpeg_encode_model.py and PIL).
 //
@@ -139,15 +140,15 @@ __global__ __launch_bounds__(256) void jpeg_enc_forward_kernel(JpegEncParams p) 
         if (im < 0) continue;
         const JpegEncImage I = p.img[im];
         const int comp = desc[b][1];
-        const long long row0 = ((long long)I.frame * p.H + I.top) * p.W + I.left;        // pixel index of the rectangle's first pixel
+        const long long row0 = I.pix0;
         int v;
         if (comp == 0 || p.hs == 1) {
             const int py = min(desc[b][2] * 8 + y, I.h - 1), px = min(desc[b][3] * 8 + x, I.w - 1);
-            v = je_component(p, (row0 + (long long)py * p.W + px) * 3, comp);
+            v = je_component(p, (row0 + (long long)py * I.pitch + px) * 3, comp);
         } else {                                  // 2 x 2 box: the last real downsampled row repeats, the full-size edges repeat inside it
             const int oy = min(desc[b][2] * 8 + y, ((I.h + 1) >> 1) - 1), ox = desc[b][3] * 8 + x;
             const int r0 = min(2 * oy, I.h - 1), r1 = min(2 * oy + 1, I.h - 1), c0 = min(2 * ox, I.w - 1), c1 = min(2 * ox + 1, I.w - 1);
-            const long long a0 = row0 + (long long)r0 * p.W, a1 = row0 + (long long)r1 * p.W;
+            const long long a0 = row0 + (long long)r0 * I.pitch, a1 = row0 + (long long)r1 * I.pitch;
             v = (je_component(p, (a0 + c0) * 3, comp) + je_component(p, (a0 + c1) * 3, comp) + je_component(p, (a1 + c0) * 3, comp) +
                  je_component(p, (a1 + c1) * 3, comp) + 1 + (ox & 1)) >> 2;
         }
@@ -505,8 +506,7 @@ static hipError_t je_prefix_sum(const uint32_t* in, long long n, u64* out, u64* 
 
 // ----------------------------------------------------------------------------------------------------------------- launchers
 static bool je_common_ok(const JpegEncParams& p) {
-    return p.frames && p.img && p.tab && p.coef && p.n > 0 && p.n_blocks > 0 && p.n_blocks < (1LL << 31) && p.B > 0 && p.H > 0 && p.W > 0 &&
-           p.total_bytes == (long long)p.B * p.H * p.W * 3 && ((p.hs == 2 && p.vs == 2) || (p.hs == 1 && p.vs == 1)) && p.ri >= 0;
+    return p.frames && p.img && p.tab && p.coef && p.n > 0 && p.n_blocks > 0 && p.n_blocks < (1LL << 31) && p.total_bytes > 0 && ((p.hs == 2 && p.vs == 2) || (p.hs == 1 && p.vs == 1)) && p.ri >= 0;
 }
 static bool je_entropy_ok(const JpegEncParams& p) {
     return je_common_ok(p) && p.n_int >= p.n && p.n_int < (1LL << 31) && p.blk_bits && p.bit_prefix && p.group_tot && p.int_word && p.int_bytes &&

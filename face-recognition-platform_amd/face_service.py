@@ -81,6 +81,27 @@ NMS_IOU = float(os.getenv("FRP_NMS_IOU", "0.4"))
 CLUSTER_TILE = 64          # candidate seeds scored per gallery pass in cluster_faces
 MAX_FACES_ENCODE = int(os.getenv("FRP_MAX_FACES", "64"))
 
+
+
+def enhanced_size(w: int, h: int, upscale: float = 2.0, max_pixels: int = 4_000_000) -> Tuple[int, int]:
+    """the enhancer's output size (services/enhancer.py:49-62, _safe_resize_params): the frame times `upscale`, or - beyond
+    `max_pixels` - scaled to that many pixels"""
+    new_w = int(round(w * upscale))
+    new_h = int(round(h * upscale))
+    if new_w * new_h > max_pixels:
+        scale = (max_pixels / (w * h)) ** 0.5
+        new_w = max(1, int(round(w * scale)))
+        new_h = max(1, int(round(h * scale)))
+    return new_w, new_h
+
+
+def enhancer_settings() -> Tuple[float, int, int, bool]:
+    """(upscale factor, pixel cap, JPEG quality, sharpen) with the reference's variables, defaults and parsing (services/enhancer.py:30-33),
+    read when asked"""
+    return (float(os.getenv("ENHANCER_UPSCALE_FACTOR", "2")), int(os.getenv("ENHANCER_MAX_PIXELS", str(4_000_000))),
+            int(os.getenv("ENHANCER_JPEG_QUALITY", "85")), os.getenv("ENHANCER_SHARPEN", "true").lower() in ("1", "true", "yes"))
+
+
 _METRIC_KEYS = ("total_encodings", "total_comparisons", "cache_hits", "cache_misses",
                 "cumulative_encoding_time", "cumulative_comparison_time", "failed_encodings")
 
@@ -443,17 +464,42 @@ class FaceService:
                 for (b, loc), ok in zip(faces, on_dev)]
 
     # ------------------------------------------------------------------ pictures back out (routes/camera.py:73-87,148-149)
-    def snapshot_jpeg(self, frame: int = 0, quality: int = 95) -> Optional[bytes]:
+    @staticmethod
+    def _encode_enhanced(eng, rects, quality: int) -> List[bytes]:
+        """services/enhancer.py:64-92 for rectangles of the resident frames, on the device: each upscaled with BICUBIC to
+        enhanced_size of its own size - only when that is larger (enhancer.py:80) - then UnsharpMask(1, 120, 3) when ENHANCER_SHARPEN
+        says so, then JPEG.  (Annex K Huffman tables: Pillow's save(quality=q), not the optimize=True the reference adds.)"""
+        upscale, max_pixels, _, sharpen = enhancer_settings()
+        sizes = []
+        for _, top, right, bottom, left in rects:
+            w, h = right - left, bottom - top
+            new_w, new_h = enhanced_size(w, h, upscale, max_pixels)
+            sizes.append((new_w, new_h) if new_w > w or new_h > h else (w, h))
+        return eng.encode_jpeg_enhanced(rects, sizes, radius=1, percent=120, threshold=3, sharpen=sharpen, quality=quality)
+
+    def snapshot_jpeg(self, frame: int = 0, quality: int = 95, enhance: bool = False) -> Optional[bytes]:
         """the /snapshot route's cv2.imencode('.jpg', frame, [IMWRITE_JPEG_QUALITY, q]) for a frame that is RESIDENT on the engine
-        (BGR, as the camera loop uploads it), encoded on the device.  None, and a log line, when it cannot be encoded."""
+        (BGR, as the camera loop uploads it), encoded on the device.  enhance: the route's enhance=true branch (routes/snapshot.py:54-117)
+        in front of the encoder - upscaled and sharpened as ENHANCER_UPSCALE_FACTOR / _MAX_PIXELS / _SHARPEN say, on the device too.
+        None, and a log line, when it cannot be encoded."""
         try:
             eng = self._eng()
             with self._sequence_of(eng):
                 _, H, W = eng.resident_shape
-                return eng.encode_jpeg([(int(frame), 0, W, H, 0)], quality=quality)[0]
+                rects = [(int(frame), 0, W, H, 0)]
+                return (self._encode_enhanced(eng, rects, quality) if enhance else eng.encode_jpeg(rects, quality=quality))[0]
         except Exception as e:
             logger.exception("Error encoding snapshot of frame %s: %s", frame, e)
             return None
+
+    def enhance_snapshot(self, frame: int = 0) -> Optional[bytes]:
+        """services/enhancer.py's enhance_snapshot for a resident frame: snapshot_jpeg(enhance=True) at ENHANCER_JPEG_QUALITY"""
+        try:
+            quality = enhancer_settings()[2]
+        except Exception as e:
+            logger.exception("Error reading the enhancer's settings: %s", e)
+            return None
+        return self.snapshot_jpeg(frame, quality=quality, enhance=True)
 
     def encode_frames(self, quality: int = 95) -> List[bytes]:
         """every resident frame as a JPEG (gen_frames_from_cap's cv2.imencode per frame; mjpeg.multipart_part frames one for /feed),
@@ -467,10 +513,11 @@ class FaceService:
             logger.exception("Error encoding the resident frames: %s", e)
             return []
 
-    def face_thumbnails(self, faces: List[Tuple[int, Tuple[int, int, int, int]]], margin: float = 0.0, quality: int = 95) -> List[bytes]:
+    def face_thumbnails(self, faces: List[Tuple[int, Tuple[int, int, int, int]]], margin: float = 0.0, quality: int = 95,
+                        enhance: bool = False) -> List[bytes]:
         """JPEG crops of `faces` = [(frame index, (top, right, bottom, left))] out of the resident frames, each grown by `margin`
-        times its height / width on every side and clipped to the frame; one device call.  [] and a log line on failure (a face
-        that clipping leaves empty is one)."""
+        times its height / width on every side and clipped to the frame; one device call.  enhance: every crop through the
+        enhancer first, as in snapshot_jpeg.  [] and a log line on failure (a face that clipping leaves empty is one)."""
         try:
             eng = self._eng()
             with self._sequence_of(eng):
@@ -479,7 +526,9 @@ class FaceService:
                 for b, (top, right, bottom, left) in faces:
                     dy, dx = int(round(margin * (bottom - top))), int(round(margin * (right - left)))
                     rects.append((int(b), max(0, int(top) - dy), min(W, int(right) + dx), min(H, int(bottom) + dy), max(0, int(left) - dx)))
-                return eng.encode_jpeg(rects, quality=quality) if rects else []
+                if not rects:
+                    return []
+                return self._encode_enhanced(eng, rects, quality) if enhance else eng.encode_jpeg(rects, quality=quality)
         except Exception as e:
             logger.exception("Error encoding face thumbnails: %s", e)
             return []

@@ -31,6 +31,7 @@ JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}      # include/frp.h: FRP_JPEG_4
 YUV_LAYOUTS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3}      # include/frp.h: FRP_YUV_NV12 ... (plane order: frp_upload_yuv)
 YUV_MATRICES = {"BT601": 0, "BT709": 1, "JFIF": 2}             # FRP_YUV_BT601, FRP_YUV_BT709, FRP_YUV_JFIF
 YUV_DEVICE = 1                                                  # frp_yuv_desc.flags: FRP_YUV_DEVICE
+ENHANCE_MAX_RADIUS, ENHANCE_MAX_PIXELS = 2.0, 1 << 24      # include/frp.h: FRP_ENHANCE_MAX_RADIUS, FRP_ENHANCE_MAX_PIXELS (per output image)
 QUALITY_TILE_H, QUALITY_TILE_W = 32, 64      # csrc/frp_internal.h: one workgroup of the face-quality kernel covers this much of a crop
 
 ABI_SYMBOLS = [
@@ -46,13 +47,17 @@ ABI_SYMBOLS = [
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_debug_fc_l2norm", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
     "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_match_groups", "frp_match_within_groups", "frp_set_frame_groups",
     "frp_track_config", "frp_set_frame_streams", "frp_track_reset", "frp_fetch_tracks", "frp_track_stats", "frp_debug_track_step",
-    "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_enhance_pixels", "frp_encode_jpeg_enhanced", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
 class FrpConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("max_batch", C.c_int32), ("max_faces", C.c_int32),
                 ("max_h", C.c_int32), ("max_w", C.c_int32), ("profile", C.c_int32), ("reserved", C.c_int32 * 10)]
+
+
+class FrpEnhanceParams(C.Structure):     # include/frp.h: frp_enhance_params
+    _fields_ = [("radius", C.c_float), ("percent", C.c_int32), ("threshold", C.c_int32), ("sharpen", C.c_int32)]
 
 
 class FrpCounters(C.Structure):
@@ -271,6 +276,9 @@ def load_library() -> C.CDLL:
         lib.frp_jpeg_encode_headers.restype = i64
         lib.frp_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, u32, vp, i64, vp]
         lib.frp_encode_jpeg_coefficients.argtypes = [vp, vp, i32, i32, i32, u32, vp, i64]
+    if hasattr(lib, "frp_enhance_pixels"):   # (as above)
+        lib.frp_enhance_pixels.argtypes = [vp, vp, vp, i32, C.POINTER(FrpEnhanceParams), u32, vp, i64, vp]
+        lib.frp_encode_jpeg_enhanced.argtypes = [vp, vp, vp, i32, C.POINTER(FrpEnhanceParams), i32, i32, i32, u32, vp, i64, vp]
     lib.frp_conv2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]
     if hasattr(lib, "frp_conv_block64"):   # (an older build loaded through FRP_LIB as an A/B partner has none)
         lib.frp_conv_block64.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp]
@@ -985,6 +993,47 @@ class Engine:
             out = np.empty(cap, np.uint8)
             rc = self._lib.frp_encode_jpeg(self._h, _ptr(r), n, int(quality), _subsampling_code(subsampling), int(restart_mcus),
                                            FLAG_RGB if rgb else 0, _ptr(out), cap, _ptr(offsets))
+            if rc == 0 or offsets[n] <= cap:
+                break
+            cap = int(offsets[n])
+        self._chk(rc)
+        return [out[offsets[i]:offsets[i + 1]].tobytes() for i in range(n)]
+
+    @staticmethod
+    def _enhance_args(rects, sizes, radius, percent, threshold, sharpen):
+        r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 5)
+        sz = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
+        if sz.shape[0] != r.shape[0]:
+            raise ValueError(f"{r.shape[0]} rectangles, {sz.shape[0]} output sizes")
+        return r, sz, FrpEnhanceParams(float(radius), int(percent), int(threshold), 1 if sharpen else 0)
+
+    def enhance_pixels(self, rects, sizes, radius: float = 1.0, percent: int = 120, threshold: int = 3, sharpen: bool = True, rgb: bool = False):
+        """rectangles (frame, top, right, bottom, left) of the RESIDENT frames, each resized to its (out_w, out_h) of `sizes` with
+        Pillow's BICUBIC and sharpened with UnsharpMask(radius, percent, threshold), byte for byte (frp.h: frp_enhance_pixels) ->
+        list of [out_h, out_w, 3] u8 arrays in the frames' channel order.  An axis that keeps its size is not resampled;
+        sharpen=False skips the mask.  The last pass's results stay fetchable."""
+        r, sz, prm = self._enhance_args(rects, sizes, radius, percent, threshold, sharpen)
+        n = r.shape[0]
+        cap = int(3 * (np.clip(sz[:, 0].astype(np.int64), 0, None) @ np.clip(sz[:, 1].astype(np.int64), 0, None))) if n else 0
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(n + 1, np.int64)
+        self._chk(self._lib.frp_enhance_pixels(self._h, _ptr(r), _ptr(sz), n, C.byref(prm), FLAG_RGB if rgb else 0, _ptr(out), cap, _ptr(offsets)))
+        return [out[offsets[i]:offsets[i + 1]].reshape(int(sz[i, 1]), int(sz[i, 0]), 3).copy() for i in range(n)]
+
+    def encode_jpeg_enhanced(self, rects, sizes, radius: float = 1.0, percent: int = 120, threshold: int = 3, sharpen: bool = True,
+                             quality: int = 85, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False):
+        """the images of enhance_pixels as baseline JPEG files -> list[bytes], byte for byte Pillow's save(quality=quality) of the
+        enhanced image (frp.h: frp_encode_jpeg_enhanced): enhancer and encoder run back to back on the device.  The first call
+        guesses the size; a second one with the reported size follows when it was too small."""
+        r, sz, prm = self._enhance_args(rects, sizes, radius, percent, threshold, sharpen)
+        n = r.shape[0]
+        offsets = np.zeros(n + 1, np.int64)
+        px = int(np.clip(sz[:, 0].astype(np.int64), 0, None) @ np.clip(sz[:, 1].astype(np.int64), 0, None)) if n else 0
+        cap = 1024 * n + px + 4096
+        for _ in range(2):
+            out = np.empty(cap, np.uint8)
+            rc = self._lib.frp_encode_jpeg_enhanced(self._h, _ptr(r), _ptr(sz), n, C.byref(prm), int(quality), _subsampling_code(subsampling),
+                                                    int(restart_mcus), FLAG_RGB if rgb else 0, _ptr(out), cap, _ptr(offsets))
             if rc == 0 or offsets[n] <= cap:
                 break
             cap = int(offsets[n])

@@ -555,6 +555,38 @@ int frp_encode_jpeg(frp_handle* h, const int32_t* rects, int32_t n, int32_t qual
 int frp_encode_jpeg_coefficients(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, uint32_t flags,
                                  int16_t* coef, int64_t coef_elems);
 
+/* Snapshot enhancer: rectangles of the RESIDENT frames, each upscaled to its own output size with Pillow's Image.resize(BICUBIC) and
+ * sharpened with ImageFilter.UnsharpMask(radius, percent, threshold) - Pillow's integer arithmetic on 8-bit pixels, byte for byte.
+ * replaces: the enhance=true branch of /snapshot (routes/snapshot.py:54-117 -> services/enhancer.py:64-92): resize x2 capped at
+ * ENHANCER_MAX_PIXELS, UnsharpMask(1, 120, 3), JPEG at quality 85 - and the trip of the frame to a host thread in front of it.
+ * rects [n*5] as for the JPEG encoder; sizes [n*2] = out_w, out_h per rectangle.  An axis with out == in is not resampled (as in
+ * Pillow); with sharpen == 0 the mask is skipped.  The blur clamps at the edge of the enhanced crop, never at the frame's: a crop's
+ * neighbours in the frame do not reach the result.
+ * Refused with FRP_ERR_INVALID before anything is launched, nothing written, the message names the rectangle: a rectangle the JPEG
+ * encoder refuses; out_w < w or out_h < h (no downscaling); out_w or out_h above 65535; out_w * out_h above
+ * FRP_ENHANCE_MAX_PIXELS; radius < 0, NaN or above FRP_ENHANCE_MAX_RADIUS; percent < 0; threshold < 0; a flag other than
+ * FRP_FLAG_RGB; no resident frames; n < 0.  n == 0: FRP_OK, nothing launched.  Queued on the handle's stream behind a pending
+ * pass; waits; the handle's last results stay fetchable. */
+typedef struct frp_enhance_params {
+    float radius;          /* UnsharpMask radius, 0..FRP_ENHANCE_MAX_RADIUS */
+    int32_t percent;       /* >= 0 */
+    int32_t threshold;     /* >= 0: differences up to it are left alone */
+    int32_t sharpen;       /* 0: resample only */
+} frp_enhance_params;
+#define FRP_ENHANCE_MAX_RADIUS 2.0f
+#define FRP_ENHANCE_MAX_PIXELS 16777216   /* per output image */
+/* out: the n images back to back, each [out_h][out_w][3] tightly packed in the frames' channel order (FRP_FLAG_RGB changes nothing
+ * here); offsets [n+1]: byte offsets, offsets[n] = the total.  When the total exceeds out_cap: FRP_ERR_INVALID, offsets filled, out
+ * untouched. */
+int frp_enhance_pixels(frp_handle* h, const int32_t* rects, const int32_t* sizes, int32_t n, const frp_enhance_params* params, uint32_t flags,
+                       uint8_t* out, int64_t out_cap, int64_t* offsets);
+/* the same images as baseline JPEG files - quality, subsampling, restart_mcus, flags, out, out_cap and offsets as in the JPEG encoder,
+ * whose checks apply too: byte for byte Pillow's save(quality=q) of the enhanced image (Annex K Huffman tables: against
+ * save(quality=q, optimize=True), which the reference writes, every quantised coefficient agrees and the DHT segments and the scan's
+ * codes differ).  The encoder reads the enhanced pixels where the enhancer left them: no pixel crosses PCIe between the two. */
+int frp_encode_jpeg_enhanced(frp_handle* h, const int32_t* rects, const int32_t* sizes, int32_t n, const frp_enhance_params* params, int32_t quality,
+                             int32_t subsampling, int32_t restart_mcus, uint32_t flags, uint8_t* out, int64_t out_cap, int64_t* offsets);
+
 /* one convolution through the MFMA kernel on host tensors (kernel parity tests):
  * x [N,H,W,Cin] fp16, w [Cout][k][k][Cin] fp16, bias fp32 [Cout] or [9][Cout], out fp16 or fp32
  * flags (0: what the engine would launch for this shape, as set by the environment switches of INTEGRATION.md):

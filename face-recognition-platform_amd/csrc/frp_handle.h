@@ -257,6 +257,10 @@ FRP_LOCAL int stage_queries(frp_handle* h, int n, const float* rows = nullptr, c
 // the hit lists of frp_set_within in the same launch; marks the pass as matched
 // `groups`: over the rows the frame mask of each face permits (frp_set_frame_groups; the caller has checked that B masks are set)
 FRP_LOCAL int match_pass(frp_handle* h, const frp::Switches& sw, int n, const int32_t* n_dev, bool within, bool groups);
+// match_api.cpp: the score rows of the n unit fp16 queries at q16 (device, [round_up(n, 32), 512], zero padded) against the gallery ->
+// all_scores [n x g_rows] (device), by the per-tile kernel's all_scores epilogue: the bits frp_match_scores returns; counted in ctr.match_*.
+// work: the launch's partial / top-1 buffers, grown to fit - the caller's own, so the handle's last results stay (frp_gallery_cluster)
+FRP_LOCAL int match_score_rows(frp_handle* h, const void* q16, int n, ScopedBuf (&work)[4], float* all_scores, const char* what);
 // gallery_api.cpp: the row masks in device memory, for a grouped match launch (built or brought up to date where they are not)
 FRP_LOCAL int row_groups_device(frp_handle* h, const uint32_t** out);
 inline void rec(frp_handle* h, int which) { if (h->cfg.profile) (void)hipEventRecord(h->ev[which], h->stream); }   // a stage event (timers on)

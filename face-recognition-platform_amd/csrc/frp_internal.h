@@ -657,4 +657,32 @@ hipError_t launch_face_groups(const uint32_t* frame_groups, int B, const int32_t
 // top-k of each row of a device score matrix [M x N] by (cosine desc, row asc); -1 / -2.0 beyond N entries
 hipError_t launch_topk_rows(const float* scores, int M, long N, int k, int32_t* idx_out, float* cos_out, hipStream_t stream);
 
+// Greedy gallery clustering (cluster_kernels.hip; frp.h: frp_gallery_cluster; host loop: cluster_api.cpp).  The sweep's state in
+// device memory: seed_pos [n] (-1: unassigned) and the control words ctl [CLUSTER_CTL_WORDS] below.
+#define CLUSTER_MAX_TILE 64          // == FRP_CLUSTER_MAX_TILE (frp.h): one lane per candidate, one bit per candidate in the masks
+enum {
+    CLUSTER_CTL_COUNT = 0,           // candidates of the current tile (0: no unassigned position is left)
+    CLUSTER_CTL_CURSOR = 1,          // every position before it is assigned
+    CLUSTER_CTL_NCLUSTERS = 2,       // seeds so far
+    CLUSTER_CTL_SEEDS_LO = 3,        // the tile's seed mask, bit t: candidate t is a seed
+    CLUSTER_CTL_SEEDS_HI = 4,
+    CLUSTER_CTL_CAND = 8,            // the candidates' positions, ascending [CLUSTER_MAX_TILE]
+    CLUSTER_CTL_WORDS = CLUSTER_CTL_CAND + CLUSTER_MAX_TILE
+};
+struct ClusterParams {
+    const int32_t* order;     // [n] distinct gallery rows in [0, N): the row of every position
+    int n;
+    long N;                   // gallery rows = columns of a score row
+    int tile;                 // candidates per tile, 1..CLUSTER_MAX_TILE
+    int32_t* seed_pos;        // [n]
+    int32_t* ctl;             // [CLUSTER_CTL_WORDS]
+};
+hipError_t launch_cluster_pick(const ClusterParams& p, hipStream_t stream);
+// the candidates' rows -> out [tile][512]: fp16 rows widened to float32 (for launch_gallery_normalize), float64 rows copied
+hipError_t launch_cluster_stage_f16(const ClusterParams& p, const _Float16* gallery, float* out, hipStream_t stream);
+hipError_t launch_cluster_stage_f64(const ClusterParams& p, const double* rows, double* out, hipStream_t stream);
+// resolve + assign over the tile's score block [count][N]: member iff score >= min_cos (float32) / dist <= max_dist (float64)
+hipError_t launch_cluster_sweep_cos(const ClusterParams& p, const float* score, float min_cos, hipStream_t stream);
+hipError_t launch_cluster_sweep_dist(const ClusterParams& p, const double* dist, double max_dist, hipStream_t stream);
+
 }  // namespace frp

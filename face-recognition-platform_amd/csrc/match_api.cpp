@@ -307,6 +307,13 @@ int fetch_within(frp_handle* h, int cap, int32_t* idx, float* cos, int32_t* n_hi
 
 }  // namespace
 
+int frp::match_score_rows(frp_handle* h, const void* q16, int n, ScopedBuf (&work)[4], float* all_scores, const char* what) {
+    MatchParams mp;
+    FRPCHK(fill_match_params(h, q16, n, work[0], work[1], work[2], work[3], mp));
+    mp.all_scores = all_scores;
+    return launch_counted(h, mp, true, what);
+}
+
 int frp::match_pass(frp_handle* h, const Switches& sw, int n, const int32_t* n_dev, bool within, bool groups) {
     Matcher& m = h->m;
     MatchGroups mg{nullptr, nullptr};

@@ -61,6 +61,7 @@ _CAPS = {
     "stage_jpeg": ("upload_jpeg_async",),            # process_frames stages a JpegBatch: upload, swap, pass, fetch under sequence()
     "stage_yuv": ("upload_yuv_async", "swap_frames"),                                                    # ... a YuvBatch
     "track": ("track_config", "set_frame_streams", "fetch_tracks"),      # face tracks: streams=
+    "cluster": ("gallery_cluster",),                 # cluster_faces' greedy sweep on the device
 }
 EngineCaps = namedtuple("EngineCaps", list(_CAPS))
 
@@ -122,6 +123,50 @@ def within_min_cos(tol: float) -> float:
     if not m > -2.0:                      # tol >= sqrt(6) (or NaN): no cosine is excluded
         return -2.0
     return float(np.nextafter(np.float32(m), np.float32(-np.inf)))
+
+
+def _f32_from_key(key: int) -> np.float32:
+    """the float32 whose place in the total order -inf < ... < -0.0 < +0.0 < ... < +inf is `key` (sign-magnitude bits, unfolded)"""
+    bits = key if key >= 0 else (~key) ^ 0x80000000          # key >= 0: the bit pattern itself; key < 0: a negative float, -0.0 = -1
+    return np.array([bits & 0xFFFFFFFF], dtype=np.uint32).view(np.float32)[0]
+
+
+def cluster_min_cos(thr: float) -> float:
+    """The float32 bound m of the device clustering sweep (Engine.gallery_cluster, min_cos=): for EVERY float32 cos, `cos >= m` is
+    the host test `cos_to_distance(cos) <= thr` - not a bound with slack as within_min_cos, nothing re-applies the host test to
+    labels.  cos_to_distance never grows with cos, so the cosines that pass are everything from one float32 upwards; that float32
+    is found by bisection over the ordered bit patterns with cos_to_distance itself.  Nothing passes (thr negative or NaN): NaN,
+    which no comparison reaches; everything but a NaN passes: -inf."""
+    thr = float(thr)
+    ok = lambda c: bool(cos_to_distance(np.float32(c)) <= thr)
+    with np.errstate(invalid="ignore", over="ignore"):
+        lo, hi = -0x7F800000 - 1, 0x7F800000          # keys of -inf and +inf
+        if not ok(_f32_from_key(hi)):
+            return float("nan")
+        if ok(_f32_from_key(lo)):
+            return float("-inf")
+        while hi - lo > 1:                            # ok(lo) is false, ok(hi) true
+            mid = (lo + hi) // 2
+            if ok(_f32_from_key(mid)):
+                hi = mid
+            else:
+                lo = mid
+    return float(_f32_from_key(hi))
+
+
+def clusters_from_seed_pos(names: List[str], seed_pos) -> Dict[str, List[str]]:
+    """The reference's dict (face_service.py:552-585) from the sweep's labels: seeds arise in ascending position, so cluster k is
+    the k-th seed, and a cluster lists its seed, then its members in ascending position"""
+    clusters: Dict[str, List[str]] = {}
+    key_of_seed: Dict[int, str] = {}
+    for p, s in enumerate(np.asarray(seed_pos).tolist()):
+        if s == p:
+            key_of_seed[p] = f"cluster_{len(clusters)}"
+            clusters[key_of_seed[p]] = [names[p]]
+    for p, s in enumerate(np.asarray(seed_pos).tolist()):
+        if s != p:
+            clusters[key_of_seed[s]].append(names[p])
+    return clusters
 
 
 def within_to_matches(rows, cos, n_hits, tol: float, pos_of_row) -> List[Tuple[int, float]]:
@@ -376,6 +421,9 @@ class FaceService:
         # all_matches / batch_compare_faces on the device radius match (Engine.match_within, FLAG_WITHIN) where the engine has it;
         # False: the full score rows on the host (the same results; also what a face with more than WITHIN_CAP hits falls back to)
         self.use_within = True
+        # cluster_faces' sweep on the device (Engine.gallery_cluster) where the engine has it; False: score tiles on the host (the
+        # same clusters)
+        self.use_device_cluster = True
         logger.info("FaceService initialized (model=%s, tolerance=%.3f)", self.model, self.tolerance)
 
     # ------------------------------------------------------------------ engine
@@ -915,6 +963,11 @@ class FaceService:
                 return {"cluster_0": G.names()}
             names = G.names()
             rows = G.rows_of(names)
+            if self.use_device_cluster and engine_caps(self._eng()).cluster:
+                # the whole sweep in one call: rows, score tiles and labels stay on the device, one int per name comes back
+                bound = {"max_dist": float(distance_threshold)} if G.exact else {"min_cos": cluster_min_cos(distance_threshold)}
+                seed_pos, _ = self._eng().gallery_cluster(rows, tile=min(CLUSTER_TILE, 64), **bound)
+                return clusters_from_seed_pos(names, seed_pos)
             emb = self._eng().gallery_get_exact()[rows] if G.exact else self._eng().gallery_get().astype(np.float32)[rows]
             clusters: Dict[str, List[str]] = {}
             assigned = np.zeros(len(names), dtype=bool)

@@ -32,6 +32,7 @@ YUV_LAYOUTS = {"NV12": 0, "NV21": 1, "I420": 2, "YV12": 3}      # include/frp.h:
 YUV_MATRICES = {"BT601": 0, "BT709": 1, "JFIF": 2}             # FRP_YUV_BT601, FRP_YUV_BT709, FRP_YUV_JFIF
 YUV_DEVICE = 1                                                  # frp_yuv_desc.flags: FRP_YUV_DEVICE
 ENHANCE_MAX_RADIUS, ENHANCE_MAX_PIXELS = 2.0, 1 << 24      # include/frp.h: FRP_ENHANCE_MAX_RADIUS, FRP_ENHANCE_MAX_PIXELS (per output image)
+CLUSTER_EXACT, CLUSTER_MAX_TILE = 1, 64                 # include/frp.h: FRP_CLUSTER_EXACT, FRP_CLUSTER_MAX_TILE
 QUALITY_TILE_H, QUALITY_TILE_W = 32, 64      # csrc/frp_internal.h: one workgroup of the face-quality kernel covers this much of a crop
 
 ABI_SYMBOLS = [
@@ -40,7 +41,7 @@ ABI_SYMBOLS = [
     "frp_jpeg_info_get", "frp_jpeg_coefficients", "frp_upload_jpeg_async", "frp_debug_jpeg_device_batches", "frp_debug_graph_replays",
     "frp_set_jpeg_selfsync", "frp_debug_jpeg_selfsync_batches", "frp_jpeg_selfsync_coefficients",
     "frp_dist_unique_id", "frp_dist_init", "frp_dist_destroy", "frp_gallery_allgather",
-    "frp_gallery_size", "frp_gallery_get", "frp_gallery_set_groups", "frp_gallery_get_groups", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact",
+    "frp_gallery_size", "frp_gallery_get", "frp_gallery_set_groups", "frp_gallery_get_groups", "frp_gallery_exact", "frp_gallery_distances", "frp_gallery_get_exact", "frp_gallery_cluster",
     "frp_process_frames", "frp_upload_frames", "frp_process_resident", "frp_fetch_results", "frp_synchronize",
     "frp_host_alloc", "frp_host_free", "frp_upload_frames_async", "frp_swap_frames",
     "frp_upload_yuv", "frp_upload_yuv_async", "frp_get_frames",
@@ -204,6 +205,8 @@ def load_library() -> C.CDLL:
     lib.frp_gallery_exact.argtypes = [vp, i32]
     lib.frp_gallery_distances.argtypes = [vp, vp, i32, vp, i64]
     lib.frp_gallery_get_exact.argtypes = [vp, vp, i64, i64]
+    if hasattr(lib, "frp_gallery_cluster"):  # (an older build loaded through FRP_LIB as an A/B partner has none)
+        lib.frp_gallery_cluster.argtypes = [vp, vp, i64, f32, C.c_double, i32, u32, vp, C.POINTER(i32)]
     lib.frp_process_frames.argtypes = [vp, vp, i32, i32, i32, i64, i32, f32, f32, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.frp_upload_frames.argtypes = [vp, vp, i32, i32, i32, i64]
     lib.frp_process_resident.argtypes = [vp, i32, f32, f32, u32]
@@ -530,6 +533,24 @@ class Engine:
         out = np.empty((n, EMB_DIM), dtype=np.float64)
         self._chk(self._lib.frp_gallery_get_exact(self._h, _ptr(out), first, n))
         return out
+
+    def gallery_cluster(self, order, *, min_cos: Optional[float] = None, max_dist: Optional[float] = None, tile: int = 0):
+        """The greedy sweep of cluster_faces on the device (frp.h: frp_gallery_cluster) over the gallery rows `order`, one per
+        position -> (seed_pos [n] int32: the position of the seed that took each position, the number of clusters).  Exactly one
+        bound: min_cos - member iff the seed's frp_match_scores entry >= min_cos in float32 (unit fp16 rows); max_dist - member
+        iff its frp_gallery_distances entry <= max_dist in float64 (FRP_CLUSTER_EXACT: the exact rows)."""
+        if (min_cos is None) == (max_dist is None):
+            raise ValueError("gallery_cluster: exactly one of min_cos and max_dist")
+        order = np.ascontiguousarray(np.asarray(order, dtype=np.int64).reshape(-1))
+        if order.size and (order.min() < -(1 << 31) or order.max() >= (1 << 31)):
+            raise FrpError(-1, "gallery_cluster: a row does not fit 32 bits")
+        order = order.astype(np.int32)
+        seed_pos = np.full(order.size, -1, np.int32)
+        n_clusters = C.c_int32(0)
+        self._chk(self._lib.frp_gallery_cluster(self._h, _ptr(order), order.size, 0.0 if min_cos is None else float(min_cos),
+                                                0.0 if max_dist is None else float(max_dist), int(tile),
+                                                CLUSTER_EXACT if min_cos is None else 0, _ptr(seed_pos), C.byref(n_clusters)))
+        return seed_pos, int(n_clusters.value)
 
     def gallery_remove_row(self, row: int):
         self._chk(self._lib.frp_gallery_remove_row(self._h, row))

@@ -166,6 +166,31 @@ int frp_gallery_exact(frp_handle* h, int32_t on);
 int frp_gallery_distances(frp_handle* h, const double* q, int32_t M, double* dist, int64_t n_cols);
 int frp_gallery_get_exact(frp_handle* h, double* out, int64_t first_row, int64_t n_rows);
 
+/* ---- gallery clustering ----------------------------------------------------------------
+ * replaces: the greedy sweep of FaceService.cluster_faces (face_service.py:552-585) - in dict order the first unassigned name
+ * becomes a seed and takes every unassigned name within the threshold - with the rows, the N x N scores and the labels all on the
+ * device: one call, one int per name back.
+ * The sweep runs in POSITIONS: order[p] is the gallery row of the p-th name (n distinct rows in [0, frp_gallery_size); after
+ * frp_gallery_remove_row rows are no longer in enrolment order, so the permutation is an argument; n may be smaller than the
+ * gallery: a subset is clustered among itself).  "Seed s takes p" is always evaluated with s as the QUERY and p's row as the
+ * column - the fp16 scores are not symmetric, a query is normalised and rounded again - on the very numbers the stand-alone calls
+ * return:   default              cos >= min_cos  in float32, cos = the frp_match_scores entry of s's unit fp16 row (widened,
+ *                                normalised and rounded as frp_match_scores does with a query) against row order[p], bit for bit
+ *           FRP_CLUSTER_EXACT    dist <= max_dist in float64, dist = the frp_gallery_distances entry of s's float64 row
+ * The bound that is not in use is ignored; a NaN score never passes and a NaN bound passes nothing.  A seed always takes itself,
+ * whatever its own score is: a zero or NaN row is a cluster of one.
+ * seed_pos[p] = the position of the seed that took p (== p for a seed); *n_clusters = the number of seeds.  Seeds arise in ascending
+ * position, so cluster k is the k-th seed and its members, in ascending position behind the seed, are the reference's list.
+ * tile: candidate seeds scored per gallery pass, 1..FRP_CLUSTER_MAX_TILE (0: the largest); the result does not depend on it.
+ * Waits for the stream; changes no gallery state, no result of the last pass and no track.  The fp16 route's passes count in
+ * match_launches / match_bytes.  FRP_ERR_NO_GALLERY for an empty gallery; FRP_ERR_INVALID - nothing launched, nothing written - for
+ * a null pointer, n <= 0 or beyond the gallery size, a row out of range or listed twice, a tile out of range, an unknown flag and
+ * FRP_CLUSTER_EXACT without exact rows. */
+#define FRP_CLUSTER_EXACT 1u   /* sweep the float64 rows (frp_gallery_exact must be on): member iff dist <= max_dist */
+#define FRP_CLUSTER_MAX_TILE 64
+int frp_gallery_cluster(frp_handle* h, const int32_t* order, int64_t n, float min_cos, double max_dist,
+                        int32_t tile /* 1..64, 0: 64 */, uint32_t flags, int32_t* seed_pos /* [n] */, int32_t* n_clusters);
+
 /* ---- the hot path -----------------------------------------------------------------
  * replaces, per frame: cv2.cvtColor(BGR2RGB) (camera.py:225), face_recognition.face_locations
  * (camera.py:232, face_service.py:156), the max_faces cap (camera.py:233-235),

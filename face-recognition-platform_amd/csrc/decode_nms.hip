@@ -10,12 +10,15 @@
 //   (sortable fp16 logit bits << 20) | (0xFFFFF - anchor_index)
 // so "logit descending, ties by lower anchor index" is a plain integer order.  Candidates are
 // the anchors with logit >= logit(threshold); if more than CAP=1024 survive, an exact 3-pass
-// radix select keeps the CAP largest keys.  The candidates are bitonic-sorted in LDS and NMS
-// runs greedily in that order with a barrier only on kept boxes (<= max_faces of them).
+// radix select keeps the CAP largest keys.  The candidates are sorted in LDS and NMS runs greedily
+// in that order (box_nms.h: sort_keys_desc, greedy_nms - the sort, the IoU and the NMS loop that the
+// pyramid merge and the tracker share).  This file keeps what is the detector's own: candidate count,
+// radix select, gather, the decode of an anchor's box, key points and score.
 // All box arithmetic is fp32 with one rounding per operation (file is built with
-// -ffp-contract=off) so it reproduces the fp32 oracle bit for bit.
+// -ffp-contract=off, as every file that includes box_nms.h) so it reproduces the fp32 oracle bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "box_nms.h"
 #include "frp_internal.h"
 
 namespace frp {
@@ -26,6 +29,10 @@ namespace frp {
 __device__ __forceinline__ unsigned sortable16(unsigned short h) {
     if ((h & 0x7fffu) > 0x7c00u) return 0u;     // NaN (real fp16 weights can overflow a head): the lowest key, below -inf
     return (h & 0x8000u) ? (unsigned)(unsigned short)(~h) : (unsigned)(h | 0x8000u);
+}
+// the sort key of anchor i: logit descending, ties by lower anchor index
+__device__ __forceinline__ unsigned long long anchor_key(_Float16 lg, int i) {
+    return ((unsigned long long)sortable16(__builtin_bit_cast(unsigned short, lg)) << 20) | (unsigned long long)(0xFFFFF - i);
 }
 // candidate test: logit >= threshold; in forced top-K mode (threshold -inf) EVERY anchor is a candidate, NaN logits
 // included (they sort last), so exactly min(K, anchors) faces come out and the compact face list never runs short
@@ -78,10 +85,8 @@ __global__ __launch_bounds__(256) void gather_logits_kernel(DecodeParams p) {
 __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
     __shared__ unsigned long long keys[NMS_CAP];
     __shared__ int hist[4096];
-    __shared__ float bx1[NMS_CAP], by1[NMS_CAP], bx2[NMS_CAP], by2[NMS_CAP], barea[NMS_CAP];
-    __shared__ unsigned char supp[NMS_CAP];
-    __shared__ int s_cnt, s_digit, s_need, s_keepn;
-    __shared__ int s_keep[FRP_MAX_FACES_CAP];
+    __shared__ NmsBoxes<NMS_CAP> nms;
+    __shared__ int s_cnt, s_digit, s_need;
     __shared__ int wsum[NT / 64];
 
     const int b = blockIdx.x;
@@ -91,7 +96,7 @@ __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
     const float lt = p.logit_thresh;
 
     // ---- pass 0: count candidates
-    if (tid == 0) { s_cnt = 0; s_keepn = 0; }
+    if (tid == 0) s_cnt = 0;
     __syncthreads();
     const _Float16* dense = p.logits + (long)b * A;     // written by gather_logits_kernel
     int local = 0;
@@ -115,8 +120,7 @@ __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
             for (int i = tid; i < A; i += NT) {
                 const _Float16 lg = dense[i];
                 if (is_candidate(lg, lt)) {
-                    const unsigned long long k = ((unsigned long long)sortable16(__builtin_bit_cast(unsigned short, lg)) << 20) |
-                                                 (unsigned long long)(0xFFFFF - i);
+                    const unsigned long long k = anchor_key(lg, i);
                     if (pass == 0 || (k >> (shift + 12)) == prefix) atomicAdd(&hist[(int)((k >> shift) & 0xFFF)], 1);
                 }
             }
@@ -157,13 +161,12 @@ __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
 
     // ---- gather candidates
     if (tid == 0) s_cnt = 0;
-    for (int i = tid; i < NMS_CAP; i += NT) { keys[i] = 0ull; supp[i] = 0; }
+    for (int i = tid; i < NMS_CAP; i += NT) { keys[i] = 0ull; nms.reset(i); }
     __syncthreads();
     for (int i = tid; i < A; i += NT) {
         const _Float16 lg = dense[i];
         if (is_candidate(lg, lt)) {
-            const unsigned long long k = ((unsigned long long)sortable16(__builtin_bit_cast(unsigned short, lg)) << 20) |
-                                         (unsigned long long)(0xFFFFF - i);
+            const unsigned long long k = anchor_key(lg, i);
             if (k >= T) {
                 const int s = atomicAdd(&s_cnt, 1);
                 if (s < NMS_CAP) keys[s] = k | (1ull << 40);   // bit 40 marks a real entry (> any padding 0)
@@ -173,19 +176,8 @@ __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
     __syncthreads();
     const int n = s_cnt < NMS_CAP ? s_cnt : NMS_CAP;
 
-    // ---- bitonic sort, descending
-    for (int k2 = 2; k2 <= NMS_CAP; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            const int i = tid;
-            const int ixj = i ^ j;
-            if (ixj > i) {
-                const unsigned long long a = keys[i], c = keys[ixj];
-                const bool desc = (i & k2) == 0;
-                if (desc ? (a < c) : (a > c)) { keys[i] = c; keys[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    static_assert(NT == NMS_CAP, "the sort and the NMS: one thread per slot");
+    sort_keys_desc<NMS_CAP>(keys, tid);
 
     // ---- decode boxes of the sorted candidates
     if (tid < n) {
@@ -196,46 +188,26 @@ __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
         const float cx = (float)(x * (8 << lv)), cy = (float)(y * (8 << lv));
         const float x1 = cx - (float)q[1] * s, y1 = cy - (float)q[2] * s;
         const float x2 = cx + (float)q[3] * s, y2 = cy + (float)q[4] * s;
-        bx1[tid] = x1; by1[tid] = y1; bx2[tid] = x2; by2[tid] = y2;
-        barea[tid] = (x2 - x1 + 1.0f) * (y2 - y1 + 1.0f);
+        nms.set(tid, x1, y1, x2, y2);
     }
     __syncthreads();
 
-    // ---- greedy NMS in key order; barrier only when a box is kept
+    // ---- greedy NMS in key order
     const int K = p.max_faces;
-    for (int i = 0; i < n; ++i) {
-        if (supp[i]) continue;            // uniform: written before the last barrier
-        if (tid == 0) s_keep[s_keepn] = i;
-        const int kept = s_keepn + 1;     // uniform read (updated after the barrier below)
-        if (kept >= K) { __syncthreads(); if (tid == 0) s_keepn = kept; __syncthreads(); break; }
-        const float ix1 = bx1[i], iy1 = by1[i], ix2 = bx2[i], iy2 = by2[i], ia = barea[i];
-        for (int j = i + 1 + tid; j < n; j += NT) {
-            const float xx1 = fmaxf(ix1, bx1[j]), yy1 = fmaxf(iy1, by1[j]);
-            const float xx2 = fminf(ix2, bx2[j]), yy2 = fminf(iy2, by2[j]);
-            const float w = fmaxf(0.0f, xx2 - xx1 + 1.0f), h = fmaxf(0.0f, yy2 - yy1 + 1.0f);
-            const float inter = w * h;
-            const float ovr = inter / ((ia + barea[j]) - inter);
-            if (ovr > p.nms_iou) supp[j] = 1;
-        }
-        __syncthreads();
-        if (tid == 0) s_keepn = kept;
-        __syncthreads();
-    }
-    __syncthreads();
-    const int kept = s_keepn;
+    const int kept = greedy_nms<NMS_CAP>(nms, n, K, p.nms_iou, tid);
 
     // ---- outputs
     if (tid < K) {
         float* ob = p.boxes + ((long)b * K + tid) * 4;
         float* ok = p.kps + ((long)b * K + tid) * 10;
         if (tid < kept) {
-            const int c = s_keep[tid];
+            const int c = nms.keep[tid];
             const int idx = 0xFFFFF - (int)(keys[c] & 0xFFFFF);
             int lv, x, y;
             const _Float16* q = anchor_ptr(fv, idx, lv, x, y);
             const float s = (float)(8 << lv);
             const float cx = (float)(x * (8 << lv)), cy = (float)(y * (8 << lv));
-            ob[0] = bx1[c]; ob[1] = by1[c]; ob[2] = bx2[c]; ob[3] = by2[c];
+            ob[0] = nms.x1[c]; ob[1] = nms.y1[c]; ob[2] = nms.x2[c]; ob[3] = nms.y2[c];
 #pragma unroll
             for (int t = 0; t < 5; ++t) {
                 ok[2 * t] = cx + (float)q[5 + 2 * t] * s;
@@ -244,54 +216,11 @@ __global__ __launch_bounds__(NT) void decode_nms_kernel(DecodeParams p) {
             p.scores[(long)b * K + tid] = 1.0f / (1.0f + expf(-(float)q[0]));
             if (p.anchor) p.anchor[(long)b * K + tid] = idx;
         } else {
-            ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
-            for (int t = 0; t < 10; ++t) ok[t] = 0.f;
-            p.scores[(long)b * K + tid] = 0.f;
+            write_empty_face(ob, ok, p.scores + (long)b * K + tid);
             if (p.anchor) p.anchor[(long)b * K + tid] = -1;
         }
     }
     if (tid == 0) p.counts[b] = kept;
-}
-
-// Bilinear down/up-scale of u8 frames for the multi-scale pyramid (BASELINE config 4).  Pixel centres:
-// src = (dst + 0.5) * (S / D) - 0.5, clamped to the image; fp32 lerp in x then y with one rounding per
-// operation (this file is built with -ffp-contract=off), result floor(v + 0.5) -> u8.
-__global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ src, int B, int H, int W,
-                                                        uint8_t* __restrict__ dst, int Hs, int Ws, float ry, float rx) {
-    const long total = (long)B * Hs * Ws;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % Ws);
-        const long r = i / Ws;
-        const int y = (int)(r % Hs);
-        const int b = (int)(r / Hs);
-        float sy = ((float)y + 0.5f) * ry - 0.5f, sx = ((float)x + 0.5f) * rx - 0.5f;
-        sy = fminf(fmaxf(sy, 0.0f), (float)(H - 1));
-        sx = fminf(fmaxf(sx, 0.0f), (float)(W - 1));
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = y0 + 1 < H ? y0 + 1 : H - 1, x1 = x0 + 1 < W ? x0 + 1 : W - 1;
-        const float fy = sy - (float)y0, fx = sx - (float)x0;
-        const uint8_t* p00 = src + (((long)b * H + y0) * W + x0) * 3;
-        const uint8_t* p01 = src + (((long)b * H + y0) * W + x1) * 3;
-        const uint8_t* p10 = src + (((long)b * H + y1) * W + x0) * 3;
-        const uint8_t* p11 = src + (((long)b * H + y1) * W + x1) * 3;
-        uint8_t* o = dst + i * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float top = (float)p00[c] * (1.0f - fx) + (float)p01[c] * fx;
-            const float bot = (float)p10[c] * (1.0f - fx) + (float)p11[c] * fx;
-            const float v = top * (1.0f - fy) + bot * fy;
-            o[c] = (uint8_t)fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);
-        }
-    }
-}
-
-hipError_t launch_resize_u8(const uint8_t* src, int B, int H, int W, uint8_t* dst, int Hs, int Ws, hipStream_t stream) {
-    if (!src || !dst || B <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0) return hipErrorInvalidValue;
-    const long total = (long)B * Hs * Ws;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(resize_u8_kernel, dim3(grid), dim3(256), 0, stream, src, B, H, W, dst, Hs, Ws,
-                       (float)H / (float)Hs, (float)W / (float)Ws);
-    return hipGetLastError();
 }
 
 hipError_t launch_decode_nms(const DecodeParams& p, hipStream_t stream) {
@@ -306,7 +235,7 @@ hipError_t launch_decode_nms(const DecodeParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(gather_logits_kernel, dim3((unsigned)((A + 255) / 256), p.B), dim3(256), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(decode_nms_kernel, dim3(p.B), dim3(NT), 0, stream, p);
+    hipLaunchKernelGGL(decode_nms_kernel, dim3(p.B), dim3(NT), 0, stream, p);      // NT == NMS_CAP threads: sort_keys_desc / greedy_nms<NMS_CAP>
     return hipGetLastError();
 }
 

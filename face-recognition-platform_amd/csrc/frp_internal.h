@@ -388,8 +388,9 @@ hipError_t launch_jpeg_selfsync_round(const JpegSelfsyncParams& p, int k, hipStr
 // at the fix-point: block prefix sums, coefficients (DC differences), DC running sums
 hipError_t launch_jpeg_selfsync_finish(const JpegSelfsyncParams& p, hipStream_t stream);
 
-// u8 bilinear resize for the detection pyramid (frames [B,H,W,3] tightly packed)
+// diagnostic (frp_debug_det_hashes): order-independent 64-bit hash of a tensor's 16-byte words, added to *slot (aux_kernels.hip)
 hipError_t launch_tensor_hash(const void* src, size_t bytes, unsigned long long* slot, hipStream_t stream);
+// u8 bilinear resize for the detection pyramid (pyramid_kernels.hip; frames [B,H,W,3] tightly packed)
 hipError_t launch_resize_u8(const uint8_t* src, int B, int H, int W, uint8_t* dst, int Hs, int Ws, hipStream_t stream);
 
 // K4: 5-point similarity + bilinear warp to 112x112 -> normalised fp16 NHWC8 chips

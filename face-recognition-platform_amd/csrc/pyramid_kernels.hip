@@ -1,20 +1,24 @@
-// K3b: cross-scale merge + greedy NMS of the detection pyramid (BASELINE config 4), one workgroup per frame.
+// The detection pyramid's own kernels (BASELINE config 4): the u8 bilinear resize that makes the scales (resize_u8_kernel, at the
+// end of the file) and K3b, the cross-scale merge + greedy NMS of their detections, one workgroup per frame.
 //
-// The device form of pyramid.merge_scales: every scale's detections (decode_nms_kernel's output, already NMS-ed within the
+// K3b is the device form of pyramid.merge_scales: every scale's detections (decode_nms_kernel's output, already NMS-ed within the
 // scale, coordinates of the resized image) are mapped back to frame pixels with ONE fp32 multiply per coordinate (x by
 // rx = W / Ws, y by ry = H / Hs, the ratios computed on the host as launch_resize_u8 computes them; no clipping), taken in
-// scale order, then detector order, sorted by score descending and put through the greedy +1-pixel-area NMS of decode_nms_kernel.
+// scale order, then detector order, sorted by score descending and put through the greedy +1-pixel-area NMS that
+// decode_nms_kernel runs (box_nms.h: sort_keys_desc, greedy_nms; this file keeps the candidate keys, the rx / ry mapping and
+// the outputs).
 //
 // Ordering is total: candidate slot c = s * P + j (scale s, detector row j < counts[s][b]) gets the unique key
 //   (1 << 41) | (score bits << 9) | (511 - c)
 // - scores are finite and >= 0, so their fp32 bits order as unsigned integers; ties go to the lower slot, which is numpy's
-// stable argsort of -score; bit 41 marks a real entry, so a score of +0.0 still sorts above the padding (key 0).  The keys are
-// bitonic-sorted in LDS.  All box arithmetic is fp32 with one rounding per operation (the file is built with
-// -ffp-contract=off), so the result equals pyramid.merge_scales bit for bit.
+// stable argsort of -score; bit 41 marks a real entry, so a score of +0.0 still sorts above the padding (key 0).  All box
+// arithmetic is fp32 with one rounding per operation (the file is built with -ffp-contract=off, as every file that includes
+// box_nms.h), so the result equals pyramid.merge_scales bit for bit.
 //
 // A few KB per frame: latency-bound, nothing here is tuned.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "box_nms.h"
 #include "frp_internal.h"
 
 namespace frp {
@@ -27,11 +31,10 @@ __device__ __forceinline__ float pick4(const float (&v)[FRP_PYRAMID_MAX_SCALES],
 }
 
 __global__ __launch_bounds__(PM_NT) void pyramid_merge_kernel(PyramidMergeParams p) {
-    __shared__ unsigned long long keys[PM_NT];
-    __shared__ float bx1[PM_NT], by1[PM_NT], bx2[PM_NT], by2[PM_NT], barea[PM_NT];
-    __shared__ unsigned char supp[PM_NT];
-    __shared__ int s_keepn;
-    __shared__ int s_keep[FRP_MAX_FACES_CAP];
+    // (the alignment puts `keys` in front of `nms`; behind it this compiler pads `nms`: 15376 B of LDS instead of 15368.  Nothing
+    // depends on the order but that figure, which tests/test_box_nms_host.py holds)
+    __shared__ alignas(32) unsigned long long keys[PM_NT];
+    __shared__ NmsBoxes<PM_NT> nms;
 
     const int b = blockIdx.x;
     const int tid = threadIdx.x;
@@ -47,70 +50,34 @@ __global__ __launch_bounds__(PM_NT) void pyramid_merge_kernel(PyramidMergeParams
         key = (1ull << 41) | ((unsigned long long)bits << 9) | (unsigned long long)(PM_NT - 1 - tid);
     }
     keys[tid] = key;
-    supp[tid] = 0;
-    if (tid == 0) s_keepn = 0;
+    nms.reset(tid);
     __syncthreads();
 
-    // ---- bitonic sort, descending
-    for (int k2 = 2; k2 <= PM_NT; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            const int i = tid;
-            const int ixj = i ^ j;
-            if (ixj > i) {
-                const unsigned long long a = keys[i], c = keys[ixj];
-                const bool desc = (i & k2) == 0;
-                if (desc ? (a < c) : (a > c)) { keys[i] = c; keys[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    sort_keys_desc<PM_NT>(keys, tid);
 
-    // ---- the sorted candidates' boxes in frame pixels
+    // ---- the sorted candidates' boxes in frame pixels, greedy NMS in key order
     if (tid < n) {
         const int c = PM_NT - 1 - (int)(keys[tid] & (PM_NT - 1));
         const int s = c / P;
         const float rx = pick4(p.rx, s), ry = pick4(p.ry, s);
         const float* q = p.boxes + (((long)s * p.B + b) * P + (c - s * P)) * 4;
-        const float x1 = q[0] * rx, y1 = q[1] * ry, x2 = q[2] * rx, y2 = q[3] * ry;
-        bx1[tid] = x1; by1[tid] = y1; bx2[tid] = x2; by2[tid] = y2;
-        barea[tid] = (x2 - x1 + 1.0f) * (y2 - y1 + 1.0f);
+        nms.set(tid, q[0] * rx, q[1] * ry, q[2] * rx, q[3] * ry);
     }
     __syncthreads();
-
-    // ---- greedy NMS in key order; barrier only when a box is kept (decode_nms_kernel's loop)
-    for (int i = 0; i < n; ++i) {
-        if (supp[i]) continue;            // uniform: written before the last barrier
-        if (tid == 0) s_keep[s_keepn] = i;
-        const int kept = s_keepn + 1;     // uniform read (updated after the barrier below)
-        if (kept >= K) { __syncthreads(); if (tid == 0) s_keepn = kept; __syncthreads(); break; }
-        const float ix1 = bx1[i], iy1 = by1[i], ix2 = bx2[i], iy2 = by2[i], ia = barea[i];
-        for (int j = i + 1 + tid; j < n; j += PM_NT) {
-            const float xx1 = fmaxf(ix1, bx1[j]), yy1 = fmaxf(iy1, by1[j]);
-            const float xx2 = fminf(ix2, bx2[j]), yy2 = fminf(iy2, by2[j]);
-            const float w = fmaxf(0.0f, xx2 - xx1 + 1.0f), h = fmaxf(0.0f, yy2 - yy1 + 1.0f);
-            const float inter = w * h;
-            const float ovr = inter / ((ia + barea[j]) - inter);
-            if (ovr > p.nms_iou) supp[j] = 1;
-        }
-        __syncthreads();
-        if (tid == 0) s_keepn = kept;
-        __syncthreads();
-    }
-    __syncthreads();
-    const int kept = s_keepn;
+    const int kept = greedy_nms<PM_NT>(nms, n, K, p.nms_iou, tid);
 
     // ---- outputs: K slots per frame, zero from the count on, anchor -1 everywhere (a merged face has no anchor of one scale)
     if (tid < K) {
         float* ob = p.out_boxes + ((long)b * K + tid) * 4;
         float* ok = p.out_kps + ((long)b * K + tid) * 10;
         if (tid < kept) {
-            const int i = s_keep[tid];
+            const int i = nms.keep[tid];
             const unsigned long long k = keys[i];
             const int c = PM_NT - 1 - (int)(k & (PM_NT - 1));
             const int s = c / P;
             const float rx = pick4(p.rx, s), ry = pick4(p.ry, s);
             const float* q = p.kps + (((long)s * p.B + b) * P + (c - s * P)) * 10;
-            ob[0] = bx1[i]; ob[1] = by1[i]; ob[2] = bx2[i]; ob[3] = by2[i];
+            ob[0] = nms.x1[i]; ob[1] = nms.y1[i]; ob[2] = nms.x2[i]; ob[3] = nms.y2[i];
 #pragma unroll
             for (int t = 0; t < 5; ++t) {
                 ok[2 * t] = q[2 * t] * rx;
@@ -118,13 +85,52 @@ __global__ __launch_bounds__(PM_NT) void pyramid_merge_kernel(PyramidMergeParams
             }
             p.out_scores[(long)b * K + tid] = __uint_as_float((unsigned)(k >> 9));
         } else {
-            ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
-            for (int t = 0; t < 10; ++t) ok[t] = 0.f;
-            p.out_scores[(long)b * K + tid] = 0.f;
+            write_empty_face(ob, ok, p.out_scores + (long)b * K + tid);
         }
         if (p.out_anchor) p.out_anchor[(long)b * K + tid] = -1;
     }
     if (tid == 0) p.out_counts[b] = kept;
+}
+
+// Bilinear down/up-scale of u8 frames for the multi-scale pyramid (BASELINE config 4).  Pixel centres:
+// src = (dst + 0.5) * (S / D) - 0.5, clamped to the image; fp32 lerp in x then y with one rounding per
+// operation (this file is built with -ffp-contract=off), result floor(v + 0.5) -> u8.
+__global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t* __restrict__ src, int B, int H, int W,
+                                                        uint8_t* __restrict__ dst, int Hs, int Ws, float ry, float rx) {
+    const long total = (long)B * Hs * Ws;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % Ws);
+        const long r = i / Ws;
+        const int y = (int)(r % Hs);
+        const int b = (int)(r / Hs);
+        float sy = ((float)y + 0.5f) * ry - 0.5f, sx = ((float)x + 0.5f) * rx - 0.5f;
+        sy = fminf(fmaxf(sy, 0.0f), (float)(H - 1));
+        sx = fminf(fmaxf(sx, 0.0f), (float)(W - 1));
+        const int y0 = (int)sy, x0 = (int)sx;
+        const int y1 = y0 + 1 < H ? y0 + 1 : H - 1, x1 = x0 + 1 < W ? x0 + 1 : W - 1;
+        const float fy = sy - (float)y0, fx = sx - (float)x0;
+        const uint8_t* p00 = src + (((long)b * H + y0) * W + x0) * 3;
+        const uint8_t* p01 = src + (((long)b * H + y0) * W + x1) * 3;
+        const uint8_t* p10 = src + (((long)b * H + y1) * W + x0) * 3;
+        const uint8_t* p11 = src + (((long)b * H + y1) * W + x1) * 3;
+        uint8_t* o = dst + i * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float top = (float)p00[c] * (1.0f - fx) + (float)p01[c] * fx;
+            const float bot = (float)p10[c] * (1.0f - fx) + (float)p11[c] * fx;
+            const float v = top * (1.0f - fy) + bot * fy;
+            o[c] = (uint8_t)fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);
+        }
+    }
+}
+
+hipError_t launch_resize_u8(const uint8_t* src, int B, int H, int W, uint8_t* dst, int Hs, int Ws, hipStream_t stream) {
+    if (!src || !dst || B <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0) return hipErrorInvalidValue;
+    const long total = (long)B * Hs * Ws;
+    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    hipLaunchKernelGGL(resize_u8_kernel, dim3(grid), dim3(256), 0, stream, src, B, H, W, dst, Hs, Ws,
+                       (float)H / (float)Hs, (float)W / (float)Ws);
+    return hipGetLastError();
 }
 
 hipError_t launch_pyramid_merge(PyramidMergeParams p, hipStream_t stream) {
@@ -140,7 +146,8 @@ hipError_t launch_pyramid_merge(PyramidMergeParams p, hipStream_t stream) {
         p.ry[s] = (float)p.frame_h / (float)p.det_h[s];          // as launch_resize_u8 and pyramid.merge_scales compute them
         p.rx[s] = (float)p.frame_w / (float)p.det_w[s];
     }
-    hipLaunchKernelGGL(pyramid_merge_kernel, dim3(p.B), dim3(PM_NT), 0, stream, p);
+    static_assert(PM_NT == FRP_PYRAMID_MAX_CAND && (PM_NT & (PM_NT - 1)) == 0, "one thread per candidate slot, a power of two of them");
+    hipLaunchKernelGGL(pyramid_merge_kernel, dim3(p.B), dim3(PM_NT), 0, stream, p);      // PM_NT threads: sort_keys_desc / greedy_nms<PM_NT>
     return hipGetLastError();
 }
 

@@ -5,8 +5,9 @@
 // Four launches per pass, stream-ordered:
 //   track_associate_kernel  one wave per stream that occurs in the batch (+ one for the frames of stream -1).  The stream's entry
 //                           list lives in LDS (two lists: the frame's old one and the one being built), two entries per lane.  Per
-//                           detection, in detector order: IoU against the lane's two entries as the NMS kernels compute it (+1-pixel
-//                           areas, fp32, one rounding per operation - the file is built with -ffp-contract=off -, inter / ((a + b) - inter)),
+//                           detection, in detector order: IoU against the lane's two entries by the NMS kernels' own function (box_nms.h:
+//                           box_iou1, a = the detection, b = the entry; +1-pixel areas, fp32, one rounding per operation - the file
+//                           is built with -ffp-contract=off, as every file that includes that header),
 //                           the candidates (unclaimed, iou >= iou_min: a NaN fails) keyed (iou bits << 8) | (255 - entry) and reduced
 //                           with a cross-lane max - a total order: largest IoU, then lowest entry.  Everything else of a frame (ids,
 //                           the new list, the slots' outputs) is lane-parallel behind that serial loop, ordered by ballots.
@@ -31,6 +32,7 @@
 // A few hundred KB per pass: latency-bound, nothing here is tuned beyond keeping the serial loop short.  No scratch memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "box_nms.h"
 #include "frp.h"
 #include "frp_internal.h"
 
@@ -55,11 +57,7 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 
 __device__ __forceinline__ unsigned long long tk_key(float ex1, float ey1, float ex2, float ey2, float ea, float dx1, float dy1, float dx2,
                                                      float dy2, float da, float iou_min, int e) {
-    const float xx1 = fmaxf(dx1, ex1), yy1 = fmaxf(dy1, ey1);
-    const float xx2 = fminf(dx2, ex2), yy2 = fminf(dy2, ey2);
-    const float w = fmaxf(0.0f, xx2 - xx1 + 1.0f), h = fmaxf(0.0f, yy2 - yy1 + 1.0f);
-    const float inter = w * h;
-    const float iou = inter / ((da + ea) - inter);
+    const float iou = box_iou1(dx1, dy1, dx2, dy2, da, ex1, ey1, ex2, ey2, ea);      // a = the detection, b = the entry: tracks.iou's order
     return iou >= iou_min ? (((unsigned long long)__float_as_uint(iou) << 8) | (unsigned long long)(255 - e)) : 0ull;
 }
 
@@ -102,10 +100,10 @@ __global__ __launch_bounds__(64) void track_associate_kernel(TrackParams p) {
             float ax1 = 0.f, ay1 = 0.f, ax2 = 0.f, ay2 = 0.f, bx1 = 0.f, by1 = 0.f, bx2 = 0.f, by2 = 0.f;
             if (v0) { ax1 = L[lane].x1; ay1 = L[lane].y1; ax2 = L[lane].x2; ay2 = L[lane].y2; }
             if (v1) { bx1 = L[lane + 64].x1; by1 = L[lane + 64].y1; bx2 = L[lane + 64].x2; by2 = L[lane + 64].y2; }
-            const float aa = (ax2 - ax1 + 1.0f) * (ay2 - ay1 + 1.0f), ba = (bx2 - bx1 + 1.0f) * (by2 - by1 + 1.0f);
+            const float aa = box_area1(ax1, ay1, ax2, ay2), ba = box_area1(bx1, by1, bx2, by2);
             for (int j = 0; j < n; ++j) {                    // the serial part
                 const float dx1 = fb[4 * j], dy1 = fb[4 * j + 1], dx2 = fb[4 * j + 2], dy2 = fb[4 * j + 3];
-                const float da = (dx2 - dx1 + 1.0f) * (dy2 - dy1 + 1.0f);
+                const float da = box_area1(dx1, dy1, dx2, dy2);
                 unsigned long long k0 = 0ull, k1 = 0ull;
                 if (v0 && !c0) k0 = tk_key(ax1, ay1, ax2, ay2, aa, dx1, dy1, dx2, dy2, da, p.iou_min, lane);
                 if (v1 && !c1) k1 = tk_key(bx1, by1, bx2, by2, ba, dx1, dy1, dx2, dy2, da, p.iou_min, lane + 64);

@@ -8,7 +8,9 @@
 //
 // Ordering is total and deterministic: every anchor gets the unique 36-bit key
 //   (sortable fp16 logit bits << 20) | (0xFFFFF - anchor_index)
-// so "logit descending, ties by lower anchor index" is a plain integer order.  Candidates are
+// so "logit descending, ties by lower anchor index" is a plain integer order.  Logits that compare equal are keyed
+// equally, the two signed zeros included (-0.0 is what a conv epilogue writes for a tiny negative value, and 0 is the
+// default threshold's boundary): among them the anchor index alone decides, as in the oracle's stable sort.  Candidates are
 // the anchors with logit >= logit(threshold); if more than CAP=1024 survive, an exact 3-pass
 // radix select keeps the CAP largest keys.  The candidates are sorted in LDS and NMS runs greedily
 // in that order (box_nms.h: sort_keys_desc, greedy_nms - the sort, the IoU and the NMS loop that the
@@ -28,7 +30,9 @@ namespace frp {
 
 __device__ __forceinline__ unsigned sortable16(unsigned short h) {
     if ((h & 0x7fffu) > 0x7c00u) return 0u;     // NaN (real fp16 weights can overflow a head): the lowest key, below -inf
-    return (h & 0x8000u) ? (unsigned)(unsigned short)(~h) : (unsigned)(h | 0x8000u);
+    // negative: 0x8000 - magnitude, not ~h = 0x7fff - magnitude: -0.0 gets +0.0's key (0x8000), equal logits get equal keys and the
+    // anchor index decides among them; -inf is 0x0400, still above NaN.  No compare: the four loops over the anchors pay per instruction
+    return (h & 0x8000u) ? 0x8000u - (h & 0x7fffu) : (unsigned)(h | 0x8000u);
 }
 // the sort key of anchor i: logit descending, ties by lower anchor index
 __device__ __forceinline__ unsigned long long anchor_key(_Float16 lg, int i) {

@@ -9,7 +9,7 @@ What this holds is the formula and the operand order against an independent rest
 operation": the host compiler fuses nothing in these two functions with or without the header's `#pragma clang fp contract(off)`, on a
 CPU with FMA instructions too (the only product in front of a sum, inter = w * h, has a second use as the numerator), so the harness
 prints the same bits either way.  On the device that rule is held by the array_equal tests of tests/test_gpu_kernels.py (decode),
-tests/test_gpu_pyramid.py and tests/test_gpu_tracks.py, and for the callers' own box arithmetic by the Makefile's -ffp-contract=off
+tests/test_gpu_decode_exact.py (the planted cases of tests/decode_cases.py), tests/test_gpu_pyramid.py and tests/test_gpu_tracks.py, and for the callers' own box arithmetic by the Makefile's -ffp-contract=off
 rule for the three files that include the header, which test_the_including_files_are_built_without_contraction holds in place.
 test_kernel_budgets_of_the_detection_tail holds the kernels' LDS and scratch sizes (no GPU: the code objects' metadata)."""
 import os

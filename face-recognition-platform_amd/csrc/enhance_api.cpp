@@ -77,10 +77,12 @@ struct Plan {
 };
 
 // every check of the two entry points' shared arguments, the images' geometry and tables; nothing is launched.  FRP_OK with n == 0: nothing to do
-int plan(frp_handle* h, const std::string& w, const int32_t* rects, const int32_t* sizes, int32_t n, const frp_enhance_params* prm, uint32_t flags, Plan& pl) {
+int plan(frp_handle* h, const std::string& w, const int32_t* rects, const int32_t* sizes, int32_t n, const frp_enhance_params* prm, uint32_t flags,
+         uint32_t allowed, Plan& pl) {
     if (h->rB <= 0 || !h->frames.p) return fail(h, FRP_ERR_INVALID, w + ": no resident frames");
     if (n < 0) return fail(h, FRP_ERR_INVALID, w + ": n < 0");
-    if (flags & ~FRP_FLAG_RGB) return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB");
+    if (flags & ~allowed)
+        return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB" + ((allowed & FRP_FLAG_JPEG_OPTIMIZE) ? " and FRP_FLAG_JPEG_OPTIMIZE" : ""));
     if (!prm) return fail(h, FRP_ERR_INVALID, w + ": null params");
     if (!(prm->radius >= 0.f && prm->radius <= FRP_ENHANCE_MAX_RADIUS))      // (NaN fails both)
         return fail(h, FRP_ERR_INVALID, w + ": radius outside 0.." + std::to_string(FRP_ENHANCE_MAX_RADIUS));
@@ -165,7 +167,7 @@ int frp_enhance_pixels(frp_handle* h, const int32_t* rects, const int32_t* sizes
     if (!h) return FRP_ERR_INVALID;
     Guard g(h, false);      // queued behind whatever pass is pending; its stage events are read after this call's own wait
     Plan pl;
-    FRPCHK(plan(h, "enhance_pixels", rects, sizes, n, params, flags, pl));
+    FRPCHK(plan(h, "enhance_pixels", rects, sizes, n, params, flags, FRP_FLAG_RGB, pl));
     if (out_cap < 0) return fail(h, FRP_ERR_INVALID, "enhance_pixels: out_cap < 0");
     if (!offsets) return fail(h, FRP_ERR_INVALID, "enhance_pixels: null offsets");
     if (n == 0) {
@@ -193,7 +195,7 @@ int frp_encode_jpeg_enhanced(frp_handle* h, const int32_t* rects, const int32_t*
     Guard g(h, false);
     const std::string w("encode_jpeg_enhanced");
     Plan pl;
-    FRPCHK(plan(h, w, rects, sizes, n, params, flags, pl));
+    FRPCHK(plan(h, w, rects, sizes, n, params, flags, FRP_FLAG_RGB | FRP_FLAG_JPEG_OPTIMIZE, pl));
     std::vector<JpegEncSource> src((size_t)std::max(n, 0));
     for (int32_t i = 0; i < n; ++i) src[(size_t)i] = JpegEncSource{pl.img[(size_t)i].out0 / 3, pl.img[(size_t)i].ow, pl.img[(size_t)i].ow, pl.img[(size_t)i].oh};
     std::vector<JpegEncImage> img;
@@ -209,7 +211,7 @@ int frp_encode_jpeg_enhanced(frp_handle* h, const int32_t* rects, const int32_t*
     FRPCHK(enqueue(h, pl, up));
     jp.frames = pl.p.out;                                   // the enhanced pixels never leave the device: the encoder reads them where they are
     jp.total_bytes = pl.p.out_bytes;
-    return jpeg_enc_files(h, w, img, jp, quality, out, out_cap, offsets);      // (waits also on its error paths: `up` lives long enough)
+    return jpeg_enc_files(h, w, img, jp, quality, (flags & FRP_FLAG_JPEG_OPTIMIZE) != 0, out, out_cap, offsets);      // (waits also on its error paths: `up` lives long enough)
 }
 
 }  // extern "C"

@@ -281,13 +281,13 @@ FRP_LOCAL void dist_shutdown(frp_handle* h);                        // gallery_a
 // jpeg_encode_api.cpp, shared with enhance_api.cpp.  The rectangle check of frp_encode_jpeg (FRP_ERR_INVALID and a message that names
 // rectangle i); then the encoder on n images that lie in a device buffer other than the resident frames: plan_buffer checks the
 // encoder's arguments and lays the images out (nothing launched), the caller sets p.frames / p.total_bytes and queues whatever
-// fills the buffer, files queues the encoder behind it and waits (offsets / out as in frp_encode_jpeg)
+// fills the buffer, files queues the encoder behind it and waits (offsets / out as in frp_encode_jpeg; optimize: FRP_FLAG_JPEG_OPTIMIZE)
 struct JpegEncSource { long long pix0; int pitch, w, h; };          // first pixel (index into the buffer), pixels per row, size
 FRP_LOCAL int jpeg_enc_check_rect(frp_handle* h, const std::string& who, const int32_t* rects, int32_t i);
 FRP_LOCAL int jpeg_enc_plan_buffer(frp_handle* h, const std::string& who, const JpegEncSource* src, int32_t n, int quality, int subsampling,
                                    int restart_mcus, uint32_t flags, std::vector<JpegEncImage>& img, JpegEncParams& p);
 FRP_LOCAL int jpeg_enc_files(frp_handle* h, const std::string& who, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality,
-                             uint8_t* out, int64_t out_cap, int64_t* offsets);
+                             bool optimize, uint8_t* out, int64_t out_cap, int64_t* offsets);
 
 // every entry point's first statement: the handle's mutex, its device, and - unless the call only touches the copy stream - the stage
 // events of a pass nobody has read yet

@@ -523,7 +523,7 @@ struct JpegEncImage {
     int pad_;
     long long blk0;               // blocks of the images before it (a block = 64 coefficients)
 };
-struct JpegEncTables {            // built on the host (jpeg_encode_api.cpp)
+struct JpegEncTables {            // built on the host (jpeg_encode_api.cpp): Annex K's, or one set per image (FRP_FLAG_JPEG_OPTIMIZE)
     uint32_t dc[2][16];           // (length << 16) | code by magnitude category; luminance, chrominance
     uint32_t ac[2][256];          // ... by run / size symbol
     uint16_t q[2][64];            // quantisation tables, natural order
@@ -533,13 +533,15 @@ struct JpegEncParams {
     long long total_bytes;        // its size: no byte at or beyond it is read
     int rgb_in;
     const JpegEncImage* img;      // [n]
-    const JpegEncTables* tab;
+    const JpegEncTables* tab;     // image i codes with tab[i * tab_stride]; the forward half quantises with tab[0].q
+    int tab_stride;               // 0: one set for the call, 1: one per image
     int n;
     int hs, vs;                   // luma sampling factors: 2 x 2 (4:2:0) or 1 x 1 (4:4:4); chroma is 1 x 1
     int ri;                       // MCUs per restart interval, 0: none
     long long n_blocks;           // of all images
     long long n_int;              // intervals of all images
     int16_t* coef;                // [n_blocks][64] natural order; per image: component by component over the MCU-padded grid
+    uint32_t* hist;               // [n][JE_HIST_BINS] symbol counts per image (zeroed before the histogram kernel); null without it
     // entropy stage (null for the forward half alone)
     uint32_t* blk_bits;                   // [n_blocks], in SCAN order within each image: bits of the block's codes
     unsigned long long* bit_prefix;       // [n_blocks + 1]: exclusive sums of blk_bits
@@ -560,8 +562,11 @@ struct JpegEncParams {
     unsigned long long out_bytes;         // allocated bytes: no byte at or beyond it is written
 };
 #define JE_CHUNK_WORDS 256
+#define JE_HIST_BINS 544          // per image: dc [2][16] by category, then ac [2][256] by run / size symbol (frp.h: FRP_JPEG_HIST_ELEMS)
 size_t jpeg_enc_scan_groups(long long n);       // entries of group_tot a prefix sum over n elements needs
 hipError_t launch_jpeg_enc_forward(const JpegEncParams& p, hipStream_t stream);
+// the symbols every image's scan will code, counted into hist (zeroed by the caller, behind the forward half)
+hipError_t launch_jpeg_enc_hist(const JpegEncParams& p, hipStream_t stream);
 // block bits + their prefix sums; bit_prefix[n_blocks] is the size of everything
 hipError_t launch_jpeg_enc_measure(const JpegEncParams& p, hipStream_t stream);
 // (words zeroed, n_words >= (bit_prefix[n_blocks] >> 5) + n_int + 1): bit packing, 0xFF counts, the intervals' places -> img_off

@@ -1,8 +1,12 @@
-// frp_jpeg_encode_headers, frp_encode_jpeg, frp_encode_jpeg_coefficients (include/frp.h): baseline JPEG files of rectangles of the
-// resident frames.  The header segments are written here, in PIL's order; the scans come from jpeg_encode_kernels.hip.
+// frp_jpeg_encode_headers, frp_jpeg_optimal_table, frp_encode_jpeg, frp_encode_jpeg_coefficients, frp_encode_jpeg_histograms
+// (include/frp.h): baseline JPEG files of rectangles of the resident frames.  The header segments are written here, in PIL's order,
+// and so are the optimal Huffman tables of FRP_FLAG_JPEG_OPTIMIZE, from the counts of jpeg_enc_hist_kernel; the scans come from
+// jpeg_encode_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <functional>
+#include <queue>
 
 #include "frp.h"
 #include "frp_handle.h"
@@ -60,13 +64,108 @@ void huff_codes(const uint8_t* bits, const uint8_t* vals, uint32_t* out) {
     }
 }
 
-void build_tables(int quality, JpegEncTables& t) {
+// BITS / HUFFVAL of one table, as a DHT segment carries them
+struct HuffSpec {
+    uint8_t bits[16];
+    uint8_t vals[256];
+    int n;             // symbols
+};
+// DC0, AC0, DC1, AC1 - the order of the DHT segments
+struct HuffSet { HuffSpec t[4]; };
+
+HuffSet annex_k() {
+    HuffSet s{};
+    for (int i = 0; i < 2; ++i) {
+        std::memcpy(s.t[2 * i].bits, kDcBits[i], 16);
+        std::memcpy(s.t[2 * i].vals, kDcVals, 12);
+        s.t[2 * i].n = 12;
+        std::memcpy(s.t[2 * i + 1].bits, kAcBits[i], 16);
+        std::memcpy(s.t[2 * i + 1].vals, kAcVals[i], 162);
+        s.t[2 * i + 1].n = 162;
+    }
+    return s;
+}
+
+void build_tables(int quality, const HuffSet& s, JpegEncTables& t) {
     std::memset(&t, 0, sizeof(t));
     for (int i = 0; i < 2; ++i) {
-        huff_codes(kDcBits[i], kDcVals, t.dc[i]);
-        huff_codes(kAcBits[i], kAcVals[i], t.ac[i]);
+        huff_codes(s.t[2 * i].bits, s.t[2 * i].vals, t.dc[i]);
+        huff_codes(s.t[2 * i + 1].bits, s.t[2 * i + 1].vals, t.ac[i]);
     }
     quant_tables(quality, t.q);
+}
+
+// libjpeg's jpeg_gen_optimal_table, from its definition (T.81 K.2; frp.h: frp_jpeg_optimal_table).  false: all counts zero, or a code
+// deeper than 32 bits.  (libjpeg's searches start from a bound of 10^9 and so never pick a larger count; here every count can be
+// picked - the two agree below that bound, which no file Pillow can write comes near.)
+bool optimal_table(const uint32_t* counts, HuffSpec& out) {
+    long long freq[257];
+    int codesize[257], others[257], bits[33];
+    bool any = false;
+    for (int i = 0; i < 256; ++i) {
+        freq[i] = counts[i];
+        any = any || counts[i];
+    }
+    if (!any) return false;
+    freq[256] = 1;                                            // the pseudo-symbol: no real symbol gets the all-ones code
+    for (int i = 0; i < 257; ++i) { codesize[i] = 0; others[i] = -1; }
+    // libjpeg finds the two least frequent entries by two linear searches with `<=` (ties go to the larger index, the second search
+    // skips the first's pick): the same two entries leave a heap ordered by (count, larger index first) - a call with hundreds of
+    // crops makes over a thousand tables, and the searches were most of its time
+    typedef std::pair<long long, int> Entry;                  // (count, -index): the smallest pair is the next pick
+    std::vector<Entry> entries;
+    entries.reserve(257);
+    for (int i = 0; i <= 256; ++i)
+        if (freq[i]) entries.push_back(Entry(freq[i], -i));
+    std::priority_queue<Entry, std::vector<Entry>, std::greater<Entry>> live(std::greater<Entry>(), std::move(entries));
+    while (live.size() > 1) {
+        int c1 = -live.top().second;
+        live.pop();
+        int c2 = -live.top().second;
+        live.pop();
+        freq[c1] += freq[c2];
+        freq[c2] = 0;
+        live.push(Entry(freq[c1], -c1));
+        for (++codesize[c1]; others[c1] >= 0;) { c1 = others[c1]; ++codesize[c1]; }
+        others[c1] = c2;                                      // chain c2's tree behind c1's
+        for (++codesize[c2]; others[c2] >= 0;) { c2 = others[c2]; ++codesize[c2]; }
+    }
+    std::memset(bits, 0, sizeof(bits));
+    int first[34] = {0};                                      // HUFFVAL is the symbols by (unlimited) code length, then by value:
+    for (int i = 0; i <= 256; ++i) {                          // first[len] = symbols with shorter codes (a counting sort)
+        if (codesize[i] > 32) return false;
+        if (codesize[i]) ++bits[codesize[i]];
+        if (codesize[i] && i < 256) ++first[codesize[i] + 1];
+    }
+    for (int len = 1; len <= 33; ++len) first[len] += first[len - 1];
+    for (int i = 32; i > 16; --i)                             // Figure K.3: no code longer than 16
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (bits[j] == 0) --j;
+            bits[i] -= 2; ++bits[i - 1];
+            bits[j + 1] += 2; --bits[j];
+        }
+    int last = 16;
+    while (bits[last] == 0) --last;
+    --bits[last];                                             // the pseudo-symbol leaves: it had the longest code
+    out = HuffSpec{};
+    for (int i = 1; i <= 16; ++i) out.bits[i - 1] = (uint8_t)bits[i];
+    for (int j = 0; j < 256; ++j)
+        if (codesize[j]) {
+            out.vals[first[codesize[j]]++] = (uint8_t)j;
+            ++out.n;
+        }
+    return true;
+}
+
+// the four tables of one image from its symbol counts (JE_HIST_BINS: dc [2][16], ac [2][256])
+bool optimal_set(const uint32_t* hist, HuffSet& s) {
+    for (int i = 0; i < 2; ++i) {
+        uint32_t dc[256] = {0};
+        std::memcpy(dc, hist + 16 * i, 16 * sizeof(uint32_t));
+        if (!optimal_table(dc, s.t[2 * i]) || !optimal_table(hist + 32 + 256 * i, s.t[2 * i + 1])) return false;
+    }
+    return true;
 }
 
 bool sampling_ok(int subsampling, int& hs, int& vs) {
@@ -82,8 +181,9 @@ struct Seg {           // appends big-endian segments
     void marker(int m, int payload) { u8(0xFF); u8(m); u16(payload + 2); }
 };
 
-// SOI, APP0 (JFIF 1.01, no density), DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, DRI when restart_mcus > 0, SOS
-std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs, int restart_mcus) {
+// SOI, APP0 (JFIF 1.01, no density), DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, DRI when restart_mcus > 0, SOS; the DHT segments carry
+// the tables of `huff`: their length is the image's own
+std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs, int restart_mcus, const HuffSet& huff) {
     Seg s;
     s.u8(0xFF); s.u8(0xD8);
     s.marker(0xE0, 14);
@@ -101,15 +201,12 @@ std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs,
     s.u8(1); s.u8((hs << 4) | vs); s.u8(0);
     s.u8(2); s.u8(0x11); s.u8(1);
     s.u8(3); s.u8(0x11); s.u8(1);
-    for (int t = 0; t < 2; ++t) {
-        s.marker(0xC4, 1 + 16 + 12);
-        s.u8(t);
-        for (int i = 0; i < 16; ++i) s.u8(kDcBits[t][i]);
-        for (int i = 0; i < 12; ++i) s.u8(kDcVals[i]);
-        s.marker(0xC4, 1 + 16 + 162);
-        s.u8(0x10 | t);
-        for (int i = 0; i < 16; ++i) s.u8(kAcBits[t][i]);
-        for (int i = 0; i < 162; ++i) s.u8(kAcVals[t][i]);
+    for (int t = 0; t < 4; ++t) {
+        const HuffSpec& hf = huff.t[t];
+        s.marker(0xC4, 1 + 16 + hf.n);
+        s.u8(((t & 1) << 4) | (t >> 1));                     // class (0: DC, 1: AC), table
+        for (int i = 0; i < 16; ++i) s.u8(hf.bits[i]);
+        for (int i = 0; i < hf.n; ++i) s.u8(hf.vals[i]);
     }
     if (restart_mcus > 0) {
         s.marker(0xDD, 2);
@@ -118,6 +215,11 @@ std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs,
     s.marker(0xDA, 10);
     s.u8(3); s.u8(1); s.u8(0x00); s.u8(2); s.u8(0x11); s.u8(3); s.u8(0x11); s.u8(0); s.u8(63); s.u8(0);
     return s.b;
+}
+
+// ... with the Annex K tables
+std::vector<uint8_t> headers(int width, int height, int quality, int hs, int vs, int restart_mcus) {
+    return headers(width, height, quality, hs, vs, restart_mcus, annex_k());
 }
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -161,11 +263,12 @@ int layout(frp_handle* h, const std::string& w, const JpegEncSource* src, int32_
 
 // validation + geometry of rectangles of the resident frames; FRP_OK with n == 0 means: nothing to do
 int plan(frp_handle* h, const char* who, const int32_t* rects, int32_t n, int quality, int subsampling, int restart_mcus, uint32_t flags,
-         std::vector<JpegEncImage>& img, JpegEncParams& p) {
+         uint32_t allowed, std::vector<JpegEncImage>& img, JpegEncParams& p) {
     const std::string w(who);
     if (h->rB <= 0 || !h->frames.p) return fail(h, FRP_ERR_INVALID, w + ": no resident frames");
     if (n < 0) return fail(h, FRP_ERR_INVALID, w + ": n < 0");
-    if (flags & ~FRP_FLAG_RGB) return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB");
+    if (flags & ~allowed)
+        return fail(h, FRP_ERR_INVALID, w + ": flags other than FRP_FLAG_RGB" + ((allowed & FRP_FLAG_JPEG_OPTIMIZE) ? " and FRP_FLAG_JPEG_OPTIMIZE" : ""));
     int hs = 0, vs = 0;
     FRPCHK(check_args(h, w, quality, subsampling, restart_mcus, hs, vs));
     if (n == 0) return FRP_OK;
@@ -182,19 +285,24 @@ int plan(frp_handle* h, const char* who, const int32_t* rects, int32_t n, int qu
     return FRP_OK;
 }
 
-// rectangles + tables (+ room for the scans' places) to the device, the coefficient buffer; queues the forward half
-int forward(frp_handle* h, const std::vector<JpegEncImage>& img, int quality, JpegEncParams& p, std::vector<uint8_t>& up) {
+// rectangles + tables (+ room for the scans' places; `hist`: and for every image's symbol counts and its own tables, p.hist) to the
+// device, the coefficient buffer; queues the forward half
+int forward(frp_handle* h, const std::vector<JpegEncImage>& img, int quality, JpegEncParams& p, std::vector<uint8_t>& up, bool hist = false) {
     const size_t img_bytes = align16(img.size() * sizeof(JpegEncImage)), tab_bytes = align16(sizeof(JpegEncTables));
+    const size_t base_bytes = img_bytes + tab_bytes + align16(img.size() * sizeof(unsigned long long));
+    const size_t hist_bytes = hist ? align16(img.size() * JE_HIST_BINS * sizeof(uint32_t)) : 0;
     up.assign(img_bytes + tab_bytes, 0);
     std::memcpy(up.data(), img.data(), img.size() * sizeof(JpegEncImage));
     JpegEncTables t;
-    build_tables(quality, t);
+    build_tables(quality, annex_k(), t);
     std::memcpy(up.data() + img_bytes, &t, sizeof(t));
-    FRPCHK(ensure(h, h->jenc_in, up.size() + align16(img.size() * sizeof(unsigned long long))));
+    FRPCHK(ensure(h, h->jenc_in, base_bytes + hist_bytes + (hist ? img.size() * sizeof(JpegEncTables) : 0)));
     FRPCHK(ensure(h, h->jenc_coef, (size_t)p.n_blocks * 64 * sizeof(int16_t)));
     uint8_t* in = (uint8_t*)h->jenc_in.p;
     p.img = (const JpegEncImage*)in;
     p.tab = (const JpegEncTables*)(in + img_bytes);
+    p.tab_stride = 0;
+    p.hist = hist ? (uint32_t*)(in + base_bytes) : nullptr;
     p.scan_base = (const unsigned long long*)(in + img_bytes + tab_bytes);
     p.coef = (int16_t*)h->jenc_coef.p;
     HIPCHK(h, hipMemcpyAsync(h->jenc_in.p, up.data(), up.size(), hipMemcpyHostToDevice, h->stream));
@@ -209,13 +317,54 @@ int drain(frp_handle* h, int rc) {
     return rc;
 }
 
-// the planned images (p.frames / p.total_bytes: their buffer) -> the files in out; waits
-int files(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality, uint8_t* out, int64_t out_cap,
-          int64_t* offsets) {
+// behind the forward half (queued with room for them: forward(..., hist = true)): the images' symbol counts -> counts [n][JE_HIST_BINS]; waits
+int histograms(frp_handle* h, const std::string& w, JpegEncParams& p, std::vector<uint32_t>& counts) {
+    counts.assign((size_t)p.n * JE_HIST_BINS, 0);
+    hipError_t e = hipMemsetAsync(p.hist, 0, counts.size() * sizeof(uint32_t), h->stream);
+    if (e == hipSuccess) e = launch_jpeg_enc_hist(p, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), p.hist, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, FRP_ERR_HIP, w + " histograms: " + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, w + " histograms sync: " + hipGetErrorString(e2));
+    return FRP_OK;
+}
+
+// a count is at most 63 per block (ZRL and the AC symbols of a block together): it has to fit uint32
+int check_hist_range(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& img, const JpegEncParams& p) {
+    for (size_t i = 0; i < img.size(); ++i)
+        if ((unsigned long long)img[i].mx * img[i].my * (p.hs * p.vs + 2) * 63ull > 0xFFFFFFFFull)
+            return fail(h, FRP_ERR_INVALID, w + ": image " + std::to_string(i) + " has too many blocks for 32-bit symbol counts");
+    return FRP_OK;
+}
+
+// the planned images (p.frames / p.total_bytes: their buffer) -> the files in out; waits.  optimize: every image with Huffman tables
+// of its own - histogram kernel, one more copy and wait, the tables made here and uploaded, then the same entropy stage
+int files(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality, bool optimize, uint8_t* out,
+          int64_t out_cap, int64_t* offsets) {
     std::vector<uint8_t> up;
     const int32_t n = p.n;
     const int restart_mcus = p.ri;
-    FRPCHK(forward(h, img, quality, p, up));
+    if (optimize) FRPCHK(check_hist_range(h, w, img, p));
+    FRPCHK(forward(h, img, quality, p, up, optimize));
+    std::vector<HuffSet> huff;                              // per image (optimize); empty: Annex K's for all
+    std::vector<JpegEncTables> tabs;                        // (read by the upload until the next wait)
+    if (optimize) {
+        std::vector<uint32_t> counts;
+        const int hrc = histograms(h, w, p, counts);
+        if (hrc != FRP_OK) return drain(h, hrc);
+        huff.resize((size_t)n);
+        tabs.resize((size_t)n);
+        for (int32_t i = 0; i < n; ++i) {
+            if (!optimal_set(counts.data() + (size_t)i * JE_HIST_BINS, huff[(size_t)i]))
+                return drain(h, fail(h, FRP_ERR_HIP, w + ": implausible symbol counts for image " + std::to_string(i)));
+            build_tables(quality, huff[(size_t)i], tabs[(size_t)i]);
+        }
+        JpegEncTables* dev = (JpegEncTables*)(p.hist + align16((size_t)n * JE_HIST_BINS * sizeof(uint32_t)) / sizeof(uint32_t));
+        hipError_t e = hipMemcpyAsync(dev, tabs.data(), tabs.size() * sizeof(JpegEncTables), hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, w + " tables: " + hipGetErrorString(e)));
+        p.tab = dev;
+        p.tab_stride = 1;
+    }
     // the work arrays of the entropy half, carved out of one allocation
     const size_t nb = (size_t)p.n_blocks, ni = (size_t)p.n_int;
     const size_t groups = jpeg_enc_scan_groups((long long)std::max(nb, ni)) + 64;      // (the 0xFF chunks are fewer than the blocks: see n_words)
@@ -223,7 +372,8 @@ int files(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& 
     auto carve = [&](size_t bytes) { const size_t at = off; off += align16(bytes); return at; };
     const size_t o_bits = carve(nb * 4), o_pre = carve((nb + 1) * 8), o_grp = carve(groups * 8), o_iw = carve((ni + 1) * 8), o_ib = carve(ni * 4),
                  o_if = carve(ni * 8), o_io = carve(ni * 4), o_ip = carve((ni + 1) * 8), o_img = carve(((size_t)n + 1) * 8);
-    FRPCHK(ensure(h, h->jenc_work, off));
+    int rc = ensure(h, h->jenc_work, off);
+    if (rc != FRP_OK) return drain(h, rc);                  // (the uploads above read this frame's vectors)
     uint8_t* wk = (uint8_t*)h->jenc_work.p;
     p.blk_bits = (uint32_t*)(wk + o_bits);
     p.bit_prefix = (unsigned long long*)(wk + o_pre);
@@ -240,14 +390,16 @@ int files(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& 
     if (e == hipSuccess) e = hipMemcpyAsync(&total_bits, p.bit_prefix + nb, sizeof(total_bits), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return drain(h, fail(h, FRP_ERR_HIP, w + " measure: " + hipGetErrorString(e)));
-    // a block codes at most 20 + 63 * 26 bits: anything beyond that is not a size
-    if (total_bits > (unsigned long long)nb * 1658ull) return drain(h, fail(h, FRP_ERR_HIP, w + ": implausible bit count"));
+    // a block codes at most 20 + 63 * 26 bits with Annex K's tables (a DC code of 9 bits + 11 magnitude bits; per AC coefficient a
+    // code of 16 + 10 - a ZRL covers 16 coefficients with at most 16 bits), 27 + 63 * 26 with tables whose DC codes may take 16 bits:
+    // anything beyond that is not a size
+    if (total_bits > (unsigned long long)nb * (optimize ? 1665ull : 1658ull)) return drain(h, fail(h, FRP_ERR_HIP, w + ": implausible bit count"));
     // 2. the stream in words (every interval starts on a word of its own), 0xFF counts per chunk, the intervals' places
     p.n_words = (total_bits >> 5) + ni + 1;
     p.n_chunks = (long long)((p.n_words + JE_CHUNK_WORDS - 1) / JE_CHUNK_WORDS);
     if (jpeg_enc_scan_groups(p.n_chunks) > groups) return drain(h, fail(h, FRP_ERR_INVALID, w + ": stream too long"));
     const size_t words_bytes = align16((size_t)p.n_words * 4), chunk_bytes = align16((size_t)p.n_chunks * 4);
-    int rc = ensure(h, h->jenc_bits, words_bytes + chunk_bytes + align16(((size_t)p.n_chunks + 1) * 8));
+    rc = ensure(h, h->jenc_bits, words_bytes + chunk_bytes + align16(((size_t)p.n_chunks + 1) * 8));
     if (rc != FRP_OK) return drain(h, rc);
     uint8_t* bw = (uint8_t*)h->jenc_bits.p;
     p.words = (uint32_t*)bw;
@@ -264,7 +416,8 @@ int files(frp_handle* h, const std::string& w, const std::vector<JpegEncImage>& 
     std::vector<unsigned long long> scan_base((size_t)n);
     int64_t at = 0;
     for (int32_t i = 0; i < n; ++i) {
-        hdr[(size_t)i] = headers(img[(size_t)i].w, img[(size_t)i].h, quality, p.hs, p.vs, restart_mcus);
+        hdr[(size_t)i] = optimize ? headers(img[(size_t)i].w, img[(size_t)i].h, quality, p.hs, p.vs, restart_mcus, huff[(size_t)i])
+                                  : headers(img[(size_t)i].w, img[(size_t)i].h, quality, p.hs, p.vs, restart_mcus);
         const unsigned long long scan = scan_off[(size_t)i + 1] - scan_off[(size_t)i];
         // stuffing at most doubles a stream, and every interval adds a marker: anything beyond that is not a size
         if (scan_off[(size_t)i + 1] < scan_off[(size_t)i] || scan > 2ull * ((total_bits >> 3) + 4ull * ni) + 16)
@@ -299,14 +452,14 @@ int encode(frp_handle* h, const int32_t* rects, int32_t n, int quality, int subs
            int64_t out_cap, int64_t* offsets) {
     std::vector<JpegEncImage> img;
     JpegEncParams p;
-    FRPCHK(plan(h, "encode_jpeg", rects, n, quality, subsampling, restart_mcus, flags, img, p));
+    FRPCHK(plan(h, "encode_jpeg", rects, n, quality, subsampling, restart_mcus, flags, FRP_FLAG_RGB | FRP_FLAG_JPEG_OPTIMIZE, img, p));
     if (out_cap < 0) return fail(h, FRP_ERR_INVALID, "encode_jpeg: out_cap < 0");
     if (!offsets) return fail(h, FRP_ERR_INVALID, "encode_jpeg: null offsets");
     if (n == 0) {
         offsets[0] = 0;
         return FRP_OK;
     }
-    return files(h, "encode_jpeg", img, p, quality, out, out_cap, offsets);
+    return files(h, "encode_jpeg", img, p, quality, (flags & FRP_FLAG_JPEG_OPTIMIZE) != 0, out, out_cap, offsets);
 }
 
 }  // namespace
@@ -331,9 +484,9 @@ int jpeg_enc_plan_buffer(frp_handle* h, const std::string& who, const JpegEncSou
     return layout(h, who, src, n, hs, vs, restart_mcus, flags, img, p);
 }
 
-int jpeg_enc_files(frp_handle* h, const std::string& who, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality, uint8_t* out,
-                   int64_t out_cap, int64_t* offsets) {
-    return files(h, who, img, p, quality, out, out_cap, offsets);
+int jpeg_enc_files(frp_handle* h, const std::string& who, const std::vector<JpegEncImage>& img, JpegEncParams& p, int quality, bool optimize,
+                   uint8_t* out, int64_t out_cap, int64_t* offsets) {
+    return files(h, who, img, p, quality, optimize, out, out_cap, offsets);
 }
 
 }  // namespace frp
@@ -351,6 +504,15 @@ int64_t frp_jpeg_encode_headers(int32_t width, int32_t height, int32_t quality, 
     return (int64_t)b.size();
 }
 
+int frp_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256]) {
+    if (!freq || !bits || !vals) return FRP_ERR_INVALID;
+    HuffSpec s;
+    if (!optimal_table(freq, s)) return FRP_ERR_INVALID;
+    std::memcpy(bits, s.bits, 16);
+    std::memcpy(vals, s.vals, (size_t)s.n);
+    return s.n;
+}
+
 int frp_encode_jpeg(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint32_t flags,
                     uint8_t* out, int64_t out_cap, int64_t* offsets) {
     if (!h) return FRP_ERR_INVALID;
@@ -365,7 +527,7 @@ int frp_encode_jpeg_coefficients(frp_handle* h, const int32_t* rects, int32_t n,
     std::vector<JpegEncImage> img;
     std::vector<uint8_t> up;
     JpegEncParams p;
-    FRPCHK(plan(h, "encode_jpeg_coefficients", rects, n, quality, subsampling, 0, flags, img, p));
+    FRPCHK(plan(h, "encode_jpeg_coefficients", rects, n, quality, subsampling, 0, flags, FRP_FLAG_RGB, img, p));
     if (n == 0) return FRP_OK;
     if (!coef || coef_elems != p.n_blocks * 64)
         return fail(h, FRP_ERR_INVALID, "encode_jpeg_coefficients: the rectangles have " + std::to_string(p.n_blocks * 64) + " coefficients, coef_elems is " +
@@ -376,6 +538,29 @@ int frp_encode_jpeg_coefficients(frp_handle* h, const int32_t* rects, int32_t n,
     if (e != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("encode_jpeg_coefficients: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(h, FRP_ERR_HIP, std::string("encode_jpeg_coefficients sync: ") + hipGetErrorString(e2));
     settle_events(h, true);
+    return FRP_OK;
+}
+
+int frp_encode_jpeg_histograms(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, int32_t restart_mcus,
+                               uint32_t flags, uint32_t* hist, int64_t hist_elems) {
+    if (!h) return FRP_ERR_INVALID;
+    Guard g(h, false);
+    const std::string w("encode_jpeg_histograms");
+    std::vector<JpegEncImage> img;
+    std::vector<uint8_t> up;
+    JpegEncParams p;
+    FRPCHK(plan(h, w.c_str(), rects, n, quality, subsampling, restart_mcus, flags, FRP_FLAG_RGB | FRP_FLAG_JPEG_OPTIMIZE, img, p));
+    if (n == 0) return FRP_OK;
+    if (!hist || hist_elems != (int64_t)n * JE_HIST_BINS)
+        return fail(h, FRP_ERR_INVALID, w + ": " + std::to_string(n) + " images have " + std::to_string((int64_t)n * JE_HIST_BINS) + " counts, hist_elems is " +
+                    std::to_string(hist_elems));
+    FRPCHK(check_hist_range(h, w, img, p));
+    FRPCHK(forward(h, img, quality, p, up, true));
+    std::vector<uint32_t> counts;
+    const int rc = histograms(h, w, p, counts);           // (waits on its error paths too: `up` lives long enough)
+    settle_events(h, true);
+    if (rc != FRP_OK) return rc;
+    std::memcpy(hist, counts.data(), counts.size() * sizeof(uint32_t));
     return FRP_OK;
 }
 

@@ -18,6 +18,9 @@
 //   jpeg_enc_bits_kernel      a wave per block, lane = zig-zag position: __ballot of the non-zero lanes gives every lane its zero run
 //                             (ZRL prefixes for runs >= 16 are part of the lane's code, EOB is lane 63's when coefficient 63 is zero);
 //                             the wave's sum of code lengths -> blk_bits (scan order)
+//   jpeg_enc_hist_kernel      (FRP_FLAG_JPEG_OPTIMIZE only, in front of the others) the same lanes, counting the symbols instead of
+//                             coding them: per image dc [2][16] + ac [2][256], from which the host makes the image's own tables
+//                             (tab[i * tab_stride]: Annex K's for every image, or one set per image)
 //   prefix sum 1              bit_prefix over all blocks of the call; an interval's bits are a difference of two entries
 //   jpeg_enc_intervals_kernel each interval gets words [int_word, ...) of the unstuffed stream: (bits before it >> 5) + its index, which
 //                             leaves every interval its own words without a second scan (intervals start on a word)
@@ -221,36 +224,60 @@ __device__ inline JeBlock je_scan_block(const JpegEncParams& p, const JpegEncIma
     return b;
 }
 
-// the code of this lane's zig-zag position (right-aligned in `code`, `len` bits, at most 3 * 11 + 16 + 10 = 59); 0 bits for a zero
-// coefficient that is not the end of the block
-__device__ inline void je_lane_code(const JpegEncParams& p, const JpegEncImage& I, const JeBlock& b, int lane, u64& code, int& len) {
+// What this lane's zig-zag position contributes to the scan - the ONE definition of the symbols, for the kernels that code them
+// (je_lane_code) and the one that counts them (jpeg_enc_hist_kernel).  Called by whole waves (__ballot).
+enum { JE_NONE = 0, JE_DC, JE_AC, JE_EOB };      // a zero coefficient inside the block | lane 0 | a non-zero AC | lane 63 when it is zero
+struct JeSymbol {
+    int kind;
+    int tb;            // table: 0 luminance, 1 chrominance
+    int v;             // the coefficient (lane 0: the DC difference)
+    int size;          // its magnitude category: the DC symbol, the low nibble of the AC symbol
+    int run;           // JE_AC: zeros since the last non-zero AC; run >> 4 ZRL symbols precede the symbol (run & 15) << 4 | size
+};
+__device__ inline JeSymbol je_lane_symbol(const JpegEncParams& p, const JpegEncImage& I, const JeBlock& b, int lane) {
     const int16_t* c = p.coef + (I.blk0 + b.nat) * 64;
-    int v = c[je_zigzag[lane]];
-    if (lane == 0 && b.prev >= 0) v -= p.coef[(I.blk0 + b.prev) * 64];
-    const u64 nz = __ballot(v != 0) & ~1ull;                 // non-zero AC positions
-    const int tb = b.comp ? 1 : 0;
-    const unsigned a = (unsigned)(v < 0 ? -v : v);
-    const int size = a ? 32 - __clz(a) : 0;
-    const u64 vbits = (u64)((unsigned)(v > 0 ? v : v - 1) & ((1u << size) - 1u));
-    code = 0;
-    len = 0;
-    if (lane == 0) {
-        const uint32_t e = p.tab->dc[tb][size & 15];
-        code = ((u64)(e & 0xffffu) << size) | vbits;
-        len = (int)(e >> 16) + size;
-    } else if (v != 0) {
+    JeSymbol s;
+    s.v = c[je_zigzag[lane]];
+    if (lane == 0 && b.prev >= 0) s.v -= p.coef[(I.blk0 + b.prev) * 64];
+    const u64 nz = __ballot(s.v != 0) & ~1ull;                // non-zero AC positions
+    s.tb = b.comp ? 1 : 0;
+    const unsigned a = (unsigned)(s.v < 0 ? -s.v : s.v);
+    s.size = a ? 32 - __clz(a) : 0;
+    s.run = 0;
+    if (lane == 0) s.kind = JE_DC;
+    else if (s.v != 0) {
         const u64 below = nz & ((1ull << lane) - 1ull);
         const int prevpos = below ? 63 - __clzll((long long)below) : 0;
-        const int run = lane - prevpos - 1;
-        const uint32_t zrl = p.tab->ac[tb][0xF0], e = p.tab->ac[tb][((run & 15) << 4) | (size & 15)];
-        for (int i = 0; i < (run >> 4); ++i) {
-            code = (code << (zrl >> 16)) | (zrl & 0xffffu);
-            len += (int)(zrl >> 16);
+        s.run = lane - prevpos - 1;
+        s.kind = JE_AC;
+    } else s.kind = lane == 63 ? JE_EOB : JE_NONE;
+    return s;
+}
+
+// the code of this lane's zig-zag position with the image's tables T: `pre` (prelen bits: the ZRL codes of a run >= 16, at most
+// 3 * 16) in front of `code` (len bits: Huffman code + magnitude bits, at most 16 + 11), both right-aligned; 0 bits for a zero
+// coefficient that is not the end of the block.  (Two parts: with Annex K's 11-bit ZRL a lane's bits fit 64, with a table of the
+// image's own, where ZRL may take 16, they need not.)
+__device__ inline void je_lane_code(const JpegEncTables& T, const JeSymbol& s, u64& pre, int& prelen, u64& code, int& len) {
+    const u64 vbits = (u64)((unsigned)(s.v > 0 ? s.v : s.v - 1) & ((1u << s.size) - 1u));
+    pre = 0;
+    prelen = 0;
+    code = 0;
+    len = 0;
+    if (s.kind == JE_DC) {
+        const uint32_t e = T.dc[s.tb][s.size & 15];
+        code = ((u64)(e & 0xffffu) << s.size) | vbits;
+        len = (int)(e >> 16) + s.size;
+    } else if (s.kind == JE_AC) {
+        const uint32_t zrl = T.ac[s.tb][0xF0], e = T.ac[s.tb][((s.run & 15) << 4) | (s.size & 15)];
+        for (int i = 0; i < (s.run >> 4); ++i) {
+            pre = (pre << (zrl >> 16)) | (zrl & 0xffffu);
+            prelen += (int)(zrl >> 16);
         }
-        code = (((code << (e >> 16)) | (e & 0xffffu)) << size) | vbits;
-        len += (int)(e >> 16) + size;
-    } else if (lane == 63) {                                  // end of block
-        const uint32_t e = p.tab->ac[tb][0];
+        code = ((u64)(e & 0xffffu) << s.size) | vbits;
+        len = (int)(e >> 16) + s.size;
+    } else if (s.kind == JE_EOB) {
+        const uint32_t e = T.ac[s.tb][0];
         code = e & 0xffffu;
         len = (int)(e >> 16);
     }
@@ -269,13 +296,54 @@ __global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(JpegEncParams p) {
     const int lane = threadIdx.x & 63;
     const long long S = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (S >= p.n_blocks) return;                              // (whole waves leave: S is uniform in a wave)
-    const JpegEncImage I = p.img[je_image_of_block(p, S)];
+    const int im = je_image_of_block(p, S);
+    const JpegEncImage I = p.img[im];
     const JeBlock b = je_scan_block(p, I, S - I.blk0);
-    u64 code;
-    int len;
-    je_lane_code(p, I, b, lane, code, len);
-    const int tot = je_wave_inclusive(len, lane);
+    u64 pre, code;
+    int prelen, len;
+    je_lane_code(p.tab[(size_t)im * p.tab_stride], je_lane_symbol(p, I, b, lane), pre, prelen, code, len);
+    const int tot = je_wave_inclusive(prelen + len, lane);
     if (lane == 63) p.blk_bits[S] = (uint32_t)tot;
+}
+
+// The symbol counts of every image (FRP_FLAG_JPEG_OPTIMIZE): the index space of jpeg_enc_bits_kernel, JE_HIST_WG_BLOCKS consecutive
+// blocks per workgroup, a wave per block, lane = zig-zag position.  Counts gather in LDS - the EOB and 0x01 bins are hit by nearly
+// every block - and the non-zero bins go to the image's histogram with one vector atomic each.  The blocks of all images form one
+// index space, so a workgroup may span images (a small crop is 3 or 6 blocks): it works image by image and flushes and clears at
+// every boundary.  Integer adds: the result does not depend on the order.
+#define JE_HIST_WG_BLOCKS 256
+__global__ __launch_bounds__(256) void jpeg_enc_hist_kernel(JpegEncParams p) {
+    __shared__ uint32_t h[JE_HIST_BINS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long g0 = (long long)blockIdx.x * JE_HIST_WG_BLOCKS, g1 = min(g0 + JE_HIST_WG_BLOCKS, p.n_blocks);
+    for (int i = threadIdx.x; i < JE_HIST_BINS; i += 256) h[i] = 0;
+    __syncthreads();
+    if (g0 >= g1) return;                                     // (never: the grid covers n_blocks)
+    int im = je_image_of_block(p, g0);
+    long long s = g0;
+    while (s < g1 && im < p.n) {                              // (uniform in the workgroup: the barriers below are met by all)
+        const JpegEncImage I = p.img[im];
+        const long long end = im + 1 < p.n ? min(g1, p.img[im + 1].blk0) : g1;
+        for (long long S = s + wv; S < end; S += 4) {         // (S is uniform in a wave)
+            const JeSymbol y = je_lane_symbol(p, I, je_scan_block(p, I, S - I.blk0), lane);
+            if (y.kind == JE_DC) atomicAdd(&h[y.tb * 16 + (y.size & 15)], 1u);
+            else if (y.kind == JE_AC) {
+                atomicAdd(&h[32 + y.tb * 256 + (((y.run & 15) << 4) | (y.size & 15))], 1u);
+                if (y.run >> 4) atomicAdd(&h[32 + y.tb * 256 + 0xF0], (uint32_t)(y.run >> 4));
+            } else if (y.kind == JE_EOB) atomicAdd(&h[32 + y.tb * 256], 1u);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < JE_HIST_BINS; i += 256) {
+            const uint32_t c = h[i];
+            if (c) {
+                atomicAdd(p.hist + (size_t)im * JE_HIST_BINS + i, c);
+                h[i] = 0;
+            }
+        }
+        __syncthreads();
+        s = end;
+        ++im;
+    }
 }
 
 // `len` bits of code at bit `bit` of the stream that starts at word w0
@@ -319,17 +387,19 @@ __global__ __launch_bounds__(256) void jpeg_enc_pack_kernel(JpegEncParams p) {
     const int lane = threadIdx.x & 63;
     const long long S = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (S >= p.n_blocks) return;
-    const JpegEncImage I = p.img[je_image_of_block(p, S)];
+    const int im = je_image_of_block(p, S);
+    const JpegEncImage I = p.img[im];
     const JeBlock b = je_scan_block(p, I, S - I.blk0);
-    u64 code;
-    int len;
-    je_lane_code(p, I, b, lane, code, len);
-    const int incl = je_wave_inclusive(len, lane);
+    u64 pre, code;
+    int prelen, len;
+    je_lane_code(p.tab[(size_t)im * p.tab_stride], je_lane_symbol(p, I, b, lane), pre, prelen, code, len);
+    const int incl = je_wave_inclusive(prelen + len, lane);
     const long long t = p.ri ? b.mcu / p.ri : 0;
     long long s0, s1;
     je_interval_blocks(p, I, t, s0, s1);
     const u64 w0 = p.int_word[I.int0 + t];
     const u64 at = p.bit_prefix[S] - p.bit_prefix[s0];        // of the block inside its interval
+    if (prelen) je_put(p, w0, at + (u64)(incl - prelen - len), pre, prelen);
     if (len) je_put(p, w0, at + (u64)(incl - len), code, len);
     if (lane == 63 && S + 1 == s1) {                          // the interval ends here: 1-bits up to the byte
         const u64 end = at + (u64)incl;
@@ -506,7 +576,8 @@ static hipError_t je_prefix_sum(const uint32_t* in, long long n, u64* out, u64* 
 
 // ----------------------------------------------------------------------------------------------------------------- launchers
 static bool je_common_ok(const JpegEncParams& p) {
-    return p.frames && p.img && p.tab && p.coef && p.n > 0 && p.n_blocks > 0 && p.n_blocks < (1LL << 31) && p.total_bytes > 0 && ((p.hs == 2 && p.vs == 2) || (p.hs == 1 && p.vs == 1)) && p.ri >= 0;
+    return p.frames && p.img && p.tab && p.coef && p.n > 0 && p.n_blocks > 0 && p.n_blocks < (1LL << 31) && p.total_bytes > 0 && ((p.hs == 2 && p.vs == 2) || (p.hs == 1 && p.vs == 1)) && p.ri >= 0 &&
+           (p.tab_stride == 0 || p.tab_stride == 1);
 }
 static bool je_entropy_ok(const JpegEncParams& p) {
     return je_common_ok(p) && p.n_int >= p.n && p.n_int < (1LL << 31) && p.blk_bits && p.bit_prefix && p.group_tot && p.int_word && p.int_bytes &&
@@ -516,6 +587,12 @@ static bool je_entropy_ok(const JpegEncParams& p) {
 hipError_t launch_jpeg_enc_forward(const JpegEncParams& p, hipStream_t stream) {
     if (!je_common_ok(p)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(jpeg_enc_forward_kernel, dim3((unsigned)((p.n_blocks + JE_BLOCKS - 1) / JE_BLOCKS)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_jpeg_enc_hist(const JpegEncParams& p, hipStream_t stream) {
+    if (!je_common_ok(p) || !p.hist) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jpeg_enc_hist_kernel, dim3((unsigned)((p.n_blocks + JE_HIST_WG_BLOCKS - 1) / JE_HIST_WG_BLOCKS)), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -513,59 +513,63 @@ class FaceService:
 
     # ------------------------------------------------------------------ pictures back out (routes/camera.py:73-87,148-149)
     @staticmethod
-    def _encode_enhanced(eng, rects, quality: int) -> List[bytes]:
+    def _encode_enhanced(eng, rects, quality: int, optimize: bool = False) -> List[bytes]:
         """services/enhancer.py:64-92 for rectangles of the resident frames, on the device: each upscaled with BICUBIC to
         enhanced_size of its own size - only when that is larger (enhancer.py:80) - then UnsharpMask(1, 120, 3) when ENHANCER_SHARPEN
-        says so, then JPEG.  (Annex K Huffman tables: Pillow's save(quality=q), not the optimize=True the reference adds.)"""
+        says so, then JPEG.  optimize=False: Annex K Huffman tables, Pillow's save(quality=q); optimize=True: tables of the image's
+        own, Pillow's save(quality=q, optimize=True) - the file the reference writes (enhancer.py:88)."""
         upscale, max_pixels, _, sharpen = enhancer_settings()
         sizes = []
         for _, top, right, bottom, left in rects:
             w, h = right - left, bottom - top
             new_w, new_h = enhanced_size(w, h, upscale, max_pixels)
             sizes.append((new_w, new_h) if new_w > w or new_h > h else (w, h))
-        return eng.encode_jpeg_enhanced(rects, sizes, radius=1, percent=120, threshold=3, sharpen=sharpen, quality=quality)
+        return eng.encode_jpeg_enhanced(rects, sizes, radius=1, percent=120, threshold=3, sharpen=sharpen, quality=quality, optimize=optimize)
 
-    def snapshot_jpeg(self, frame: int = 0, quality: int = 95, enhance: bool = False) -> Optional[bytes]:
+    def snapshot_jpeg(self, frame: int = 0, quality: int = 95, enhance: bool = False, optimize: bool = False) -> Optional[bytes]:
         """the /snapshot route's cv2.imencode('.jpg', frame, [IMWRITE_JPEG_QUALITY, q]) for a frame that is RESIDENT on the engine
         (BGR, as the camera loop uploads it), encoded on the device.  enhance: the route's enhance=true branch (routes/snapshot.py:54-117)
         in front of the encoder - upscaled and sharpened as ENHANCER_UPSCALE_FACTOR / _MAX_PIXELS / _SHARPEN say, on the device too.
+        optimize: Huffman tables of the image's own, PIL's save(optimize=True) - a smaller file for one more wait on the device.
         None, and a log line, when it cannot be encoded."""
         try:
             eng = self._eng()
             with self._sequence_of(eng):
                 _, H, W = eng.resident_shape
                 rects = [(int(frame), 0, W, H, 0)]
-                return (self._encode_enhanced(eng, rects, quality) if enhance else eng.encode_jpeg(rects, quality=quality))[0]
+                return (self._encode_enhanced(eng, rects, quality, optimize) if enhance else eng.encode_jpeg(rects, quality=quality, optimize=optimize))[0]
         except Exception as e:
             logger.exception("Error encoding snapshot of frame %s: %s", frame, e)
             return None
 
-    def enhance_snapshot(self, frame: int = 0) -> Optional[bytes]:
-        """services/enhancer.py's enhance_snapshot for a resident frame: snapshot_jpeg(enhance=True) at ENHANCER_JPEG_QUALITY"""
+    def enhance_snapshot(self, frame: int = 0, optimize: bool = False) -> Optional[bytes]:
+        """services/enhancer.py's enhance_snapshot for a resident frame: snapshot_jpeg(enhance=True) at ENHANCER_JPEG_QUALITY.
+        enhance_snapshot(frame, optimize=True) is the reference's file byte for byte (it saves with optimize=True, enhancer.py:88);
+        the default writes the same pixels with the Annex K tables."""
         try:
             quality = enhancer_settings()[2]
         except Exception as e:
             logger.exception("Error reading the enhancer's settings: %s", e)
             return None
-        return self.snapshot_jpeg(frame, quality=quality, enhance=True)
+        return self.snapshot_jpeg(frame, quality=quality, enhance=True, optimize=optimize)
 
-    def encode_frames(self, quality: int = 95) -> List[bytes]:
+    def encode_frames(self, quality: int = 95, optimize: bool = False) -> List[bytes]:
         """every resident frame as a JPEG (gen_frames_from_cap's cv2.imencode per frame; mjpeg.multipart_part frames one for /feed),
-        in one device call.  [] and a log line on failure."""
+        in one device call.  optimize: as in snapshot_jpeg.  [] and a log line on failure."""
         try:
             eng = self._eng()
             with self._sequence_of(eng):
                 B, H, W = eng.resident_shape
-                return eng.encode_jpeg([(b, 0, W, H, 0) for b in range(B)], quality=quality)
+                return eng.encode_jpeg([(b, 0, W, H, 0) for b in range(B)], quality=quality, optimize=optimize)
         except Exception as e:
             logger.exception("Error encoding the resident frames: %s", e)
             return []
 
     def face_thumbnails(self, faces: List[Tuple[int, Tuple[int, int, int, int]]], margin: float = 0.0, quality: int = 95,
-                        enhance: bool = False) -> List[bytes]:
+                        enhance: bool = False, optimize: bool = False) -> List[bytes]:
         """JPEG crops of `faces` = [(frame index, (top, right, bottom, left))] out of the resident frames, each grown by `margin`
         times its height / width on every side and clipped to the frame; one device call.  enhance: every crop through the
-        enhancer first, as in snapshot_jpeg.  [] and a log line on failure (a face that clipping leaves empty is one)."""
+        enhancer first, optimize: tables of every crop's own, both as in snapshot_jpeg.  [] and a log line on failure (a face that clipping leaves empty is one)."""
         try:
             eng = self._eng()
             with self._sequence_of(eng):
@@ -576,7 +580,7 @@ class FaceService:
                     rects.append((int(b), max(0, int(top) - dy), min(W, int(right) + dx), min(H, int(bottom) + dy), max(0, int(left) - dx)))
                 if not rects:
                     return []
-                return self._encode_enhanced(eng, rects, quality) if enhance else eng.encode_jpeg(rects, quality=quality)
+                return self._encode_enhanced(eng, rects, quality, optimize) if enhance else eng.encode_jpeg(rects, quality=quality, optimize=optimize)
         except Exception as e:
             logger.exception("Error encoding face thumbnails: %s", e)
             return []

@@ -25,6 +25,8 @@ CHIP = 112
 MAX_FACES_CAP = 128
 MAX_TOPK = 64
 FLAG_FORCED_K, FLAG_RGB, FLAG_NO_MATCH, FLAG_WITHIN, FLAG_GROUPS, FLAG_TRACK = 1, 2, 4, 8, 16, 32
+FLAG_JPEG_OPTIMIZE = 64                      # include/frp.h: FRP_FLAG_JPEG_OPTIMIZE - encode_jpeg / encode_jpeg_enhanced(optimize=True)
+JPEG_HIST_ELEMS = 544                        # include/frp.h: FRP_JPEG_HIST_ELEMS - per image dc [2][16], then ac [2][256]
 GROUPS_ALL = 0xFFFFFFFF                      # include/frp.h: FRP_GROUPS_ALL - the mask of a gallery row that arrived without one
 F32, F16, F64 = 0, 1, 2
 JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}      # include/frp.h: FRP_JPEG_420, FRP_JPEG_444
@@ -48,7 +50,7 @@ ABI_SYMBOLS = [
     "frp_detect", "frp_detect_resident", "frp_get_det_source", "frp_finish_faces", "frp_process_pyramid", "frp_debug_pyramid_merge", "frp_debug_fc_l2norm", "frp_get_head_map", "frp_debug_det_prefix", "frp_debug_det_hashes", "frp_decode_heads", "frp_align", "frp_debug_align_resident", "frp_embed_aligned", "frp_embed_faces",
     "frp_match", "frp_match_scores", "frp_debug_match_f16", "frp_match_within", "frp_set_within", "frp_fetch_within", "frp_match_groups", "frp_match_within_groups", "frp_set_frame_groups",
     "frp_track_config", "frp_set_frame_streams", "frp_track_reset", "frp_fetch_tracks", "frp_track_stats", "frp_debug_track_step",
-    "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_enhance_pixels", "frp_encode_jpeg_enhanced", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
+    "frp_face_quality", "frp_jpeg_encode_headers", "frp_encode_jpeg", "frp_encode_jpeg_coefficients", "frp_jpeg_optimal_table", "frp_encode_jpeg_histograms", "frp_enhance_pixels", "frp_encode_jpeg_enhanced", "frp_conv2d_nhwc", "frp_conv_block64", "frp_conv2d_f8", "frp_get_counters", "frp_reset_counters", "frp_set_profile",
 ]
 
 
@@ -145,6 +147,20 @@ def jpeg_encode_headers(width: int, height: int, quality: int = 95, subsampling:
     if n < 0:
         raise FrpError(int(n), "jpeg_encode_headers: argument out of range")
     return buf[:n].tobytes()
+
+
+def jpeg_optimal_table(freq):
+    """libjpeg's jpeg_gen_optimal_table: the counts of the 256 symbols -> (bits [16]: codes of length 1..16, vals: the symbols by
+    code length, then by value) of the length-limited Huffman code, as a DHT segment carries them: include/frp.h
+    frp_jpeg_optimal_table.  Needs no GPU."""
+    f = np.ascontiguousarray(freq, dtype=np.uint32).reshape(-1)
+    if f.size != 256:
+        raise ValueError(f"{f.size} counts, 256 expected")
+    bits, vals = np.zeros(16, np.uint8), np.zeros(256, np.uint8)
+    n = load_library().frp_jpeg_optimal_table(_ptr(f), _ptr(bits), _ptr(vals))
+    if n < 0:
+        raise FrpError(int(n), "jpeg_optimal_table: all counts are zero, or the code is deeper than 32 bits")
+    return bits.tolist(), vals[:n].tolist()
 
 
 class FrpError(RuntimeError):
@@ -279,6 +295,9 @@ def load_library() -> C.CDLL:
         lib.frp_jpeg_encode_headers.restype = i64
         lib.frp_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, u32, vp, i64, vp]
         lib.frp_encode_jpeg_coefficients.argtypes = [vp, vp, i32, i32, i32, u32, vp, i64]
+    if hasattr(lib, "frp_jpeg_optimal_table"):   # (as above)
+        lib.frp_jpeg_optimal_table.argtypes = [vp, vp, vp]
+        lib.frp_encode_jpeg_histograms.argtypes = [vp, vp, i32, i32, i32, i32, u32, vp, i64]
     if hasattr(lib, "frp_enhance_pixels"):   # (as above)
         lib.frp_enhance_pixels.argtypes = [vp, vp, vp, i32, C.POINTER(FrpEnhanceParams), u32, vp, i64, vp]
         lib.frp_encode_jpeg_enhanced.argtypes = [vp, vp, vp, i32, C.POINTER(FrpEnhanceParams), i32, i32, i32, u32, vp, i64, vp]
@@ -1001,10 +1020,13 @@ class Engine:
         self._chk(self._lib.frp_face_quality(self._h, _ptr(r), r.shape[0], FLAG_RGB if rgb else 0, _ptr(sums)))
         return sums
 
-    def encode_jpeg(self, rects, quality: int = 95, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False):
+    def encode_jpeg(self, rects, quality: int = 95, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False, optimize: bool = False):
         """baseline JPEG files of rectangles (frame, top, right, bottom, left) of the RESIDENT frames, as uploaded (rgb: their channel
         order) -> list[bytes], one complete file per rectangle, byte for byte what libjpeg (PIL, cv2.imencode) writes for those pixels
-        (frp.h: frp_encode_jpeg).  The first call guesses the size; a second one with the reported size follows when it was too small."""
+        (frp.h: frp_encode_jpeg).  optimize: Huffman tables of every image's own (FLAG_JPEG_OPTIMIZE) - PIL's save(optimize=True),
+        smaller files, one more wait inside the call.  The first call guesses the size; a second one with the reported size follows
+        when it was too small."""
+        flags = (FLAG_RGB if rgb else 0) | (FLAG_JPEG_OPTIMIZE if optimize else 0)
         r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 5)
         n = r.shape[0]
         offsets = np.zeros(n + 1, np.int64)
@@ -1013,7 +1035,7 @@ class Engine:
         for _ in range(2):
             out = np.empty(cap, np.uint8)
             rc = self._lib.frp_encode_jpeg(self._h, _ptr(r), n, int(quality), _subsampling_code(subsampling), int(restart_mcus),
-                                           FLAG_RGB if rgb else 0, _ptr(out), cap, _ptr(offsets))
+                                           flags, _ptr(out), cap, _ptr(offsets))
             if rc == 0 or offsets[n] <= cap:
                 break
             cap = int(offsets[n])
@@ -1042,10 +1064,12 @@ class Engine:
         return [out[offsets[i]:offsets[i + 1]].reshape(int(sz[i, 1]), int(sz[i, 0]), 3).copy() for i in range(n)]
 
     def encode_jpeg_enhanced(self, rects, sizes, radius: float = 1.0, percent: int = 120, threshold: int = 3, sharpen: bool = True,
-                             quality: int = 85, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False):
+                             quality: int = 85, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False, optimize: bool = False):
         """the images of enhance_pixels as baseline JPEG files -> list[bytes], byte for byte Pillow's save(quality=quality) of the
-        enhanced image (frp.h: frp_encode_jpeg_enhanced): enhancer and encoder run back to back on the device.  The first call
-        guesses the size; a second one with the reported size follows when it was too small."""
+        enhanced image - with optimize its save(quality=quality, optimize=True), the file the reference writes (frp.h:
+        frp_encode_jpeg_enhanced): enhancer and encoder run back to back on the device.  The first call guesses the size; a second
+        one with the reported size follows when it was too small."""
+        flags = (FLAG_RGB if rgb else 0) | (FLAG_JPEG_OPTIMIZE if optimize else 0)
         r, sz, prm = self._enhance_args(rects, sizes, radius, percent, threshold, sharpen)
         n = r.shape[0]
         offsets = np.zeros(n + 1, np.int64)
@@ -1054,7 +1078,7 @@ class Engine:
         for _ in range(2):
             out = np.empty(cap, np.uint8)
             rc = self._lib.frp_encode_jpeg_enhanced(self._h, _ptr(r), _ptr(sz), n, C.byref(prm), int(quality), _subsampling_code(subsampling),
-                                                    int(restart_mcus), FLAG_RGB if rgb else 0, _ptr(out), cap, _ptr(offsets))
+                                                    int(restart_mcus), flags, _ptr(out), cap, _ptr(offsets))
             if rc == 0 or offsets[n] <= cap:
                 break
             cap = int(offsets[n])
@@ -1072,6 +1096,16 @@ class Engine:
         self._chk(self._lib.frp_encode_jpeg_coefficients(self._h, _ptr(r), r.shape[0], int(quality), _subsampling_code(subsampling),
                                                          FLAG_RGB if rgb else 0, _ptr(coef), n))
         return coef
+
+    def encode_jpeg_histograms(self, rects, quality: int = 95, subsampling: str = "4:2:0", restart_mcus: int = 0, rgb: bool = False) -> np.ndarray:
+        """parity: the symbol counts encode_jpeg(optimize=True) makes its tables from (frp.h: frp_encode_jpeg_histograms) - uint32
+        [n, JPEG_HIST_ELEMS]: per image dc [2][16] by magnitude category, then ac [2][256] by run / size symbol; table 1 counts Cb
+        and Cr together"""
+        r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 5)
+        hist = np.zeros((r.shape[0], JPEG_HIST_ELEMS), np.uint32)
+        self._chk(self._lib.frp_encode_jpeg_histograms(self._h, _ptr(r), r.shape[0], int(quality), _subsampling_code(subsampling), int(restart_mcus),
+                                                       FLAG_RGB if rgb else 0, _ptr(hist), hist.size))
+        return hist
 
     def match_scores(self, q: np.ndarray) -> np.ndarray:
         """all cosines [M, N].  The output is sized from gallery_size(); the library re-checks that size under

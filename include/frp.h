@@ -58,7 +58,9 @@ typedef enum frp_dtype { FRP_F32 = 0, FRP_F16 = 1, FRP_F64 = 2 } frp_dtype;
 #define FRP_FLAG_GROUPS 16u    /* the pass matches every face against the rows its FRAME's mask permits (frp_set_frame_groups) */
 #define FRP_FLAG_TRACK 32u     /* face tracks: a detection that continues a track identified before gets the track's cached embedding
                                   and match, only the others are embedded (frp_track_config, frp_set_frame_streams) */
-#define FRP_GROUPS_ALL 0xFFFFFFFFu   /* member of every group: the mask of a row that arrived without one */
+#define FRP_FLAG_JPEG_OPTIMIZE 64u   /* frp_encode_jpeg / frp_encode_jpeg_enhanced only: per-image optimal Huffman tables, the files
+                                        of libjpeg's optimize_coding (Pillow's save(optimize=True)) */
+#define FRP_GROUPS_ALL 0xFFFFFFFFu  /* member of every group: the mask of a row that arrived without one */
 
 typedef struct frp_handle frp_handle;
 
@@ -567,13 +569,32 @@ int frp_face_quality(frp_handle* h, const int32_t* rects, int32_t n, uint32_t fl
  * Needs no handle.  Returns the byte count (<= 1024), or FRP_ERR_INVALID - nothing written - when cap is too small or an argument is
  * out of range (width / height 1..65535, quality 1..100, restart_mcus 0..65535). */
 int64_t frp_jpeg_encode_headers(int32_t width, int32_t height, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint8_t* out, int64_t cap);
+/* libjpeg's jpeg_gen_optimal_table (T.81 K.2 with libjpeg's conventions): the symbol counts freq [256] -> BITS bits [16] (codes of
+ * length 1..16) and HUFFVAL vals [256] (the symbols by code length, then by value; the first `return value` entries are set) of the
+ * length-limited Huffman code a DHT segment carries.  A pseudo-symbol of count 1 keeps every real symbol off the all-ones code; the
+ * two least frequent entries merge, ties going to the larger symbol; lengths beyond 16 are shortened as in Figure K.3.  Needs no
+ * handle.  Returns the number of symbols with a non-zero count, or FRP_ERR_INVALID - nothing written - for a null argument, counts
+ * that are all zero, or a code deeper than 32 bits before limiting (where libjpeg gives up too). */
+int frp_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256]);
 /* rects [n*5] = frame, top, right, bottom, left, validated as in frp_face_quality (the message names the rectangle); pixels are BGR,
- * RGB with FRP_FLAG_RGB (the only flag allowed).  out: the n complete files back to back; offsets [n+1]: offsets[i] = where file i
+ * RGB with FRP_FLAG_RGB.  out: the n complete files back to back; offsets [n+1]: offsets[i] = where file i
  * starts, offsets[n] = the total.  When the total exceeds out_cap: FRP_ERR_INVALID, offsets filled, out untouched - call again with
  * room for offsets[n].  n == 0: FRP_OK, nothing launched.  Any argument out of range: FRP_ERR_INVALID, nothing launched, nothing
- * written.  Queued on the handle's stream behind a pending pass; waits; the handle's last results stay fetchable. */
+ * written.  Queued on the handle's stream behind a pending pass; waits; the handle's last results stay fetchable.
+ * FRP_FLAG_JPEG_OPTIMIZE (the only other flag allowed): every file gets Huffman tables of its own, made from the counts of its own
+ * symbols (a histogram kernel, frp_jpeg_optimal_table on the host, per-image tables in the entropy stage and in the four DHT
+ * segments) - byte for byte Pillow's save(quality=q, optimize=True), one more wait inside the call, everything else as without the
+ * flag.  Pillow cannot write every such file: with optimize its output buffer is max(65536, w*h) bytes (2*w*h at quality >= 95) and
+ * libjpeg cannot suspend ("Suspension not allowed here", e.g. 160 x 160 noise at quality 100, 4:4:4); this encoder has no such limit. */
 int frp_encode_jpeg(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint32_t flags,
                     uint8_t* out, int64_t out_cap, int64_t* offsets);
+/* parity: the symbol counts FRP_FLAG_JPEG_OPTIMIZE builds its tables from - per image FRP_JPEG_HIST_ELEMS counts: dc [2][16] by
+ * magnitude category (table 0: Y, table 1: Cb and Cr together), then ac [2][256] by run / size symbol (0x00 = EOB, 0xF0 = ZRL);
+ * hist_elems must be n * FRP_JPEG_HIST_ELEMS.  flags: FRP_FLAG_RGB; FRP_FLAG_JPEG_OPTIMIZE is accepted and changes nothing.  With
+ * frp_jpeg_optimal_table a failing file can be traced to the kernel or to the table generator. */
+#define FRP_JPEG_HIST_ELEMS 544
+int frp_encode_jpeg_histograms(frp_handle* h, const int32_t* rects, int32_t n, int32_t quality, int32_t subsampling, int32_t restart_mcus,
+                               uint32_t flags, uint32_t* hist, int64_t hist_elems);
 /* parity: the quantised coefficients of the same rectangles before entropy coding - int16, natural order, per image the layout of
  * frp_jpeg_coefficients (per component [blocks_y][blocks_x][64] over the MCU-padded grid, components back to back), one image after
  * the other; coef_elems must be their exact number */
@@ -606,9 +627,10 @@ typedef struct frp_enhance_params {
 int frp_enhance_pixels(frp_handle* h, const int32_t* rects, const int32_t* sizes, int32_t n, const frp_enhance_params* params, uint32_t flags,
                        uint8_t* out, int64_t out_cap, int64_t* offsets);
 /* the same images as baseline JPEG files - quality, subsampling, restart_mcus, flags, out, out_cap and offsets as in the JPEG encoder,
- * whose checks apply too: byte for byte Pillow's save(quality=q) of the enhanced image (Annex K Huffman tables: against
- * save(quality=q, optimize=True), which the reference writes, every quantised coefficient agrees and the DHT segments and the scan's
- * codes differ).  The encoder reads the enhanced pixels where the enhancer left them: no pixel crosses PCIe between the two. */
+ * whose checks apply too: byte for byte Pillow's save(quality=q) of the enhanced image, with FRP_FLAG_JPEG_OPTIMIZE Pillow's
+ * save(quality=q, optimize=True), which is the file the reference writes (services/enhancer.py:88).  The two differ in the DHT
+ * segments and the scan's codes; every quantised coefficient agrees.  The encoder reads the enhanced pixels where the enhancer left
+ * them: no pixel crosses PCIe between the two. */
 int frp_encode_jpeg_enhanced(frp_handle* h, const int32_t* rects, const int32_t* sizes, int32_t n, const frp_enhance_params* params, int32_t quality,
                              int32_t subsampling, int32_t restart_mcus, uint32_t flags, uint8_t* out, int64_t out_cap, int64_t* offsets);
 

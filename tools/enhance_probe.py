@@ -7,7 +7,9 @@ Per case, after a warm-up of both routes: the device call (a host clock around t
 tables, runs the enhance kernel and the encoder with its two size read-backs, copies the files and waits) and the host route, each
 repeated until half a second has passed and at least 10 times, median and best; the pixel call (frp_enhance_pixels) alone, which
 returns out_w * out_h * 3 bytes over PCIe; the bytes the enhance kernel moves over the achievable HBM rate (its lower bound).  The
-files of both routes are compared on the way.  The kernels' own times come from a run of its own:
+files of both routes are compared on the way.  Three routes side by side for the optimised Huffman tables (optimize=True: the file the
+reference writes): the device call without and with the flag, the bytes each returns, and the host route with save(optimize=True).
+The kernels' own times come from a run of its own:
     rocprofv3 --kernel-trace --stats -d out -o kt -- python3 tools/enhance_probe.py
     python tools/enhance_probe.py"""
 import io
@@ -36,7 +38,7 @@ def timed(fn, min_seconds=0.5, min_runs=10):
     return statistics.median(times), min(times), len(times)
 
 
-def host_route(eng, rects, sizes):
+def host_route(eng, rects, sizes, optimize=False):
     """what the feature replaces: the frames over PCIe, then Pillow on this thread"""
     from PIL import Image, ImageFilter
     frames = eng.get_frames()
@@ -47,7 +49,7 @@ def host_route(eng, rects, sizes):
             im = im.resize(size, Image.BICUBIC)
         im = im.filter(ImageFilter.UnsharpMask(radius=1, percent=120, threshold=3))
         buf = io.BytesIO()
-        im.save(buf, "JPEG", quality=QUALITY)
+        im.save(buf, "JPEG", quality=QUALITY, optimize=optimize)
         out.append(buf.getvalue())
     return out
 
@@ -56,7 +58,12 @@ def case(eng, name, frames, rects, sizes):
     eng.upload_frames(frames)
     files = eng.encode_jpeg_enhanced(rects, sizes, quality=QUALITY)          # warm-up of both routes, and the comparison
     assert host_route(eng, rects, sizes) == files, "device and Pillow files differ"
+    files_opt = eng.encode_jpeg_enhanced(rects, sizes, quality=QUALITY, optimize=True)
+    assert host_route(eng, rects, sizes, optimize=True) == files_opt, "device and Pillow files differ with optimised tables"
     dev = timed(lambda: eng.encode_jpeg_enhanced(rects, sizes, quality=QUALITY))
+    dev_opt = timed(lambda: eng.encode_jpeg_enhanced(rects, sizes, quality=QUALITY, optimize=True))
+    dev_again = timed(lambda: eng.encode_jpeg_enhanced(rects, sizes, quality=QUALITY))       # the spread of the route the flag is held against
+    host_opt = timed(lambda: host_route(eng, rects, sizes, optimize=True))
     pix = timed(lambda: eng.enhance_pixels(rects, sizes))
     host = timed(lambda: host_route(eng, rects, sizes))
     fetch = timed(eng.get_frames)
@@ -66,10 +73,15 @@ def case(eng, name, frames, rects, sizes):
     traffic = 3 * (src_px + out_px)            # compulsory: every source pixel once, every output pixel once (halos come out of L2)
     print(f"{name}: {len(rects)} images, {src_px * 3 / 1e6:.2f} MB of pixels -> {out_px * 3 / 1e6:.2f} MB enhanced -> {out_bytes / 1e6:.2f} MB of JPEG")
     for label, (med, best, runs) in (("device: encode_jpeg_enhanced (tables up, enhance + encoder kernels, files down, wait)", dev),
+                                     ("device: encode_jpeg_enhanced(optimize=True) (+ histogram kernel, counts down, tables up, one more wait)", dev_opt),
+                                     ("device: encode_jpeg_enhanced without the flag, again", dev_again),
+                                     ("host route with save(optimize=True), one thread", host_opt),
                                      ("device: enhance_pixels alone (tables up, enhance kernel, pixels down, wait)", pix),
                                      ("host route: get_frames + Pillow resize + UnsharpMask + save, one thread", host),
                                      ("  of which get_frames (all resident frames over PCIe)", fetch)):
         print(f"  {label:98s} median {med * 1e3:9.3f} ms  best {best * 1e3:9.3f} ms  ({runs} runs)")
+    out_opt = sum(map(len, files_opt))
+    print(f"  bytes returned: {out_bytes / 1e6:.3f} MB without the flag, {out_opt / 1e6:.3f} MB with it ({(out_opt / out_bytes - 1) * 100:+.1f} %)")
     print(f"  enhance kernel traffic {traffic / 1e6:.1f} MB / {HBM_BYTES_PER_S / 1e12:.1f} TB/s (lower bound of the kernel) {traffic / HBM_BYTES_PER_S * 1e3:9.4f} ms")
 
 
